@@ -5,8 +5,11 @@ A "step" renders one full frame of the configuration BASELINE.json quotes the me
 (C1: 1920x1080, 64 spp, 3D isotropic sampling, impulse_density=32, renewal, single realization):
 primary sampleDistance, shading, one shadow transmittance per hit, per-pixel accumulation.
 Inputs (the medium's constants, the guide field, the workspace) are resident in HBM before the timed
-region; `value_cold` is the same frame with every one-off cost inside the timer, `value_unguided` the
-frame without the guide field (every march step evaluated exactly).
+region, and one untimed first frame pays the one-off allocations, so the timed frames are warm at any
+--warmup.  A plain run measures only that headline.  `--full` adds the rest: `value_cold` (the same frame
+with every one-off cost inside the timer), `value_unguided` (the frame without the guide field, every march
+step evaluated exactly, which must equal the guided frame bit for bit), the per-rank spread, the issue
+roofline and the CPU baseline.  `--dump-outputs DIR` writes the last timed frame to DIR/radiance.npy.
 
 `python bench.py --gpus N` starts its own N ranks (one process per GPU, torch.distributed / RCCL): rank 0
 broadcasts the parameter block, the image's 16-pixel tile rows are dealt round-robin to the ranks (the tile
@@ -139,6 +142,17 @@ def cpu_baseline(pkg, params, cores):
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame):
+    """DIR/radiance.npy: the (H, W) float32 frame; above DUMP_LIMIT_BYTES, a fixed sample of it instead (every k-th pixel
+    of the flattened frame, k as small as fits), so that two builds compare output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    k = -(-frame.nbytes // DUMP_LIMIT_BYTES)
+    np.save(os.path.join(out_dir, "radiance.npy"), np.ascontiguousarray(frame if k == 1 else frame.reshape(-1)[::k], dtype=np.float32))
+
+
 def launch_ranks(n_gpus, argv):
     """`python bench.py --gpus N` with no rank environment: start the N ranks ourselves, as CHILD processes of a
     parent that never touches the GPU (no torch.cuda call, no libgpis call: a process that has initialised the
@@ -240,11 +254,14 @@ def main():
                     help="auto: C2 (1D sampling, MIS, conductor) renders through the conductor NEE estimator (gpis_render_scene_s_nee, "
                          "TraceBase.cpp:346-420 / ConductorBsdf.cpp:68-137) as BASELINE.json states it, everything else through scene S's "
                          "Lambert + one shadow ray estimator")
-    ap.add_argument("--guide-cold", default="16:32", help="guide field of the cold frame ('same' = --guide): a one-frame render is fastest "
+    ap.add_argument("--guide-cold", default="16:32", help="--full: guide field of the cold frame ('same' = --guide): a one-frame render is fastest "
                     "with the coarser field (0.07 s to build); the warm frames run on --guide")
     ap.add_argument("--reserve-thread", action="store_true", help="cold frame: gpis_reserve_scene_workspace from a second thread during the guide build")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-unguided", action="store_true", help="skip the extra unguided frame (value_unguided)")
+    ap.add_argument("--full", action="store_true", help="beyond the headline, also measure the cold frame (value_cold), the "
+                    "unguided frame and its bit-identity check, the per-rank spread, the issue roofline and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-unguided", action="store_true", help="--full: skip the extra unguided frame (value_unguided)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame the last timed step rendered to DIR/radiance.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -285,7 +302,9 @@ def main():
         torch.cuda.synchronize()
 
     # ---- cold frame: everything a first frame pays — medium constants + cell table, guide field, the driver's
-    #      workspace (4 GB: a handle's first frame runs in 16 Mi-sample chunks) and the frame itself — inside ONE timer
+    #      workspace (4 GB: a handle's first frame runs in 16 Mi-sample chunks) and the frame itself — inside ONE timer.
+    #      A plain run renders this frame on --guide as untimed set-up; the cold-frame guide resolution is a --full measurement.
+    cold_spec = args.guide_cold if args.full else "same"
     fence()
     t_cold0 = time.perf_counter()
     med = pkg.Medium(params, device=local_rank)
@@ -324,7 +343,7 @@ def main():
         # The cold frame is what a ONE-frame render sees, so it gets the guide resolution that is best for one frame: 16:32
         # builds in 0.07 s instead of 0.23 s and costs 0.04 s of the frame (measured, gpurun session s65); the warm frames
         # below run on --guide, rebuilt outside their timer as a multi-frame render would do once.
-        guide_cold = build_guide_as(args.guide if args.guide_cold == "same" else args.guide_cold)
+        guide_cold = build_guide_as(args.guide if cold_spec == "same" else cold_spec)
         guide_info = guide_cold
 
     surf = np.array(pkg.default_surface_s(), dtype=pkg.SURFACE_S)
@@ -354,7 +373,7 @@ def main():
     cold_parts = {"create_s": t_created - t_cold0, "guide_build_s": guide_info["build_s"] if guide_info else 0.0,
                   "guide": ("%d:%d" % (guide_cold["half_extent_cells"], guide_cold["points_per_cell"])) if guide_cold else None,
                   "first_frame_s": time.perf_counter() - t_first0}      # the first frame runs in 16 Mi-sample chunks (4 GB workspace)
-    if guide_cold is not None and args.guide_cold != "same" and args.guide_cold != args.guide:
+    if guide_cold is not None and cold_spec != "same" and cold_spec != args.guide:
         guide_info = build_guide_as(args.guide)                           # the resolution of the warm frames; not timed
         cold_parts["guide_upgrade_s"] = guide_info["build_s"]
 
@@ -362,8 +381,9 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    med.reset_counters()
-    med.set_profiling(True)
+    if args.full:
+        med.reset_counters()
+        med.set_profiling(True)
     del rank_stats[:]
     fence()
     t0 = time.perf_counter()
@@ -371,33 +391,38 @@ def main():
         step()
     fence()
     dt = time.perf_counter() - t0
-    med.set_profiling(False)
+    if args.full:
+        med.set_profiling(False)
+    # what a caller of the timed path receives: the frame of the last timed step (assembled on rank 0)
+    frame = rad.cpu().numpy().reshape(H, W) if args.dump_outputs and rank == 0 else None
 
     tt = torch.tensor([dt, dt_cold], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt_max, dt_cold_max = float(tt[0].item()), float(tt[1].item())
-    # per-rank diagnostics (N > 1): every rank's own render and collective time per frame and its guide-field build, so that an
-    # imbalance of the interleaved tile rows or one slow guide build is visible behind the max-over-ranks metric
-    mine = torch.tensor([sum(r["render_s"] for r in rank_stats) / max(len(rank_stats), 1) * 1e3,
-                         sum(r["collective_s"] for r in rank_stats) / max(len(rank_stats), 1) * 1e3,
-                         guide_info["build_s"] if guide_info else 0.0, float(rank_stats[-1]["wire_bytes"]) if rank_stats else 0.0], dtype=torch.float64, device="cuda")
-    per_rank = [torch.zeros_like(mine) for _ in range(world)]
-    if world > 1:
-        dist.all_gather(per_rank, mine)
-    else:
-        per_rank = [mine]
-    per_rank = [[float(v) for v in t.cpu()] for t in per_rank]
+    per_rank = None
+    if args.full:
+        # per-rank diagnostics (N > 1): every rank's own render and collective time per frame and its guide-field build, so that an
+        # imbalance of the interleaved tile rows or one slow guide build is visible behind the max-over-ranks metric
+        mine = torch.tensor([sum(r["render_s"] for r in rank_stats) / max(len(rank_stats), 1) * 1e3,
+                             sum(r["collective_s"] for r in rank_stats) / max(len(rank_stats), 1) * 1e3,
+                             guide_info["build_s"] if guide_info else 0.0, float(rank_stats[-1]["wire_bytes"]) if rank_stats else 0.0], dtype=torch.float64, device="cuda")
+        per_rank = [torch.zeros_like(mine) for _ in range(world)]
+        if world > 1:
+            dist.all_gather(per_rank, mine)
+        else:
+            per_rank = [mine]
+        per_rank = [[float(v) for v in t.cpu()] for t in per_rank]
 
-    prof = [med.kernel_profile(k) for k in (0, 1)]     # (ms, launches, n_eval, n_seg)
-    prof_nee = med.kernel_profile(2) if use_nee else None
-    n_guide = med.guide_steps() if guide_info else 0
+        prof = [med.kernel_profile(k) for k in (0, 1)]     # (ms, launches, n_eval, n_seg)
+        prof_nee = med.kernel_profile(2) if use_nee else None
+        n_guide = med.guide_steps() if guide_info else 0
 
     # ---- the same frame without the guide field: every march step evaluated exactly (N = 1 only; one frame) — and the
     #      run's own parity check: the guided frame that was timed must equal this one bit for bit (the certificate only ever
     #      replaces evaluations whose sign it has proven, SCNM.cpp:132-174), otherwise the bench fails
     dt_unguided, frame_bit_identical = None, None
-    if guide_info and world == 1 and not args.no_unguided:
+    if args.full and guide_info and world == 1 and not args.no_unguided:
         rad_guided = rad.clone()
         med.drop_guide()
         fence()
@@ -413,21 +438,37 @@ def main():
     if rank == 0:
         samples_per_step = W * H * pkg.dist.total_spp(scene, world, args.shard)
         total_samples = samples_per_step * args.steps
-        b_eval = algorithmic_bytes_per_eval(params)
-        names = ("sample_distance", "transmittance")
-        dom = 0 if prof[0][0] >= prof[1][0] else 1
-        ms, launches, n_eval, n_seg = prof[dom]
-        n_eval_all = prof[0][2] + prof[1][2]
-        n_seg_all = prof[0][3] + prof[1][3]
         fast = int(med.derived()["fast_path"])
         persistent = (not fast) and med.get_option("persistent") == 1
-        kernel = ("k_guided_" if guide_info else ("k_fast_" if fast else ("k_persist_march_" if persistent else "k_"))) + names[dom]
-        workload_key = "%s %dx%dx%d guide %s n_gpus %d" % (args.config, W, H, spp, ("%d:%d" % (guide_info["half_extent_cells"], guide_info["points_per_cell"])) if guide_info else "off", world)
-        roof = issue_roofline(kernel, workload_key, ms / max(launches, 1), med.L.path)
-        if roof is None:
-            roof = {"bound": "valu_issue", "kernel": kernel, "achieved": None, "peak": N_SIMD * PEAK_CLOCK_HZ / 1e12, "unit": "T SIMD issue cycles/s",
-                    "frac": None, "traffic": None, "note": "profiles/r02_issue_model.json not found"}
-        if True:
+        res = {
+            "metric": "Msamples/s (primary rays x spp / s)", "value": total_samples / dt_max / 1e6, "unit": "Msamples/s",
+            "n_gpus": world, "ranks_seen": dist.get_world_size() if world > 1 else 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt_max / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak" if args.shard == "spp" else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "%s: scene S %dx%d, %d spp, SparseConvolutionNoiseMedium (3D isotropic, "
+                                   "impulse_density=%d, ctx=renewal, single_realization)" % (args.config, W, H, spp, int(params["impulse_density"]))
+                       if args.config == "C1" else
+                       ("C2: scene S %dx%d, %d spp, 1D sampling, 1D_sampling_scheme=mis (NEE on), Renewal+ memory, conductor BSDF "
+                        "(gpis_render_scene_s_nee: volumeLightSample + volumePhaseSample with neePDF / neeGrad, one cap light)" % (W, H, spp)
+                        if use_nee else "%s: scene S %dx%d, %d spp" % (args.config, W, H, spp)),
+                       "estimator": "conductor NEE / MIS (TraceBase.cpp:346-420, ConductorBsdf.cpp:68-137)" if use_nee else "Lambert + one shadow ray",
+                       "sharding": ("%s: %d-pixel tile rows dealt round-robin, one batch per rank, one gather of the disjoint tile rows to rank 0" % (args.shard, pkg.dist.rows_tile(scene, world))
+                                    if args.shard == "rows" else "spp slices per rank + reduce(sum) to rank 0") if world > 1 else "single GPU",
+                       "kernel_path": ("guided (certified guide field + wave-cooperative exact evaluations)" if guide_info else
+                                       "fast (wave-cooperative)") if fast else ("per-path: persistent refilling march" if persistent else "per-path: one ray per lane"),
+                       "guide": guide_info},
+        }
+        if args.full:
+            b_eval = algorithmic_bytes_per_eval(params)
+            names = ("sample_distance", "transmittance")
+            dom = 0 if prof[0][0] >= prof[1][0] else 1
+            ms, launches, n_eval, n_seg = prof[dom]
+            n_eval_all = prof[0][2] + prof[1][2]
+            kernel = ("k_guided_" if guide_info else ("k_fast_" if fast else ("k_persist_march_" if persistent else "k_"))) + names[dom]
+            workload_key = "%s %dx%dx%d guide %s n_gpus %d" % (args.config, W, H, spp, ("%d:%d" % (guide_info["half_extent_cells"], guide_info["points_per_cell"])) if guide_info else "off", world)
+            roof = issue_roofline(kernel, workload_key, ms / max(launches, 1), med.L.path)
+            if roof is None:
+                roof = {"bound": "valu_issue", "kernel": kernel, "achieved": None, "peak": N_SIMD * PEAK_CLOCK_HZ / 1e12, "unit": "T SIMD issue cycles/s",
+                        "frac": None, "traffic": None, "note": "profiles/r02_issue_model.json not found"}
             roof["kernel_ms"] = {names[0]: prof[0][0] / max(prof[0][1], 1), names[1]: prof[1][0] / max(prof[1][1], 1)}     # per launch
             if prof_nee:
                 # per frame: the march kernels (one sampleDistance, two masked transmittance launches) and the two k_nee launches
@@ -443,39 +484,27 @@ def main():
                                    "certified_steps": n_guide,
                                    "reference_equivalent_evals_per_s": (n_eval_all + n_guide) / dt_max,
                                    "doc": "exact evaluations the kernels performed; a certified march step stands for one evaluateValue of the reference"}
-        res = {
-            "metric": "Msamples/s (primary rays x spp / s)", "value": total_samples / dt_max / 1e6, "unit": "Msamples/s",
-            "value_cold": samples_per_step / dt_cold_max / 1e6,
-            "value_unguided": (samples_per_step / dt_unguided / 1e6) if dt_unguided else None,
-            "frame_bit_identical": frame_bit_identical,
-            "n_gpus": world, "ranks_seen": dist.get_world_size() if world > 1 else 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt_max / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak" if args.shard == "spp" else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s: scene S %dx%d, %d spp, SparseConvolutionNoiseMedium (3D isotropic, "
-                                   "impulse_density=%d, ctx=renewal, single_realization)" % (args.config, W, H, spp, int(params["impulse_density"]))
-                       if args.config == "C1" else
-                       ("C2: scene S %dx%d, %d spp, 1D sampling, 1D_sampling_scheme=mis (NEE on), Renewal+ memory, conductor BSDF "
-                        "(gpis_render_scene_s_nee: volumeLightSample + volumePhaseSample with neePDF / neeGrad, one cap light)" % (W, H, spp)
-                        if use_nee else "%s: scene S %dx%d, %d spp" % (args.config, W, H, spp)),
-                       "estimator": "conductor NEE / MIS (TraceBase.cpp:346-420, ConductorBsdf.cpp:68-137)" if use_nee else "Lambert + one shadow ray",
-                       "sharding": ("%s: %d-pixel tile rows dealt round-robin, one batch per rank, one gather of the disjoint tile rows to rank 0" % (args.shard, pkg.dist.rows_tile(scene, world))
-                                    if args.shard == "rows" else "spp slices per rank + reduce(sum) to rank 0") if world > 1 else "single GPU",
-                       "kernel_path": ("guided (certified guide field + wave-cooperative exact evaluations)" if guide_info else
-                                       "fast (wave-cooperative)") if fast else ("per-path: persistent refilling march" if persistent else "per-path: one ray per lane"),
-                       "guide": guide_info,
-                       "value_cold_doc": "one frame with gpis_create (cell table), the guide-field build (--guide-cold: the resolution that is fastest for a single frame) and the workspace allocation inside the timer (%.2f s)" % dt_cold_max,
-                       "value_cold_parts": cold_parts,
-                       "value_unguided_doc": "one frame after gpis_drop_guide: every march step is an exact wave-cooperative evaluation" if dt_unguided else None},
-            "roofline": roof,
-            "per_rank": None if world == 1 else {
-                "render_ms": {"min": min(p[0] for p in per_rank), "max": max(p[0] for p in per_rank), "mean": sum(p[0] for p in per_rank) / world, "all": [p[0] for p in per_rank]},
-                "collective_ms": {"max": max(p[1] for p in per_rank), "all": [p[1] for p in per_rank]},
-                "guide_build_s": [p[2] for p in per_rank], "wire_bytes_per_frame": [int(p[3]) for p in per_rank],
-                "doc": "each rank's own clock around its share of a frame (device synchronised) and around the gather / reduce"},
-        }
-        if not args.no_cpu_baseline and world == 1:
-            cores = usable_cores()
-            res["cpu_baseline"] = cpu_baseline(pkg, params, cores)
-            res["gpu_over_cpu"] = res["value"] / res["cpu_baseline"]["value"]
+            res.update({
+                "value_cold": samples_per_step / dt_cold_max / 1e6,
+                "value_unguided": (samples_per_step / dt_unguided / 1e6) if dt_unguided else None,
+                "frame_bit_identical": frame_bit_identical,
+                "roofline": roof,
+                "per_rank": None if world == 1 else {
+                    "render_ms": {"min": min(p[0] for p in per_rank), "max": max(p[0] for p in per_rank), "mean": sum(p[0] for p in per_rank) / world, "all": [p[0] for p in per_rank]},
+                    "collective_ms": {"max": max(p[1] for p in per_rank), "all": [p[1] for p in per_rank]},
+                    "guide_build_s": [p[2] for p in per_rank], "wire_bytes_per_frame": [int(p[3]) for p in per_rank],
+                    "doc": "each rank's own clock around its share of a frame (device synchronised) and around the gather / reduce"},
+            })
+            res["config"].update({
+                "value_cold_doc": "one frame with gpis_create (cell table), the guide-field build (--guide-cold: the resolution that is fastest for a single frame) and the workspace allocation inside the timer (%.2f s)" % dt_cold_max,
+                "value_cold_parts": cold_parts,
+                "value_unguided_doc": "one frame after gpis_drop_guide: every march step is an exact wave-cooperative evaluation" if dt_unguided else None})
+            if not args.no_cpu_baseline and world == 1:
+                cores = usable_cores()
+                res["cpu_baseline"] = cpu_baseline(pkg, params, cores)
+                res["gpu_over_cpu"] = res["value"] / res["cpu_baseline"]["value"]
+        if frame is not None:
+            dump_outputs(args.dump_outputs, frame)
         print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()

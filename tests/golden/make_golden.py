@@ -8,6 +8,9 @@ Two kinds of vectors (the reference ships no tests, fixtures or scenes for this 
   ref_primitives.npz   produced by the REAL reference compiled in place (oracle/_ref: its own
                        MathUtil.hpp / UniformSampler.hpp / TangentFrame.hpp / Gaussian.cpp):
                        xxhash32 x4, PCG32 streams, the per-impulse draw order, Duff ONB, Box–Muller.
+  ref_pins.npz         produced by the REAL reference compiled in place: the inputs and reference outputs that
+                       tests/test_oracle_vs_ref.py pins the oracle's integer layer, ONB, Box–Muller, Eigen expression
+                       forms and Fresnel / MIS arithmetic to.
   ref_fs_primitives.npz  produced by the REAL reference compiled in place: Eigen's SelfAdjointEigenSolver / LLT, the
                        MultivariateNormalDistribution of sampling/Gaussian.cpp, pseudo-inverse / conditioning product forms,
                        rand_truncated_normal, fbm / simplex3d / random3 of math/SdfFunctions.cpp.
@@ -81,6 +84,112 @@ def ref_primitives():
     cap_in = rng.uniform(-0.99, 0.9999, 128).astype(f32)
     out.update(cap_pdf_in=cap_in, cap_pdf_out=np.array([ref.ref_uniform_spherical_cap_pdf(float(c)) for c in cap_in], dtype=f32))
     np.savez_compressed(os.path.join(HERE, "ref_primitives.npz"), **out)
+
+
+def ref_pins():
+    """ref_pins.npz — inputs and the REAL reference's outputs (oracle/_ref) for tests/test_oracle_vs_ref.py: xxhash32 x4,
+    PCG32 streams and float conversion, the per-impulse draw order, Duff ONB and frame transforms, Box–Muller, the Eigen
+    expression forms of the evaluator, and the conductor NEE estimator's Fresnel / MIS arithmetic."""
+    ref = ob.ref_lib()
+    assert ref is not None, "oracle/_ref must be built (needs /root/reference)"
+    out = {}
+    # xxhash32, every arity
+    rng = np.random.default_rng(1)
+    edge = np.array([0, 1, 2, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF, 0xBA5EBA11, 7], dtype=np.uint32)
+    for arity in (1, 2, 3, 4):
+        words = rng.integers(0, 2 ** 32, size=(4000, arity), dtype=np.uint64).astype(np.uint32)
+        words[:64] = rng.choice(edge, size=(64, arity))
+        fn = getattr(ref, "ref_xxhash32_%d" % arity)
+        out["xxhash%d_in" % arity] = words
+        out["xxhash%d_out" % arity] = np.array([fn(*[int(w) for w in row]) for row in words], dtype=np.uint32)
+    # PCG32 streams, normalizedUint, Bernoulli sign
+    rng = np.random.default_rng(2)
+    states = rng.integers(0, 2 ** 63, size=200, dtype=np.uint64)
+    states[:4] = [0, 1, 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF]
+    streams = np.zeros((200, 64), dtype=np.uint32)
+    for i, s in enumerate(states):
+        ref.ref_pcg32_stream(ctypes.c_uint64(int(s)), 64, P(streams[i]))
+    ints = np.concatenate([streams.ravel()[:2000], np.array([0, 1, 511, 512, 2 ** 32 - 1], dtype=np.uint32)])
+    bern_in = np.array([0.0, 0.25, 0.49999997, 0.5, 0.50000006, 0.99999994], dtype=f32)
+    out.update(pcg_state=states, pcg_stream=streams, normalized_uint_in=ints,
+               normalized_uint_out=np.array([ref.ref_normalized_uint(int(v)) for v in ints], dtype=f32),
+               bernoulli_in=bern_in, bernoulli_out=np.array([ref.ref_bernoulli(float(v)) for v in bern_in], dtype=f32))
+    # next3D() draw order of the per-impulse sampler
+    cell_states = np.array([1, 12345, 0xDEADBEEF, 2 ** 40 + 17], dtype=np.uint64)
+    cell = np.zeros((4, 4 * 32), dtype=f32)
+    for i, s in enumerate(cell_states):
+        ref.ref_cell3d_draws(ctypes.c_uint64(int(s)), 32, P(cell[i]))
+    out.update(cell3d_state=cell_states, cell3d_draws=cell)
+    # TangentFrame (Duff ONB), toLocal / toGlobal, Vec3f::normalized
+    rng = np.random.default_rng(3)
+    ns = rng.standard_normal((500, 3)).astype(f32)
+    ns[:6] = [[0, 0, 1], [0, 0, -1], [1, 0, 0], [0, 1, 0], [1e-8, 0, -1], [0.3, -0.4, -0.0]]
+    ps = np.zeros((500, 3), dtype=f32)
+    fr = {k: np.zeros((500, 9 if k == "tangent_frame" else 3), dtype=f32) for k in ("tangent_frame", "frame_to_local", "frame_to_global", "vec3_normalized")}
+    for i, n in enumerate(ns):
+        ref.ref_tangent_frame(P(n), P(fr["tangent_frame"][i]))
+        ps[i] = rng.standard_normal(3).astype(f32)
+        for fn in ("frame_to_local", "frame_to_global"):
+            getattr(ref, "ref_" + fn)(P(n), P(ps[i]), P(fr[fn][i]))
+        ref.ref_vec3_normalized(P(n), P(fr["vec3_normalized"][i]))
+    out.update(frame_n=ns, frame_p=ps, **{"frame_" + k: v for k, v in fr.items()})
+    # Box–Muller
+    bm_states = np.array([3, 99, 0xABCDEF, 2 ** 50 + 1], dtype=np.uint64)
+    bm2, xy = np.zeros((4, 8)), np.zeros((4, 2))
+    for i, s in enumerate(bm_states):
+        ref.ref_sample_standard_normal2(ctypes.c_uint64(int(s)), 4, P(bm2[i]))
+        ref.ref_sample_xy_over_sqrt2(ctypes.c_uint64(int(s)), P(xy[i]))
+    out.update(box_muller_state=bm_states, box_muller_normal2=bm2, box_muller_xy_over_sqrt2=xy)
+    # the Eigen expression forms
+    rng = np.random.default_rng(4)
+    N = 1500
+    e_in = {k: np.zeros((N,) + sh, dtype=f32) for k, sh in (("ab", (3,)), ("M", (9,)), ("s", ()), ("B", (9,)))}
+    e_out = {k: np.zeros((N,) + sh, dtype=f32) for k, sh in (
+        ("dist2_ab", ()), ("dot_col", (3,)), ("matvec_div", (3,)), ("matvec_mul", (3,)), ("matvec", (3,)), ("inverse3", (9,)),
+        ("second_deriv_inv", (9,)), ("scaled_matmul", (9,)), ("gram", (9,)), ("gram_det", ()), ("scale_and_inverse", (2, 9)),
+        ("invcov_scale", (2, 9)))}
+    for it in range(N):
+        ab = rng.standard_normal(3).astype(f32)
+        M = rng.standard_normal(9).astype(f32)
+        if it % 3 == 0:   # diagonal matrices as in useAnisoMtx=false
+            M = np.diag(rng.uniform(0.1, 30, 3)).astype(f32).ravel()
+        s = ctypes.c_float(float(rng.uniform(0.3, 3)))
+        B = rng.standard_normal(9).astype(f32)
+        e_in["ab"][it], e_in["M"][it], e_in["s"][it], e_in["B"][it] = ab, M, s.value, B
+        o = {k: v[it] for k, v in e_out.items()}
+        e_out["dist2_ab"][it] = ref.ref_eig_dist2_ab(P(ab), P(M))
+        for c in range(3):
+            o["dot_col"][c] = ref.ref_eig_dot_col(P(ab), P(M), c)
+        for fn in ("matvec_div", "matvec_mul"):
+            getattr(ref, "ref_eig_" + fn)(P(M), P(ab), s, P(o[fn]))
+        ref.ref_eig_matvec(P(M), P(ab), P(o["matvec"]))
+        for fn in ("inverse3", "second_deriv_inv"):
+            getattr(ref, "ref_eig_" + fn)(P(M), P(o[fn]))
+        ref.ref_eig_scaled_matmul(ctypes.c_float(0.37), P(M), P(B), P(o["scaled_matmul"]))
+        det = ctypes.c_float()
+        ref.ref_eig_gram(P(M), P(o["gram"]), ctypes.byref(det))
+        e_out["gram_det"][it] = det.value
+        ref.ref_eig_scale_and_inverse(ctypes.c_float(0.0354), P(M), P(o["scale_and_inverse"][0]), P(o["scale_and_inverse"][1]))
+        for is_cov in (0, 1):
+            ref.ref_eig_invcov_scale(P(M), ctypes.c_float(1.7), ctypes.c_float(0.6), is_cov, P(o["invcov_scale"][is_cov]))
+    out.update({"eig_in_" + k: v for k, v in e_in.items()})
+    out.update({"eig_" + k: v for k, v in e_out.items()})
+    # Fresnel.hpp conductor reflectance, SampleWarp.hpp power heuristic and uniform spherical cap pdf
+    for n, k in (("ref_conductor_reflectance", 3), ("ref_power_heuristic", 2), ("ref_uniform_spherical_cap_pdf", 1)):
+        getattr(ref, n).restype = ctypes.c_float
+        getattr(ref, n).argtypes = [ctypes.c_float] * k
+    rng = np.random.default_rng(5)
+    rows = []
+    for eta, k in ((0.2, 3.9), (1.5, 0.0), (0.0, 0.0), (2.9, 3.1), (0.05, 7.0)):
+        for c in np.concatenate([rng.uniform(-1, 1, 400), [0.0, 1.0, -1.0, 1e-6, 0.999999]]).astype(f32):
+            rows.append((eta, k, c))
+    fresnel_in = np.array(rows, dtype=f32)
+    ph_in = rng.uniform(0, 50, (2000, 2)).astype(f32)
+    cap_in = rng.uniform(-0.99, 0.9999, 500).astype(f32)
+    out.update(fresnel_in=fresnel_in, fresnel_out=np.array([ref.ref_conductor_reflectance(*map(float, r)) for r in fresnel_in], dtype=f32),
+               power_heuristic_in=ph_in, power_heuristic_out=np.array([ref.ref_power_heuristic(*map(float, r)) for r in ph_in], dtype=f32),
+               cap_pdf_in=cap_in, cap_pdf_out=np.array([ref.ref_uniform_spherical_cap_pdf(float(c)) for c in cap_in], dtype=f32))
+    np.savez_compressed(os.path.join(HERE, "ref_pins.npz"), **out)
 
 
 def _se(x, y=None, l=0.05, s2=0.01):
@@ -257,6 +366,7 @@ def reference_kat():
 if __name__ == "__main__":
     ob.build()
     ref_primitives()
+    ref_pins()
     ref_fs_primitives()
     reference_kat()
     oracle_vectors()
