@@ -616,6 +616,78 @@ int gpis_render_scene_s_nee(gpis_medium *m, const gpis_scene_s *s, const gpis_su
 int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo,
                               float *radiance_sum, void *stream);
 
+/* ---- weight-space GP medium (WeightSpaceGaussianProcessMedium.cpp, WeightSpaceGaussianProcess.cpp) --------------------
+ * The field of one realization is  f(p) = sqrt(cov(p,p)) * (sqrt(2/N) * sum_i w_i cos((d_i . p) * omega_i + phi_i)) + mean(p)
+ * with N random Fourier features of the squared-exponential covariance (WSG:120-127, 160-240).  A realization is fixed by the
+ * pixelSampleSegment word pss = (pixel.x, pixel.y, spp, segment): the basis (phi_i, then the spectral sample d_i * omega_i,
+ * 5 uniforms per function) comes from a PCG32 stream seeded with xxhash32(pss), the weights w_i (standard normals, pairs of
+ * Box–Muller) from a stream seeded with seed + xxhash32(pss).  single_realization: pss = (0,0,0,0) for every ray; correlation
+ * context GLOBAL: pss.w = 0; the other contexts: a new realization on every segment (WSM:159-180).
+ *
+ * gpis_ws_create reads these fields of gpis_params: step_size (> 0; 0 is the affine-arithmetic sphere trace, refused), min_step,
+ * seed, single_realization, correlation_context, max_bounces, sigma_a, sigma_s, density, sigma, length_scale, aniso, mean,
+ * has_mean_additional, mean_additional, mean_color (ramp types only), kernel_type (squared exponential only), nonstationary and
+ * grid_nonstationary (must be 0).  use_aniso_mtx / aniso_mtx are accepted and ignored: the reference's spectral sampler reads only
+ * the "aniso" vector (GPF.hpp:1812-1815).  Everything else of gpis_params is ignored.
+ * Refused with GPIS_ERR_UNSUPPORTED: step_size == 0, kernels other than squared exponential and the non-stationary wrappers
+ * (their spectral samplers draw from std::mt19937 / std::gamma_distribution), normal methods beckmann / ggx, intersect method
+ * mean, basis_functions outside 0..GPIS_WS_MAX_BASIS.
+ *
+ * rays[i].u_jitter is the one sampler.next1D() of the march (WSM:247).  All results are bit-identical to the reference's double
+ * evaluation.  The device restates glibc's cos / sin for |x| < 105414350 only: an entry for which one of the evaluations the
+ * reference performs met a larger argument returns GPIS_ERR_UNSUPPORTED (results are written but must not be used); march points
+ * the device evaluated ahead and discarded do not count.  For that check the ws batch entries synchronise `stream` before they
+ * return.  min_step 0 is accepted with the reference's arithmetic: (far - near) / 0.0f is +inf (the step is step_size), or NaN
+ * when far == near (no march point). */
+#define GPIS_WS_PARAMS_VERSION 1
+#define GPIS_WS_MAX_BASIS 1024
+typedef enum gpis_normal_method {
+    GPIS_NORMAL_CONDITIONED_GAUSSIAN = 0,   /* "conditioned_gaussian": the analytic gradient of the realization (WSG:50-76) */
+    GPIS_NORMAL_FINITE_DIFFERENCES = 1,     /* "finite_differences": central differences, float eps = 1e-4 (WSM:89-114) */
+    GPIS_NORMAL_BECKMANN = 2,               /* refused */
+    GPIS_NORMAL_GGX = 3                     /* refused */
+} gpis_normal_method;
+typedef enum gpis_intersect_method { GPIS_INTERSECT_GP_DISCRETE = 0, GPIS_INTERSECT_MEAN = 1 /* refused */ } gpis_intersect_method;
+typedef struct gpis_ws_params {
+    uint32_t version;                /* must be GPIS_WS_PARAMS_VERSION */
+    int32_t basis_functions;         /* "basis_functions" (0 .. GPIS_WS_MAX_BASIS; default 300; 0 = the mean alone) */
+    int32_t normal_method;           /* "normal_method" gpis_normal_method */
+    int32_t intersect_method;        /* "intersect_method" gpis_intersect_method */
+    int32_t _pad[4];
+} gpis_ws_params;
+/* One point query of gpis_ws_eval_batch: the realization of (pixel, spp, segment) under the medium's rule above.  48 bytes. */
+typedef struct gpis_ws_query {
+    double p[3];
+    uint32_t pixel[2];
+    uint32_t spp;
+    uint32_t segment;
+    uint32_t _pad[2];
+} gpis_ws_query;
+
+/* Fills `p` with the reference's defaults (WSM:21-32, GPM.cpp:86-95). */
+void gpis_ws_default_params(gpis_ws_params *p);
+/* WeightSpaceGaussianProcessMedium::fromJson + prepareForRender.  For single_realization the global basis is built on the device
+ * here.  The handle is freed by gpis_destroy; it is accepted by the gpis_ws_* entries only (the other entries return
+ * GPIS_ERR_INVALID_ARG for it, and the gpis_ws_* entries for any other handle). */
+int gpis_ws_create(const gpis_params *params, const gpis_ws_params *ws, int device, gpis_medium **out);
+/* Medium::sampleDistance / transmittance (GPM.cpp:221-393 over WSM:64-291), device pointers, one wave per segment. */
+int gpis_ws_sample_distance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, void *stream);
+int gpis_ws_transmittance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, uint8_t *visible, void *stream);
+/* The same for host pointers (synchronous; what integration/HipWeightSpaceMedium.cpp calls with a batch of one). */
+int gpis_ws_sample_distance_host(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out);
+int gpis_ws_transmittance_host(gpis_medium *m, size_t n, const gpis_ray_in *rays, uint8_t *visible);
+/* Test surface: WeightSpaceRealization::evaluate (value, gp id) and the medium's normal method's gradient (evaluateGradient, or
+ * the six-point finite differences) at q[i].p.  Device pointers; value, grad3 (xyz triples) and gp_id may each be NULL. */
+int gpis_ws_eval_batch(gpis_medium *m, size_t n, const gpis_ws_query *q, double *value, double *grad3, int32_t *gp_id, void *stream);
+/* Test surface: the basis and weights of n realizations.  pss4: n words (pixel.x, pixel.y, spp, segment), mapped by the medium's
+ * rule above; out: n x N records of 6 doubles (d.x, d.y, d.z, omega, phi, w) in basis order.  Device pointers. */
+int gpis_ws_basis_batch(gpis_medium *m, size_t n, const uint32_t *pss4, double *out, void *stream);
+/* Evaluations the reference performs (n_eval: value evaluations of the march, gradient evaluations counted once, finite
+ * differences six times), evaluations the device computed (n_spec >= n_eval: speculative march positions included) and
+ * segments since the last reset.  Synchronises the device. */
+int gpis_ws_get_counters(gpis_medium *m, uint64_t *n_eval, uint64_t *n_spec, uint64_t *n_seg);
+int gpis_ws_reset_counters(gpis_medium *m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,12 +157,41 @@ def default_surface_s():
     return s
 
 
+# ---- weight-space GP medium (include/gpis.h: gpis_ws_*) ----
+WS_MAX_BASIS = 1024
+
+
+class NORMAL:
+    CONDITIONED_GAUSSIAN, FINITE_DIFFERENCES, BECKMANN, GGX = 0, 1, 2, 3
+
+
+class INTERSECT:
+    GP_DISCRETE, MEAN = 0, 1
+
+
+WS_PARAMS = np.dtype([
+    ("version", "<u4"), ("basis_functions", "<i4"), ("normal_method", "<i4"), ("intersect_method", "<i4"), ("_pad", "<i4", 4),
+], align=True)
+WS_QUERY = np.dtype([("p", "<f8", 3), ("pixel", "<u4", 2), ("spp", "<u4"), ("segment", "<u4"), ("_pad", "<u4", 2)], align=True)
+
+
+def default_ws_params(basis_functions=300, normal_method=NORMAL.CONDITIONED_GAUSSIAN):
+    """The weight-space medium's own keys with the reference's defaults (WSM:21-32, GPM.cpp:86-95)."""
+    w = np.zeros((), dtype=WS_PARAMS)
+    w["version"] = 1
+    w["basis_functions"] = basis_functions
+    w["normal_method"] = normal_method
+    w["intersect_method"] = INTERSECT.GP_DISCRETE
+    return w
+
+
 _EXPECTED_SIZES = {
     "gpis_params": PARAMS.itemsize, "gpis_mean": MEAN.itemsize, "gpis_ray_in": RAY_IN.itemsize,
     "gpis_seg_out": SEG_OUT.itemsize, "gpis_cond_coeff": COND_COEFF.itemsize, "gpis_query": QUERY.itemsize,
     "gpis_nee_query": NEE_QUERY.itemsize, "gpis_derived": DERIVED.itemsize, "gpis_scene_s": SCENE_S.itemsize,
     "gpis_surface_s": SURFACE_S.itemsize, "gpis_ramp": RAMP.itemsize,
     "gpis_fs_state": FS_STATE.itemsize, "gpis_guide_info": GUIDE_INFO.itemsize,
+    "gpis_ws_params": WS_PARAMS.itemsize, "gpis_ws_query": WS_QUERY.itemsize,
 }
 assert RAY_IN.itemsize == 128 and SEG_OUT.itemsize == 96 and COND_COEFF.itemsize == 32
 assert QUERY.itemsize == 96 and NEE_QUERY.itemsize == 96
@@ -303,6 +332,9 @@ class GpisLib:
         "gpis_get_counters", "gpis_reset_counters", "gpis_set_profiling", "gpis_get_kernel_profile",
         "gpis_set_batch_order", "gpis_set_option", "gpis_get_option", "gpis_build_guide", "gpis_drop_guide", "gpis_get_guide_info", "gpis_get_guide_steps", "gpis_guide_selfcheck", "gpis_guide_raycheck",
         "gpis_set_variance_grid", "gpis_default_scene_s", "gpis_reserve_scene_workspace", "gpis_render_scene_s", "gpis_render_scene_s_paths", "gpis_render_scene_s_nee",
+        "gpis_ws_default_params", "gpis_ws_create", "gpis_ws_sample_distance_batch", "gpis_ws_transmittance_batch",
+        "gpis_ws_sample_distance_host", "gpis_ws_transmittance_host", "gpis_ws_eval_batch", "gpis_ws_basis_batch",
+        "gpis_ws_get_counters", "gpis_ws_reset_counters",
     ]
 
     def __init__(self, path=None):
@@ -375,6 +407,17 @@ class GpisLib:
         L.gpis_render_scene_s.argtypes = [vp, vp, vp, vp, vp]
         L.gpis_render_scene_s_paths.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
         L.gpis_render_scene_s_nee.argtypes = [vp, vp, vp, vp, vp]
+        L.gpis_ws_default_params.argtypes = [vp]
+        L.gpis_ws_default_params.restype = None
+        L.gpis_ws_create.argtypes = [vp, vp, i32, ctypes.POINTER(vp)]
+        L.gpis_ws_sample_distance_batch.argtypes = [vp, sz, vp, vp, vp]
+        L.gpis_ws_transmittance_batch.argtypes = [vp, sz, vp, vp, vp]
+        L.gpis_ws_sample_distance_host.argtypes = [vp, sz, vp, vp]
+        L.gpis_ws_transmittance_host.argtypes = [vp, sz, vp, vp]
+        L.gpis_ws_eval_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+        L.gpis_ws_basis_batch.argtypes = [vp, sz, vp, vp, vp]
+        L.gpis_ws_get_counters.argtypes = [vp, vp, vp, vp]
+        L.gpis_ws_reset_counters.argtypes = [vp]
         if hasattr(L, "gpis_abi_sizes"):
             L.gpis_abi_sizes.restype = ctypes.c_char_p
             got = dict(kv.split("=") for kv in L.gpis_abi_sizes().decode().split(","))
@@ -646,3 +689,108 @@ class Medium:
         fn = getattr(self.L.lib, name)
         conv = [(_ptr(a) if (a is None or isinstance(a, np.ndarray)) else a) for a in args]
         self.L.check(fn(self.h, *conv), name)
+
+
+class WeightSpaceMedium:
+    """Handle of the weight-space GP medium (gpis_ws_create): numpy in / numpy out.  sample_distance / transmittance go through
+    the *_host entries; eval / basis (test surfaces) and the *_batch forms through torch device buffers."""
+
+    def __init__(self, params, ws_params=None, device=0, lib=None):
+        self.L = lib or load_library()
+        self.params = as_params(params)
+        self.ws_params = np.array(ws_params if ws_params is not None else default_ws_params(), dtype=WS_PARAMS).reshape(())
+        self.device = int(device)
+        self.h = None
+        h = ctypes.c_void_p()
+        self.L.check(self.L.lib.gpis_ws_create(_ptr(self.params), _ptr(self.ws_params), int(device), ctypes.byref(h)), "gpis_ws_create")
+        self.h = h
+
+    @property
+    def n_basis(self):
+        return int(self.ws_params["basis_functions"])
+
+    def close(self):
+        if self.h:
+            self.L.lib.gpis_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sample_distance(self, rays):
+        rays = np.ascontiguousarray(rays, dtype=RAY_IN)
+        out = np.zeros(rays.shape[0], dtype=SEG_OUT)
+        self.L.check(self.L.lib.gpis_ws_sample_distance_host(self.h, rays.shape[0], _ptr(rays), _ptr(out)), "gpis_ws_sample_distance_host")
+        return out
+
+    def transmittance(self, rays):
+        rays = np.ascontiguousarray(rays, dtype=RAY_IN)
+        vis = np.zeros(rays.shape[0], dtype=np.uint8)
+        self.L.check(self.L.lib.gpis_ws_transmittance_host(self.h, rays.shape[0], _ptr(rays), _ptr(vis)), "gpis_ws_transmittance_host")
+        return vis
+
+    def _dev(self, a):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(torch.device("cuda", self.device))
+
+    def sample_distance_batch(self, rays):
+        """The device-pointer entry (rays staged through a torch buffer)."""
+        import torch
+        rays = np.ascontiguousarray(rays, dtype=RAY_IN)
+        n = rays.shape[0]
+        d_rays = self._dev(rays)
+        d_out = torch.zeros(max(n, 1) * SEG_OUT.itemsize, dtype=torch.uint8, device=d_rays.device)
+        torch.cuda.synchronize(d_rays.device)
+        self.L.check(self.L.lib.gpis_ws_sample_distance_batch(self.h, n, ctypes.c_void_p(d_rays.data_ptr()), ctypes.c_void_p(d_out.data_ptr()), None),
+                     "gpis_ws_sample_distance_batch")
+        return d_out.cpu().numpy()[:n * SEG_OUT.itemsize].view(SEG_OUT).copy()
+
+    def transmittance_batch(self, rays):
+        import torch
+        rays = np.ascontiguousarray(rays, dtype=RAY_IN)
+        n = rays.shape[0]
+        d_rays = self._dev(rays)
+        d_vis = torch.zeros(max(n, 1), dtype=torch.uint8, device=d_rays.device)
+        torch.cuda.synchronize(d_rays.device)
+        self.L.check(self.L.lib.gpis_ws_transmittance_batch(self.h, n, ctypes.c_void_p(d_rays.data_ptr()), ctypes.c_void_p(d_vis.data_ptr()), None),
+                     "gpis_ws_transmittance_batch")
+        return d_vis.cpu().numpy()[:n].copy()
+
+    def eval(self, queries):
+        """value, gradient (the medium's normal method) and gp id at each query's point, for its (pixel, spp, segment) realization."""
+        import torch
+        q = np.ascontiguousarray(queries, dtype=WS_QUERY)
+        n = q.shape[0]
+        d_q = self._dev(q)
+        dev = d_q.device
+        d_v = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
+        d_g = torch.zeros(max(n, 1) * 3, dtype=torch.float64, device=dev)
+        d_id = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.L.check(self.L.lib.gpis_ws_eval_batch(self.h, n, ctypes.c_void_p(d_q.data_ptr()), ctypes.c_void_p(d_v.data_ptr()),
+                                                   ctypes.c_void_p(d_g.data_ptr()), ctypes.c_void_p(d_id.data_ptr()), None), "gpis_ws_eval_batch")
+        return d_v.cpu().numpy()[:n].copy(), d_g.cpu().numpy()[:3 * n].reshape(n, 3).copy(), d_id.cpu().numpy()[:n].copy()
+
+    def basis(self, pss4):
+        """(n, N, 6) array of d.x, d.y, d.z, omega, phi, w of the realizations of the (pixel.x, pixel.y, spp, segment) words."""
+        import torch
+        pss4 = np.ascontiguousarray(pss4, dtype=np.uint32).reshape(-1, 4)
+        n, N = pss4.shape[0], self.n_basis
+        d_p = self._dev(pss4)
+        d_out = torch.zeros(max(n * N, 1) * 6, dtype=torch.float64, device=d_p.device)
+        torch.cuda.synchronize(d_p.device)
+        self.L.check(self.L.lib.gpis_ws_basis_batch(self.h, n, ctypes.c_void_p(d_p.data_ptr()), ctypes.c_void_p(d_out.data_ptr()), None),
+                     "gpis_ws_basis_batch")
+        torch.cuda.synchronize(d_p.device)
+        return d_out.cpu().numpy()[:n * N * 6].reshape(n, N, 6).copy()
+
+    def counters(self):
+        e, s, g = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self.L.check(self.L.lib.gpis_ws_get_counters(self.h, ctypes.byref(e), ctypes.byref(s), ctypes.byref(g)), "gpis_ws_get_counters")
+        return {"n_eval": e.value, "n_spec": s.value, "n_seg": g.value}
+
+    def reset_counters(self):
+        self.L.check(self.L.lib.gpis_ws_reset_counters(self.h), "gpis_ws_reset_counters")

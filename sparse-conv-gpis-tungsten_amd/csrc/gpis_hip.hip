@@ -55,6 +55,21 @@ static int set_err(int code, const char *fmt, ...)
 
 extern "C" const char *gpis_last_error(void) { return g_err; }
 
+// ---- shared with the weight-space medium's translation unit (tu_ws.hip) ----
+namespace gpis {
+int ws_destroy(gpis_medium *m);
+int host_set_err(int code, const char *msg) { return set_err(code, "%s", msg); }
+// a weight-space handle starts with kWsHandleTag where a gpis_medium holds params.abi_version (GPIS_ABI_VERSION)
+bool ws_is_handle(const void *m)
+{
+    uint32_t w = 0;
+    if (m) memcpy(&w, m, sizeof w);
+    return w == 0x57534D31u;
+}
+}   // namespace gpis
+// a weight-space handle (tu_ws.hip) is refused by every sparse-convolution / function-space entry: its first word is not abi_version
+static bool std_handle(const gpis_medium *m) { return m && !gpis::ws_is_handle(m); }
+
 // ======================================================================================
 // handle
 // ======================================================================================
@@ -430,6 +445,14 @@ static int build_model(const gpis_params &P, DevModel &M, gpis_derived &D)
     D.multi_resolution = M.multi_res;
     return GPIS_OK;
 }
+// the model part a weight-space medium shares (means, colour, medium coefficients; tu_ws.hip)
+namespace gpis {
+int host_build_model(const gpis_params &P, DevModel &M)
+{
+    gpis_derived D;
+    return build_model(P, M, D);
+}
+}   // namespace gpis
 
 // MeanFunction::color / emission at double-precision points (GPF.hpp:849-857; ramp noises: three equal components)
 __global__ void __launch_bounds__(256) k_mean_color_emission(const DevModel *__restrict__ Mp, size_t n, const double *__restrict__ p3,
@@ -1022,9 +1045,11 @@ extern "C" const char *gpis_abi_sizes(void)
     static char buf[512];
     snprintf(buf, sizeof buf,
              "gpis_params=%zu,gpis_mean=%zu,gpis_ray_in=%zu,gpis_seg_out=%zu,gpis_cond_coeff=%zu,gpis_query=%zu,"
-             "gpis_nee_query=%zu,gpis_derived=%zu,gpis_scene_s=%zu,gpis_surface_s=%zu,gpis_ramp=%zu,gpis_fs_state=%zu,gpis_guide_info=%zu",
+             "gpis_nee_query=%zu,gpis_derived=%zu,gpis_scene_s=%zu,gpis_surface_s=%zu,gpis_ramp=%zu,gpis_fs_state=%zu,gpis_guide_info=%zu,"
+             "gpis_ws_params=%zu,gpis_ws_query=%zu",
              sizeof(gpis_params), sizeof(gpis_mean), sizeof(gpis_ray_in), sizeof(gpis_seg_out), sizeof(gpis_cond_coeff),
-             sizeof(gpis_query), sizeof(gpis_nee_query), sizeof(gpis_derived), sizeof(gpis_scene_s), sizeof(gpis_surface_s), sizeof(gpis_ramp), sizeof(gpis_fs_state), sizeof(gpis_guide_info));
+             sizeof(gpis_query), sizeof(gpis_nee_query), sizeof(gpis_derived), sizeof(gpis_scene_s), sizeof(gpis_surface_s), sizeof(gpis_ramp), sizeof(gpis_fs_state), sizeof(gpis_guide_info),
+             sizeof(gpis_ws_params), sizeof(gpis_ws_query));
     return buf;
 }
 
@@ -1168,6 +1193,7 @@ extern "C" int gpis_create(const gpis_params *params, int device, gpis_medium **
 extern "C" int gpis_destroy(gpis_medium *m)
 {
     if (!m) return GPIS_OK;
+    if (gpis::ws_is_handle(m)) return gpis::ws_destroy(m);
     (void)hipSetDevice(m->device);
     (void)hipDeviceSynchronize();
     fast_table_free(&m->fast);
@@ -1204,7 +1230,7 @@ extern "C" int gpis_destroy(gpis_medium *m)
 
 extern "C" int gpis_get_derived(const gpis_medium *m, gpis_derived *out)
 {
-    if (!m || !out) return set_err(GPIS_ERR_INVALID_ARG, "null argument");
+    if (!std_handle(m) || !out) return set_err(GPIS_ERR_INVALID_ARG, "null argument or not a sparse-convolution handle");
     *out = m->derived;
     return GPIS_OK;
 }
@@ -1469,28 +1495,28 @@ static int transmittance_impl(gpis_medium *m, size_t n, const gpis_ray_in *rays,
 
 extern "C" int gpis_sample_distance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, gpis_cond_coeff *coeff, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || (rays && out)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (rays && out)));
     std::lock_guard<std::mutex> lock(m->mu);      // the handle's event lists / wavefront workspace are shared; held while ENQUEUEING only
     HIP_TRY(hipSetDevice(m->device));
     return sample_distance_impl(m, n, rays, out, coeff, nullptr, (hipStream_t)stream, m->batch_hint);
 }
 extern "C" int gpis_transmittance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, uint8_t *visible, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || (rays && visible)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (rays && visible)));
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
     return transmittance_impl(m, n, rays, visible, nullptr, (hipStream_t)stream, m->batch_hint);
 }
 extern "C" int gpis_set_batch_order(gpis_medium *m, int order)
 {
-    CHECK_ARGS(m && (order == GPIS_ORDER_COHERENT || order == GPIS_ORDER_SCATTERED));
+    CHECK_ARGS(std_handle(m) && (order == GPIS_ORDER_COHERENT || order == GPIS_ORDER_SCATTERED));
     std::lock_guard<std::mutex> lock(m->mu);
     m->batch_hint = order;
     return GPIS_OK;
 }
 extern "C" int gpis_set_option(gpis_medium *m, int option, long long value)
 {
-    CHECK_ARGS(m && option >= 0 && option < GPIS_OPT_COUNT_);
+    CHECK_ARGS(std_handle(m) && option >= 0 && option < GPIS_OPT_COUNT_);
     switch (option) {
     case GPIS_OPT_MARCH_FORM: CHECK_ARGS(value >= GPIS_MARCH_FORM_AUTO && value <= GPIS_MARCH_FORM_WAVE); break;
     case GPIS_OPT_WAVE_TAIL: CHECK_ARGS(value >= 0); break;
@@ -1506,14 +1532,14 @@ extern "C" int gpis_set_option(gpis_medium *m, int option, long long value)
 }
 extern "C" int gpis_get_option(gpis_medium *m, int option, long long *value)
 {
-    CHECK_ARGS(m && value && option >= 0 && option < GPIS_OPT_COUNT_);
+    CHECK_ARGS(std_handle(m) && value && option >= 0 && option < GPIS_OPT_COUNT_);
     std::lock_guard<std::mutex> lock(m->mu);
     *value = m->opt[option];
     return GPIS_OK;
 }
 extern "C" int gpis_eval_value_batch(gpis_medium *m, size_t n, const gpis_query *q, float *value, int32_t *gp_id, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || (q && value)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (q && value)));
     if (n == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
     launch::eval_value(m->d_model, n, q, value, gp_id, m->d_counters, (hipStream_t)stream);
@@ -1521,7 +1547,7 @@ extern "C" int gpis_eval_value_batch(gpis_medium *m, size_t n, const gpis_query 
 }
 extern "C" int gpis_eval_gradient_batch(gpis_medium *m, size_t n, const gpis_query *q, float *grad3, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || (q && grad3)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (q && grad3)));
     if (n == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
     launch::eval_gradient(m->d_model, n, q, grad3, m->d_counters, (hipStream_t)stream);
@@ -1530,7 +1556,7 @@ extern "C" int gpis_eval_gradient_batch(gpis_medium *m, size_t n, const gpis_que
 extern "C" int gpis_conditioning_batch(gpis_medium *m, size_t n, const gpis_query *q, const float *target_val, const float *target_grad3,
                                        gpis_cond_coeff *coeff_out, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || (q && target_val && target_grad3 && coeff_out)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (q && target_val && target_grad3 && coeff_out)));
     if (n == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
     launch::conditioning(m->d_model, n, q, target_val, target_grad3, coeff_out, m->d_counters, (hipStream_t)stream);
@@ -1538,7 +1564,7 @@ extern "C" int gpis_conditioning_batch(gpis_medium *m, size_t n, const gpis_quer
 }
 extern "C" int gpis_nee_pdf_batch(gpis_medium *m, size_t n, const gpis_nee_query *q, float *pdf, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || (q && pdf)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (q && pdf)));
     if (n == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
     launch::nee(nee_instance(m->host_model), m->d_model, n, q, pdf, nullptr, m->d_counters, nullptr, (hipStream_t)stream);
@@ -1546,7 +1572,7 @@ extern "C" int gpis_nee_pdf_batch(gpis_medium *m, size_t n, const gpis_nee_query
 }
 extern "C" int gpis_nee_grad_batch(gpis_medium *m, size_t n, const gpis_nee_query *q, float *grad3, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || (q && grad3)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (q && grad3)));
     if (n == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
     launch::nee(nee_instance(m->host_model), m->d_model, n, q, nullptr, grad3, m->d_counters, nullptr, (hipStream_t)stream);
@@ -1554,7 +1580,7 @@ extern "C" int gpis_nee_grad_batch(gpis_medium *m, size_t n, const gpis_nee_quer
 }
 extern "C" int gpis_mean_color_emission_batch(gpis_medium *m, size_t n, const double *p3, float *color3, float *emission3, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || p3));
+    CHECK_ARGS(std_handle(m) && (n == 0 || p3));
     if (n == 0 || (!color3 && !emission3)) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
     k_mean_color_emission<<<grid_of(n, 256), 256, 0, (hipStream_t)stream>>>(m->d_model, n, p3, color3, emission3);
@@ -1596,7 +1622,7 @@ extern "C" int gpis_fs_prof_read(unsigned long long *out16, int reset) { return 
 #endif
 extern "C" int gpis_fs_linalg_batch(gpis_medium *m, int op, int n, size_t count, const double *in, double *out, double *evals, void *stream)
 {
-    CHECK_ARGS(m && op >= GPIS_FS_OP_EIGH && op <= GPIS_FS_OP_PINV && n >= 1 && n <= GPIS_FS_MAX_CTX && (count == 0 || (in && out)));
+    CHECK_ARGS(std_handle(m) && op >= GPIS_FS_OP_EIGH && op <= GPIS_FS_OP_PINV && n >= 1 && n <= GPIS_FS_MAX_CTX && (count == 0 || (in && out)));
     if (count == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
     unsigned cap = 0;
@@ -1628,14 +1654,14 @@ extern "C" int gpis_libm_batch(int fn, size_t n, const double *x, const double *
 }
 extern "C" int gpis_fs_sample_distance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_fs_state *states, gpis_seg_out *out, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || (rays && states && out)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (rays && states && out)));
     if (int st = fs_check(m)) return st;
     if (n == 0) return GPIS_OK;
     return fs_launch(true, m, n, rays, states, out, nullptr, (hipStream_t)stream);
 }
 extern "C" int gpis_fs_transmittance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_fs_state *states, uint8_t *visible, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || (rays && states && visible)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (rays && states && visible)));
     if (int st = fs_check(m)) return st;
     if (n == 0) return GPIS_OK;
     return fs_launch(false, m, n, rays, states, nullptr, visible, (hipStream_t)stream);
@@ -1669,17 +1695,17 @@ static int fs_host(gpis_medium *m, bool want_sample, size_t n, const gpis_ray_in
 }
 extern "C" int gpis_fs_sample_distance_host(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_fs_state *states, gpis_seg_out *out)
 {
-    CHECK_ARGS(m && (n == 0 || (rays && states && out)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (rays && states && out)));
     return fs_host(m, true, n, rays, states, out);
 }
 extern "C" int gpis_fs_transmittance_host(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_fs_state *states, uint8_t *visible)
 {
-    CHECK_ARGS(m && (n == 0 || (rays && states && visible)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (rays && states && visible)));
     return fs_host(m, false, n, rays, states, visible);
 }
 extern "C" int gpis_mean_color_emission_host(gpis_medium *m, size_t n, const double *p3, float *color3, float *emission3)
 {
-    CHECK_ARGS(m && (n == 0 || p3));
+    CHECK_ARGS(std_handle(m) && (n == 0 || p3));
     if (n == 0 || (!color3 && !emission3)) return GPIS_OK;
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
@@ -1696,7 +1722,7 @@ extern "C" int gpis_mean_color_emission_host(gpis_medium *m, size_t n, const dou
 }
 extern "C" int gpis_xxhash32_batch(gpis_medium *m, size_t n, int arity, const uint32_t *words, uint32_t *out, void *stream)
 {
-    CHECK_ARGS(m && arity >= 1 && arity <= 4 && (n == 0 || (words && out)));
+    CHECK_ARGS(std_handle(m) && arity >= 1 && arity <= 4 && (n == 0 || (words && out)));
     if (n == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
     k_xxhash32<<<grid_of(n, 256), 256, 0, (hipStream_t)stream>>>(n, arity, words, out);
@@ -1704,7 +1730,7 @@ extern "C" int gpis_xxhash32_batch(gpis_medium *m, size_t n, int arity, const ui
 }
 extern "C" int gpis_pcg32_stream_batch(gpis_medium *m, size_t n, const uint64_t *state, uint32_t count, uint32_t *out, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || (state && out)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (state && out)));
     if (n == 0 || count == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
     k_pcg32_stream<<<grid_of(n, 256), 256, 0, (hipStream_t)stream>>>(n, state, count, out);
@@ -1795,7 +1821,7 @@ static int host_march(gpis_medium *m, bool sample, size_t n, const gpis_ray_in *
 }
 extern "C" int gpis_sample_distance_host(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, gpis_cond_coeff *coeff)
 {
-    CHECK_ARGS(m && (n == 0 || (rays && out)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (rays && out)));
     if (n == 0) return GPIS_OK;
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
@@ -1803,7 +1829,7 @@ extern "C" int gpis_sample_distance_host(gpis_medium *m, size_t n, const gpis_ra
 }
 extern "C" int gpis_transmittance_host(gpis_medium *m, size_t n, const gpis_ray_in *rays, uint8_t *visible)
 {
-    CHECK_ARGS(m && (n == 0 || (rays && visible)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (rays && visible)));
     if (n == 0) return GPIS_OK;
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
@@ -1821,7 +1847,7 @@ extern "C" void gpis_free_host(void *p)
 }
 extern "C" int gpis_eval_value_host(gpis_medium *m, size_t n, const gpis_query *q, float *value, int32_t *gp_id)
 {
-    CHECK_ARGS(m && (n == 0 || (q && value)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (q && value)));
     if (n == 0) return GPIS_OK;
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
@@ -1838,7 +1864,7 @@ extern "C" int gpis_eval_value_host(gpis_medium *m, size_t n, const gpis_query *
 }
 extern "C" int gpis_eval_gradient_host(gpis_medium *m, size_t n, const gpis_query *q, float *grad3)
 {
-    CHECK_ARGS(m && (n == 0 || (q && grad3)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (q && grad3)));
     if (n == 0) return GPIS_OK;
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
@@ -1856,7 +1882,7 @@ extern "C" int gpis_eval_gradient_host(gpis_medium *m, size_t n, const gpis_quer
 extern "C" int gpis_conditioning_host(gpis_medium *m, size_t n, const gpis_query *q, const float *target_val, const float *target_grad3,
                                       gpis_cond_coeff *coeff_out)
 {
-    CHECK_ARGS(m && (n == 0 || (q && target_val && target_grad3 && coeff_out)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (q && target_val && target_grad3 && coeff_out)));
     if (n == 0) return GPIS_OK;
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
@@ -1891,19 +1917,19 @@ static int nee_host(gpis_medium *m, size_t n, const gpis_nee_query *q, float *pd
 }
 extern "C" int gpis_nee_pdf_host(gpis_medium *m, size_t n, const gpis_nee_query *q, float *pdf)
 {
-    CHECK_ARGS(m && (n == 0 || (q && pdf)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (q && pdf)));
     return n ? nee_host(m, n, q, pdf, nullptr) : GPIS_OK;
 }
 extern "C" int gpis_nee_grad_host(gpis_medium *m, size_t n, const gpis_nee_query *q, float *grad3)
 {
-    CHECK_ARGS(m && (n == 0 || (q && grad3)));
+    CHECK_ARGS(std_handle(m) && (n == 0 || (q && grad3)));
     return n ? nee_host(m, n, q, nullptr, grad3) : GPIS_OK;
 }
 
 // ---- measurement -------------------------------------------------------------------------
 extern "C" int gpis_get_counters(gpis_medium *m, uint64_t *n_eval, uint64_t *n_seg)
 {
-    CHECK_ARGS(m);
+    CHECK_ARGS(std_handle(m));
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     Counters c[2];
@@ -1914,7 +1940,7 @@ extern "C" int gpis_get_counters(gpis_medium *m, uint64_t *n_eval, uint64_t *n_s
 }
 extern "C" int gpis_reset_counters(gpis_medium *m)
 {
-    CHECK_ARGS(m);
+    CHECK_ARGS(std_handle(m));
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemset(m->d_counters, 0, 2 * sizeof(Counters)));
@@ -1926,7 +1952,7 @@ extern "C" int gpis_reset_counters(gpis_medium *m)
 // ---- guide field ---------------------------------------------------------------------------
 extern "C" int gpis_build_guide(gpis_medium *m, int half_extent_cells, int points_per_cell)
 {
-    CHECK_ARGS(m);
+    CHECK_ARGS(std_handle(m));
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -1941,7 +1967,7 @@ extern "C" int gpis_build_guide(gpis_medium *m, int half_extent_cells, int point
 }
 extern "C" int gpis_drop_guide(gpis_medium *m)
 {
-    CHECK_ARGS(m);
+    CHECK_ARGS(std_handle(m));
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -1951,7 +1977,7 @@ extern "C" int gpis_drop_guide(gpis_medium *m)
 }
 extern "C" int gpis_get_guide_steps(gpis_medium *m, uint64_t *n_guide)
 {
-    CHECK_ARGS(m && n_guide);
+    CHECK_ARGS(std_handle(m) && n_guide);
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     unsigned long long v = 0;
@@ -1962,7 +1988,7 @@ extern "C" int gpis_get_guide_steps(gpis_medium *m, uint64_t *n_guide)
 extern "C" int gpis_guide_selfcheck(gpis_medium *m, size_t n, const float *points3, uint64_t *checked, uint64_t *violations,
                                     float *max_ratio, float *mean_bound, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || points3));
+    CHECK_ARGS(std_handle(m) && (n == 0 || points3));
     if (!m->guide.enabled) return set_err(GPIS_ERR_UNSUPPORTED, "gpis_guide_selfcheck: no guide field built");
     HIP_TRY(hipSetDevice(m->device));
     // scratch: [0] = points inside the field, [1] = violations, word 2 = {max ratio bits, sum of bounds}, [3] = points in tabulated bricks
@@ -1986,7 +2012,7 @@ extern "C" int gpis_guide_selfcheck(gpis_medium *m, size_t n, const float *point
 }
 extern "C" int gpis_get_guide_info(gpis_medium *m, gpis_guide_info *out)
 {
-    CHECK_ARGS(m && out);
+    CHECK_ARGS(std_handle(m) && out);
     memset(out, 0, sizeof *out);
     if (!m->guide.enabled) return GPIS_OK;
     const GuideField &F = m->guide;
@@ -2003,7 +2029,7 @@ extern "C" int gpis_get_guide_info(gpis_medium *m, gpis_guide_info *out)
 extern "C" int gpis_guide_raycheck(gpis_medium *m, size_t n, const gpis_ray_in *rays, uint32_t steps, uint64_t *certified,
                                    uint64_t *violations, void *stream)
 {
-    CHECK_ARGS(m && (n == 0 || rays));
+    CHECK_ARGS(std_handle(m) && (n == 0 || rays));
     if (!m->guide.enabled) return set_err(GPIS_ERR_UNSUPPORTED, "gpis_guide_raycheck: no guide field built");
     HIP_TRY(hipSetDevice(m->device));
     unsigned long long *st = m->d_guide_cnt + 1;
@@ -2022,13 +2048,13 @@ extern "C" int gpis_guide_raycheck(gpis_medium *m, size_t n, const gpis_ray_in *
 
 extern "C" int gpis_set_profiling(gpis_medium *m, int enable)
 {
-    CHECK_ARGS(m);
+    CHECK_ARGS(std_handle(m));
     m->profiling = enable != 0;
     return GPIS_OK;
 }
 extern "C" int gpis_get_kernel_profile(gpis_medium *m, int which, double *total_ms, uint64_t *launches, uint64_t *n_eval, uint64_t *n_seg)
 {
-    CHECK_ARGS(m && which >= 0 && which <= 2);
+    CHECK_ARGS(std_handle(m) && which >= 0 && which <= 2);
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     for (size_t i = 0; i < m->events_used[which]; ++i) {
@@ -2162,7 +2188,7 @@ static int lambert_ws_plan(gpis_medium *m, const gpis_scene_s *s, size_t total_p
 
 extern "C" int gpis_set_variance_grid(gpis_medium *m, const gpis_variance_grid *g, const float *voxels)
 {
-    CHECK_ARGS(m && g && voxels);
+    CHECK_ARGS(std_handle(m) && g && voxels);
     CHECK_ARGS(g->dims[0] >= 1 && g->dims[1] >= 1 && g->dims[2] >= 1 && (g->interpolate == 0 || g->interpolate == 1));
     if (!m->host_model.grid.on) return set_err(GPIS_ERR_INVALID_ARG, "gpis_set_variance_grid: the medium was not created with grid_nonstationary = 1");
     std::lock_guard<std::mutex> lock(m->mu);
@@ -2185,7 +2211,7 @@ extern "C" int gpis_set_variance_grid(gpis_medium *m, const gpis_variance_grid *
 
 extern "C" int gpis_reserve_scene_workspace(gpis_medium *m, const gpis_scene_s *s)
 {
-    CHECK_ARGS(m && s);
+    CHECK_ARGS(std_handle(m) && s);
     CHECK_ARGS(scene_args_ok(s));
     HIP_TRY(hipSetDevice(m->device));
     LambertWs W;
@@ -2197,7 +2223,7 @@ extern "C" int gpis_reserve_scene_workspace(gpis_medium *m, const gpis_scene_s *
 
 extern "C" int gpis_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radiance_sum, uint32_t *hit_count, void *stream)
 {
-    CHECK_ARGS(m && s && radiance_sum);
+    CHECK_ARGS(std_handle(m) && s && radiance_sum);
     CHECK_ARGS(scene_args_ok(s));
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
@@ -2241,7 +2267,7 @@ extern "C" int gpis_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float 
 
 extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo, float *radiance_sum, void *stream)
 {
-    CHECK_ARGS(m && s && radiance_sum && max_path_bounces >= 1);
+    CHECK_ARGS(std_handle(m) && s && radiance_sum && max_path_bounces >= 1);
     CHECK_ARGS(scene_args_ok(s));
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
@@ -2338,7 +2364,7 @@ extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, 
 
 extern "C" int gpis_render_scene_s_nee(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_s *surf, float *radiance_sum, void *stream)
 {
-    CHECK_ARGS(m && s && surf && radiance_sum);
+    CHECK_ARGS(std_handle(m) && s && surf && radiance_sum);
     CHECK_ARGS(scene_args_ok(s));
     CHECK_ARGS(surf->cap_cos < 1.0f && surf->cap_cos > -1.0f);
     std::lock_guard<std::mutex> lock(m->mu);

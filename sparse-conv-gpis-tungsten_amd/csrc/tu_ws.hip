@@ -1,0 +1,332 @@
+// tu_ws.hip — the weight-space GP medium (gpis_ws.hpp): its kernels and its gpis_ws_* entry points (include/gpis.h).
+//
+// A weight-space handle is its own object (WsHandle) behind the opaque gpis_medium pointer; its first word is kWsHandleTag,
+// where a sparse-convolution handle holds gpis_params::abi_version, so either family of entries can refuse the other's handles.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <new>
+
+#include "gpis.h"
+#include "gpis_ws.hpp"
+
+#pragma clang fp contract(off)
+
+namespace gpis {
+// gpis_hip.hip
+int host_build_model(const gpis_params &P, DevModel &M);
+int host_set_err(int code, const char *msg);
+bool ws_is_handle(const void *m);
+int ws_destroy(gpis_medium *m);
+}   // namespace gpis
+
+using namespace gpis;
+
+namespace {
+
+struct WsHandle {
+    uint32_t tag = kWsHandleTag;          // must stay the first member
+    int device = 0;
+    gpis_params params{};
+    gpis_ws_params wsp{};
+    WsModel host{};
+    WsModel *d_model = nullptr;
+    WsCounters *d_counters = nullptr;
+    double *d_basis = nullptr;            // single realization: [6][N]
+    double *d_work = nullptr;             // per-path realizations: one [6][N] slice per resident workgroup
+    unsigned work_blocks = 0;
+    unsigned grid_cap = 0;                // resident one-wave workgroups of k_ws_march on this device
+    std::mutex mu;                        // serialises the entries of one handle (workspace, staging, counters)
+    void *stage[3] = {nullptr, nullptr, nullptr};
+    size_t stage_bytes[3] = {0, 0, 0};
+};
+
+int ws_err(int code, const char *fmt, ...)
+{
+    char buf[480];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return host_set_err(code, buf);
+}
+
+#define WS_HIP_TRY(expr)                                                                                              \
+    do {                                                                                                              \
+        hipError_t e_ = (expr);                                                                                       \
+        if (e_ != hipSuccess) return ws_err(GPIS_ERR_DEVICE, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+WsHandle *as_ws(gpis_medium *m) { return ws_is_handle(m) ? reinterpret_cast<WsHandle *>(m) : nullptr; }
+
+// the refusals of the built scope (include/gpis.h); no device needed
+int ws_validate(const gpis_params &P, const gpis_ws_params &S)
+{
+    if (P.abi_version != GPIS_ABI_VERSION) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: abi_version %u != %d", P.abi_version, GPIS_ABI_VERSION);
+    if (S.version != GPIS_WS_PARAMS_VERSION) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: gpis_ws_params.version %u != %d", S.version, GPIS_WS_PARAMS_VERSION);
+    if (P.correlation_context < GPIS_CTX_GLOBAL || P.correlation_context > GPIS_CTX_NONE)
+        return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: correlation_context %d", P.correlation_context);
+    if (S.basis_functions < 0 || S.basis_functions > GPIS_WS_MAX_BASIS)
+        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: basis_functions %d outside 0..%d", S.basis_functions, GPIS_WS_MAX_BASIS);
+    if (!(P.step_size > 0.f))
+        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: step_size %g: only the ray march (step_size > 0) is built, not the affine-arithmetic "
+                                            "sphere trace of step_size == 0 (WSM:186-235)", (double)P.step_size);
+    if (P.kernel_type != GPIS_KERNEL_SQUARED_EXPONENTIAL || P.nonstationary || P.grid_nonstationary)
+        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: only the stationary squared-exponential covariance is built: the spectral samplers of "
+                                            "the other kernels and of the non-stationary wrappers draw from std::mt19937 / std::gamma_distribution");
+    if (S.normal_method == GPIS_NORMAL_BECKMANN || S.normal_method == GPIS_NORMAL_GGX)
+        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: normal_method beckmann / ggx is outside the built scope");
+    if (S.normal_method != GPIS_NORMAL_CONDITIONED_GAUSSIAN && S.normal_method != GPIS_NORMAL_FINITE_DIFFERENCES)
+        return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: normal_method %d", S.normal_method);
+    if (S.intersect_method == GPIS_INTERSECT_MEAN)
+        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: intersect_method mean is outside the built scope");
+    if (S.intersect_method != GPIS_INTERSECT_GP_DISCRETE)
+        return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: intersect_method %d", S.intersect_method);
+    if (P.mean_color.enabled && P.mean_color.type >= GPIS_NOISE_SANDSTONE)
+        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: a sandstone / rust mean colour is outside the built scope (ramp colours only)");
+    for (int w = 0; w < 1 + (P.has_mean_additional ? 1 : 0); ++w) {
+        const int t = w ? P.mean_additional.type : P.mean.type;
+        if (t < GPIS_MEAN_HOMOGENEOUS || t > GPIS_MEAN_LINEAR) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: mean type %d", t);
+    }
+    return GPIS_OK;
+}
+
+int launch_check(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ws_err(GPIS_ERR_DEVICE, "%s launch: %s", what, hipGetErrorString(e));
+    return GPIS_OK;
+}
+
+int ensure_work(WsHandle *h, unsigned blocks)
+{
+    if (h->host.single || h->host.n == 0 || h->work_blocks >= blocks) return GPIS_OK;
+    if (h->d_work) { WS_HIP_TRY(hipDeviceSynchronize()); WS_HIP_TRY(hipFree(h->d_work)); h->d_work = nullptr; h->work_blocks = 0; }
+    WS_HIP_TRY(hipMalloc(&h->d_work, (size_t)blocks * 6 * (size_t)h->host.n * sizeof(double)));
+    h->work_blocks = blocks;
+    return GPIS_OK;
+}
+
+// the arguments of cos / sin stayed inside the restated range (include/gpis.h): read after the stream drained
+int check_overflow(WsHandle *h, hipStream_t s)
+{
+    unsigned long long ov = 0;
+    WS_HIP_TRY(hipMemcpyAsync(&ov, &h->d_counters->arg_overflow, sizeof ov, hipMemcpyDeviceToHost, s));
+    WS_HIP_TRY(hipStreamSynchronize(s));
+    if (ov) {
+        WS_HIP_TRY(hipMemsetAsync(&h->d_counters->arg_overflow, 0, sizeof ov, s));
+        WS_HIP_TRY(hipStreamSynchronize(s));
+        return ws_err(GPIS_ERR_UNSUPPORTED, "weight-space medium: a cos / sin argument reached |x| >= 105414350, where glibc's large-argument "
+                                            "reduction (not restated on the device) applies; the results of this call are not valid");
+    }
+    return GPIS_OK;
+}
+
+int march(WsHandle *h, bool want_sample, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, uint8_t *visible, hipStream_t s)
+{
+    if (n == 0) return GPIS_OK;
+    WS_HIP_TRY(hipSetDevice(h->device));
+    const unsigned grid = (unsigned)(n < h->grid_cap ? n : h->grid_cap);
+    if (int st = ensure_work(h, grid)) return st;
+    if (want_sample)
+        k_ws_march<true><<<grid, 64, 0, s>>>(h->d_model, n, rays, out, nullptr, h->d_work, h->d_counters);
+    else
+        k_ws_march<false><<<grid, 64, 0, s>>>(h->d_model, n, rays, nullptr, visible, h->d_work, h->d_counters);
+    if (int st = launch_check("k_ws_march")) return st;
+    return check_overflow(h, s);
+}
+
+int stage(WsHandle *h, int k, size_t bytes)
+{
+    if (h->stage_bytes[k] >= bytes) return GPIS_OK;
+    if (h->stage[k]) { WS_HIP_TRY(hipFree(h->stage[k])); h->stage[k] = nullptr; h->stage_bytes[k] = 0; }
+    const size_t cap = bytes + bytes / 4 + 4096;
+    WS_HIP_TRY(hipMalloc(&h->stage[k], cap));
+    h->stage_bytes[k] = cap;
+    return GPIS_OK;
+}
+
+int march_host(WsHandle *h, bool want_sample, size_t n, const gpis_ray_in *rays, void *out)
+{
+    if (n == 0) return GPIS_OK;
+    WS_HIP_TRY(hipSetDevice(h->device));
+    const size_t rec = want_sample ? sizeof(gpis_seg_out) : 1;
+    if (int st = stage(h, 0, n * sizeof(gpis_ray_in))) return st;
+    if (int st = stage(h, 1, n * rec)) return st;
+    WS_HIP_TRY(hipMemcpy(h->stage[0], rays, n * sizeof(gpis_ray_in), hipMemcpyHostToDevice));
+    const int st = march(h, want_sample, n, (const gpis_ray_in *)h->stage[0], want_sample ? (gpis_seg_out *)h->stage[1] : nullptr,
+                         want_sample ? nullptr : (uint8_t *)h->stage[1], nullptr);
+    if (st && st != GPIS_ERR_UNSUPPORTED) return st;
+    WS_HIP_TRY(hipMemcpy(out, h->stage[1], n * rec, hipMemcpyDeviceToHost));
+    return st;
+}
+
+}   // namespace
+
+namespace gpis {
+int ws_destroy(gpis_medium *m)
+{
+    WsHandle *h = as_ws(m);
+    if (!h) return GPIS_OK;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();
+    if (h->d_model) (void)hipFree(h->d_model);
+    if (h->d_counters) (void)hipFree(h->d_counters);
+    if (h->d_basis) (void)hipFree(h->d_basis);
+    if (h->d_work) (void)hipFree(h->d_work);
+    for (int k = 0; k < 3; ++k)
+        if (h->stage[k]) (void)hipFree(h->stage[k]);
+    h->tag = 0;
+    delete h;
+    return GPIS_OK;
+}
+}   // namespace gpis
+
+extern "C" void gpis_ws_default_params(gpis_ws_params *p)
+{
+    memset(p, 0, sizeof *p);
+    p->version = GPIS_WS_PARAMS_VERSION;
+    p->basis_functions = 300;                                  // WSM:26
+    p->normal_method = GPIS_NORMAL_CONDITIONED_GAUSSIAN;       // GPM.cpp:93
+    p->intersect_method = GPIS_INTERSECT_GP_DISCRETE;          // GPM.cpp:92
+}
+
+extern "C" int gpis_ws_create(const gpis_params *params, const gpis_ws_params *ws, int device, gpis_medium **out)
+{
+    if (!params || !ws || !out) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: null argument");
+    *out = nullptr;
+    if (int st = ws_validate(*params, *ws)) return st;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return ws_err(GPIS_ERR_NO_DEVICE, "gpis_ws_create: no HIP device visible (this library has no CPU fallback)");
+    if (device < 0 || device >= count) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: device %d of %d", device, count);
+    WS_HIP_TRY(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    WS_HIP_TRY(hipGetDeviceProperties(&prop, device));
+    if (!strstr(prop.gcnArchName, "gfx950"))
+        return ws_err(GPIS_ERR_NO_DEVICE, "gpis_ws_create: device %d is %s, this library is built for gfx950 only", device, prop.gcnArchName);
+
+    WsHandle *h = new (std::nothrow) WsHandle();
+    if (!h) return ws_err(GPIS_ERR_DEVICE, "out of host memory");
+    h->device = device;
+    h->params = *params;
+    h->wsp = *ws;
+    WsModel &W = h->host;
+    if (int st = host_build_model(*params, W.base)) { delete h; return st; }
+    W.n = ws->basis_functions;
+    W.normal_method = ws->normal_method;
+    W.single = params->single_realization != 0;
+    W.ctx = params->correlation_context;
+    W.seed = params->seed;
+    W.min_step = params->min_step;
+    W.step_size = params->step_size;
+    W.l = params->length_scale;
+    for (int c = 0; c < 3; ++c) W.sqrt_aniso[c] = std::sqrt(params->aniso[c]);     // float overload
+    W.sqrt2n = W.n > 0 ? std::sqrt(2. / W.n) : 0.;
+    W.basis = nullptr;
+    int st = GPIS_OK;
+    auto fail = [&](int code) { gpis::ws_destroy(reinterpret_cast<gpis_medium *>(h)); return code; };
+    if (hipMalloc(&h->d_model, sizeof(WsModel)) != hipSuccess || hipMalloc(&h->d_counters, sizeof(WsCounters)) != hipSuccess ||
+        hipMemset(h->d_counters, 0, sizeof(WsCounters)) != hipSuccess)
+        return fail(ws_err(GPIS_ERR_DEVICE, "gpis_ws_create: device allocation failed"));
+    if (W.single && W.n > 0) {
+        if (hipMalloc(&h->d_basis, 6 * (size_t)W.n * sizeof(double)) != hipSuccess)
+            return fail(ws_err(GPIS_ERR_DEVICE, "gpis_ws_create: device allocation failed"));
+        W.basis = h->d_basis;
+    }
+    if (hipMemcpy(h->d_model, &W, sizeof W, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(ws_err(GPIS_ERR_DEVICE, "gpis_ws_create: upload failed"));
+    if (W.single && W.n > 0) {
+        k_ws_basis<0><<<(W.n + 255) / 256, 256>>>(h->d_model, 1, nullptr, h->d_basis, 0);     // pss (0,0,0,0)
+        if ((st = launch_check("k_ws_basis"))) return fail(st);
+        if (hipDeviceSynchronize() != hipSuccess) return fail(ws_err(GPIS_ERR_DEVICE, "gpis_ws_create: basis build failed"));
+    }
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ws_march<true>, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 8;
+    h->grid_cap = (unsigned)(per_cu * (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1));
+    *out = reinterpret_cast<gpis_medium *>(h);
+    return GPIS_OK;
+}
+
+#define WS_HANDLE(m)                                                                                            \
+    WsHandle *h = as_ws(m);                                                                                     \
+    if (!h) return ws_err(GPIS_ERR_INVALID_ARG, "%s: not a weight-space handle (gpis_ws_create)", __func__)
+
+extern "C" int gpis_ws_sample_distance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, void *stream)
+{
+    WS_HANDLE(m);
+    if (n && (!rays || !out)) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_sample_distance_batch: null pointer");
+    std::lock_guard<std::mutex> lock(h->mu);
+    return march(h, true, n, rays, out, nullptr, (hipStream_t)stream);
+}
+extern "C" int gpis_ws_transmittance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, uint8_t *visible, void *stream)
+{
+    WS_HANDLE(m);
+    if (n && (!rays || !visible)) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_transmittance_batch: null pointer");
+    std::lock_guard<std::mutex> lock(h->mu);
+    return march(h, false, n, rays, nullptr, visible, (hipStream_t)stream);
+}
+extern "C" int gpis_ws_sample_distance_host(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out)
+{
+    WS_HANDLE(m);
+    if (n && (!rays || !out)) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_sample_distance_host: null pointer");
+    std::lock_guard<std::mutex> lock(h->mu);
+    return march_host(h, true, n, rays, out);
+}
+extern "C" int gpis_ws_transmittance_host(gpis_medium *m, size_t n, const gpis_ray_in *rays, uint8_t *visible)
+{
+    WS_HANDLE(m);
+    if (n && (!rays || !visible)) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_transmittance_host: null pointer");
+    std::lock_guard<std::mutex> lock(h->mu);
+    return march_host(h, false, n, rays, visible);
+}
+extern "C" int gpis_ws_eval_batch(gpis_medium *m, size_t n, const gpis_ws_query *q, double *value, double *grad3, int32_t *gp_id, void *stream)
+{
+    WS_HANDLE(m);
+    if (n && !q) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_eval_batch: null pointer");
+    if (n == 0) return GPIS_OK;
+    std::lock_guard<std::mutex> lock(h->mu);
+    WS_HIP_TRY(hipSetDevice(h->device));
+    const unsigned grid = (unsigned)(n < h->grid_cap ? n : h->grid_cap);
+    if (int st = ensure_work(h, grid)) return st;
+    k_ws_eval<0><<<grid, 64, 0, (hipStream_t)stream>>>(h->d_model, n, q, value, grad3, gp_id, h->d_work, h->d_counters);
+    if (int st = launch_check("k_ws_eval")) return st;
+    return check_overflow(h, (hipStream_t)stream);
+}
+extern "C" int gpis_ws_basis_batch(gpis_medium *m, size_t n, const uint32_t *pss4, double *out, void *stream)
+{
+    WS_HANDLE(m);
+    if (n && (!pss4 || !out)) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_basis_batch: null pointer");
+    const size_t total = n * (size_t)h->host.n;
+    if (total == 0) return GPIS_OK;
+    WS_HIP_TRY(hipSetDevice(h->device));
+    const size_t blocks = (total + 255) / 256;
+    k_ws_basis<0><<<(unsigned)(blocks < 65536 ? blocks : 65536), 256, 0, (hipStream_t)stream>>>(h->d_model, n, pss4, out, 1);
+    return launch_check("k_ws_basis");
+}
+extern "C" int gpis_ws_get_counters(gpis_medium *m, uint64_t *n_eval, uint64_t *n_spec, uint64_t *n_seg)
+{
+    WS_HANDLE(m);
+    std::lock_guard<std::mutex> lock(h->mu);
+    WS_HIP_TRY(hipSetDevice(h->device));
+    WS_HIP_TRY(hipDeviceSynchronize());
+    WsCounters c;
+    WS_HIP_TRY(hipMemcpy(&c, h->d_counters, sizeof c, hipMemcpyDeviceToHost));
+    if (n_eval) *n_eval = c.n_eval;
+    if (n_spec) *n_spec = c.n_spec;
+    if (n_seg) *n_seg = c.n_seg;
+    return GPIS_OK;
+}
+extern "C" int gpis_ws_reset_counters(gpis_medium *m)
+{
+    WS_HANDLE(m);
+    std::lock_guard<std::mutex> lock(h->mu);
+    WS_HIP_TRY(hipSetDevice(h->device));
+    WS_HIP_TRY(hipDeviceSynchronize());
+    WS_HIP_TRY(hipMemset(h->d_counters, 0, sizeof(WsCounters)));
+    return GPIS_OK;
+}
