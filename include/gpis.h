@@ -687,6 +687,20 @@ int gpis_ws_basis_batch(gpis_medium *m, size_t n, const uint32_t *pss4, double *
  * segments since the last reset.  Synchronises the device. */
 int gpis_ws_get_counters(gpis_medium *m, uint64_t *n_eval, uint64_t *n_spec, uint64_t *n_seg);
 int gpis_ws_reset_counters(gpis_medium *m);
+/* gpis_render_scene_s over the weight-space medium.  Covers the rows [y_begin, y_begin+y_count), the tile-row shard
+ * (shard_index / shard_count) and the samples [spp_begin, spp_begin+spp_count) that `s` selects.  Per sample: the draws of
+ * gpis_render_scene_s (PCG32 seeded with xxhash32(x, y, spp, scene_seed) + 1, then jx, jy, u_march, u_shadow), a primary
+ * sampleDistance, Lambert shading against the directional light, and one shadow transmittance per lit hit through a state copy
+ * with segment + 1, first_scatter = 0 and last_aniso / last_gp_id / last_val / info_t / bounce carried from the primary result.
+ * ACCUMULATES the per-pixel sum, taken in sample order, into radiance_sum[height*width] (float, device pointer, indexed
+ * y*width+x; the caller divides by the total spp) and the per-pixel hits into hit_count (device pointer, may be NULL).  The image
+ * does not depend on how a frame is cut into calls (rows, shards, spp ranges), nor on the order in which waves finish.
+ * One fused kernel, one wave per sample: no ray or segment records in device memory; under single_realization or context GLOBAL
+ * the primary's realization serves the shadow segment.  Weight-space handles only (any other handle: GPIS_ERR_INVALID_ARG;
+ * gpis_render_scene_s keeps refusing weight-space handles).  Returns GPIS_ERR_UNSUPPORTED under the cos / sin argument rule
+ * above, for which it synchronises `stream` once per call.  gpis_ws_get_counters: n_eval counts the reference's evaluations,
+ * n_seg the primary segments marched plus the shadow segments marched. */
+int gpis_ws_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radiance_sum, uint32_t *hit_count, void *stream);
 
 #ifdef __cplusplus
 }

@@ -334,7 +334,7 @@ class GpisLib:
         "gpis_set_variance_grid", "gpis_default_scene_s", "gpis_reserve_scene_workspace", "gpis_render_scene_s", "gpis_render_scene_s_paths", "gpis_render_scene_s_nee",
         "gpis_ws_default_params", "gpis_ws_create", "gpis_ws_sample_distance_batch", "gpis_ws_transmittance_batch",
         "gpis_ws_sample_distance_host", "gpis_ws_transmittance_host", "gpis_ws_eval_batch", "gpis_ws_basis_batch",
-        "gpis_ws_get_counters", "gpis_ws_reset_counters",
+        "gpis_ws_get_counters", "gpis_ws_reset_counters", "gpis_ws_render_scene_s",
     ]
 
     def __init__(self, path=None):
@@ -405,6 +405,7 @@ class GpisLib:
         L.gpis_set_variance_grid.argtypes = [vp, vp, vp]
         L.gpis_default_scene_s.restype = None
         L.gpis_render_scene_s.argtypes = [vp, vp, vp, vp, vp]
+        L.gpis_ws_render_scene_s.argtypes = [vp, vp, vp, vp, vp]
         L.gpis_render_scene_s_paths.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
         L.gpis_render_scene_s_nee.argtypes = [vp, vp, vp, vp, vp]
         L.gpis_ws_default_params.argtypes = [vp]
@@ -786,6 +787,24 @@ class WeightSpaceMedium:
                      "gpis_ws_basis_batch")
         torch.cuda.synchronize(d_p.device)
         return d_out.cpu().numpy()[:n * N * 6].reshape(n, N, 6).copy()
+
+    def render_scene_s(self, scene, want_hits=False):
+        """One call of the scene-S frame driver (gpis_ws_render_scene_s) into zeroed device buffers: the float32 sum-of-radiance
+        image (height, width) of the rows, shard and samples `scene` selects, and the per-pixel hit counts when asked."""
+        import torch
+        scene = np.array(scene, dtype=SCENE_S).reshape(())
+        hgt, wid = int(scene["height"]), int(scene["width"])
+        dev = torch.device("cuda", self.device)
+        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
+        d_hit = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_hits else None
+        torch.cuda.synchronize(dev)
+        self.L.check(self.L.lib.gpis_ws_render_scene_s(self.h, _ptr(scene), ctypes.c_void_p(d_rad.data_ptr()),
+                                                       ctypes.c_void_p(d_hit.data_ptr()) if want_hits else None, None), "gpis_ws_render_scene_s")
+        torch.cuda.synchronize(dev)
+        rad = d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy()
+        if not want_hits:
+            return rad
+        return rad, d_hit.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
 
     def counters(self):
         e, s, g = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()

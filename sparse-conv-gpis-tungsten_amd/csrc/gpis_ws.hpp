@@ -414,6 +414,109 @@ GPIS_DEV bool ws_transmittance_one(const WsModel &W, WsLds &L, const double *B, 
     return exited;
 }
 
+// GaussianProcessMedium::sampleDistance (GPM.cpp:299-393) of one segment over the realization B (wave-uniform)
+GPIS_DEV gpis_seg_out ws_sample_distance(const WsModel &W, WsLds &L, const double *B, const gpis_ray_in &ray, int lane, bool &overflow, WsTally &tally)
+{
+    const DevModel &M = W.base;
+    bool first_scatter = ray.first_scatter != 0;
+    int last_gp_id = ray.last_gp_id;
+    V3d last_aniso{ray.last_aniso[0], ray.last_aniso[1], ray.last_aniso[2]};
+    gpis_seg_out o{};
+    const WsRay R = ws_ray(ray);
+    double startT = R.startT;
+    const float maxT = R.maxT;
+    o.gp_id = last_gp_id;
+    o.last_val = ray.last_val;
+    V3d aniso = last_aniso;
+    bool finished = false;
+    if (ray.bounce >= M.max_bounces) {
+        o.ok = 0;
+        finished = true;
+    } else if (maxT == 0.f) {
+        o.sample_t = maxT;
+        o.weight[0] = o.weight[1] = o.weight[2] = 1.f;
+        o.exited = 1;
+        const V3 pp = R.pos + R.dir * o.sample_t;
+        o.p[0] = pp.x; o.p[1] = pp.y; o.p[2] = pp.z;
+        o.scheme = GPIS_UNI;
+        o.ok = 1;
+        finished = true;
+    } else if (M.absorption_only) {
+        if (maxT == __builtin_huge_valf()) {
+            o.ok = 0;
+            finished = true;
+        } else {
+            o.sample_t = maxT;
+            const bool vis = ws_transmittance_one(W, L, B, ray, first_scatter, last_gp_id, last_aniso, lane, overflow, tally);
+            o.weight[0] = o.weight[1] = o.weight[2] = vis ? 1.f : 0.f;
+            o.exited = 1;
+            o.scheme = GPIS_UNI;
+            aniso = last_aniso;
+        }
+    } else {
+        double t = (double)maxT;
+        bool exited;
+        do {
+            exited = !ws_intersect(W, L, B, R.ro, R.rd, (float)startT, R.farT, ray.u_jitter, first_scatter, t, last_gp_id, lane, overflow, tally);
+            if (t < (double)maxT) {
+                const V3d grad = ws_gradient(W, L, B, ray_at(R.ro, R.rdn, t), lane, overflow, tally);
+                aniso = grad;
+                first_scatter = false;
+                if (!__builtin_isfinite((aniso.x + aniso.y + aniso.z) / 3.0)) {
+                    aniso = V3d{1., 0., 0.};
+                    o.t = t; o.exited = exited; o.ok = 0; o.gp_id = last_gp_id;
+                    finished = true;
+                    break;
+                }
+            }
+            startT = t;
+        } while (t < (double)maxT && exited);
+        if (!finished) {
+            o.t = t;
+            o.exited = exited;
+            if (!exited) {
+                double d = aniso.x * (double)R.dir.x; d += aniso.y * (double)R.dir.y; d += aniso.z * (double)R.dir.z;
+                double l2 = 0.; l2 += aniso.x * aniso.x; l2 += aniso.y * aniso.y; l2 += aniso.z * aniso.z;
+                if (d > 0) {
+                    o.gp_id = last_gp_id; o.ok = 0;
+                    finished = true;
+                } else if (l2 < (double)0.0000001f) {
+                    aniso = V3d{1., 0., 0.};
+                    o.gp_id = last_gp_id; o.ok = 0;
+                    finished = true;
+                } else {
+                    const float col = M.color.enabled ? (float)ramp_eval(M.color, ray_at(R.ro, R.rdn, t)) : 1.f;
+                    o.weight[0] = o.weight[1] = o.weight[2] = col;
+                    o.continued_weight[0] = o.continued_weight[1] = o.continued_weight[2] = col;
+                }
+            } else {
+                aniso = ws_gradient(W, L, B, ray_at(R.ro, R.rdn, t), lane, overflow, tally);   // GPM.cpp:319
+                o.weight[0] = o.weight[1] = o.weight[2] = 1.f;
+                o.continued_weight[0] = o.continued_weight[1] = o.continued_weight[2] = 1.f;
+            }
+            if (!finished) {
+                const float ft = (float)t;
+                o.sample_t = ft < maxT ? ft : maxT;
+                o.continued_t = (float)t;
+                for (int c = 0; c < 3; ++c) {
+                    o.weight[c] *= M.sigma_s_over_t[c];
+                    o.continued_weight[c] *= M.sigma_s_over_t[c];
+                }
+                o.scheme = GPIS_UNI;
+            }
+        }
+    }
+    if (!finished) {
+        const V3 pp = R.pos + R.dir * o.sample_t;
+        o.p[0] = pp.x; o.p[1] = pp.y; o.p[2] = pp.z;
+        o.gp_id = last_gp_id;
+        o.ok = 1;
+    }
+    o.last_val = ray.last_val;
+    o.aniso[0] = aniso.x; o.aniso[1] = aniso.y; o.aniso[2] = aniso.z;
+    return o;
+}
+
 template <bool WANT_SAMPLE>
 __global__ void __launch_bounds__(64) k_ws_march(const WsModel *__restrict__ Wp, size_t n_rays, const gpis_ray_in *__restrict__ rays,
                                                  gpis_seg_out *__restrict__ outs, uint8_t *__restrict__ visible, double *__restrict__ workspace,
@@ -421,7 +524,6 @@ __global__ void __launch_bounds__(64) k_ws_march(const WsModel *__restrict__ Wp,
 {
     __shared__ WsLds L;
     const WsModel &W = *Wp;
-    const DevModel &M = W.base;
     const int lane = (int)threadIdx.x;
     double *own = workspace ? workspace + (size_t)blockIdx.x * 6 * (size_t)W.n : nullptr;
     WsTally tally{0, 0};
@@ -437,108 +539,16 @@ __global__ void __launch_bounds__(64) k_ws_march(const WsModel *__restrict__ Wp,
             B = own;
         }
         segs++;
-        bool first_scatter = ray.first_scatter != 0;
-        int last_gp_id = ray.last_gp_id;
-        V3d last_aniso{ray.last_aniso[0], ray.last_aniso[1], ray.last_aniso[2]};
         __syncthreads();
         if (!WANT_SAMPLE) {
+            bool first_scatter = ray.first_scatter != 0;
+            int last_gp_id = ray.last_gp_id;
+            V3d last_aniso{ray.last_aniso[0], ray.last_aniso[1], ray.last_aniso[2]};
             const bool vis = ws_transmittance_one(W, L, B, ray, first_scatter, last_gp_id, last_aniso, lane, overflow, tally);
             if (lane == 0) visible[idx] = vis ? 1 : 0;
             continue;
         }
-        gpis_seg_out o{};
-        const WsRay R = ws_ray(ray);
-        double startT = R.startT;
-        const float maxT = R.maxT;
-        o.gp_id = last_gp_id;
-        o.last_val = ray.last_val;
-        V3d aniso = last_aniso;
-        bool finished = false;
-        if (ray.bounce >= M.max_bounces) {
-            o.ok = 0;
-            finished = true;
-        } else if (maxT == 0.f) {
-            o.sample_t = maxT;
-            o.weight[0] = o.weight[1] = o.weight[2] = 1.f;
-            o.exited = 1;
-            const V3 pp = R.pos + R.dir * o.sample_t;
-            o.p[0] = pp.x; o.p[1] = pp.y; o.p[2] = pp.z;
-            o.scheme = GPIS_UNI;
-            o.ok = 1;
-            finished = true;
-        } else if (M.absorption_only) {
-            if (maxT == __builtin_huge_valf()) {
-                o.ok = 0;
-                finished = true;
-            } else {
-                o.sample_t = maxT;
-                const bool vis = ws_transmittance_one(W, L, B, ray, first_scatter, last_gp_id, last_aniso, lane, overflow, tally);
-                o.weight[0] = o.weight[1] = o.weight[2] = vis ? 1.f : 0.f;
-                o.exited = 1;
-                o.scheme = GPIS_UNI;
-                aniso = last_aniso;
-            }
-        } else {
-            double t = (double)maxT;
-            bool exited;
-            do {
-                exited = !ws_intersect(W, L, B, R.ro, R.rd, (float)startT, R.farT, ray.u_jitter, first_scatter, t, last_gp_id, lane, overflow, tally);
-                if (t < (double)maxT) {
-                    const V3d grad = ws_gradient(W, L, B, ray_at(R.ro, R.rdn, t), lane, overflow, tally);
-                    aniso = grad;
-                    first_scatter = false;
-                    if (!__builtin_isfinite((aniso.x + aniso.y + aniso.z) / 3.0)) {
-                        aniso = V3d{1., 0., 0.};
-                        o.t = t; o.exited = exited; o.ok = 0; o.gp_id = last_gp_id;
-                        finished = true;
-                        break;
-                    }
-                }
-                startT = t;
-            } while (t < (double)maxT && exited);
-            if (!finished) {
-                o.t = t;
-                o.exited = exited;
-                if (!exited) {
-                    double d = aniso.x * (double)R.dir.x; d += aniso.y * (double)R.dir.y; d += aniso.z * (double)R.dir.z;
-                    double l2 = 0.; l2 += aniso.x * aniso.x; l2 += aniso.y * aniso.y; l2 += aniso.z * aniso.z;
-                    if (d > 0) {
-                        o.gp_id = last_gp_id; o.ok = 0;
-                        finished = true;
-                    } else if (l2 < (double)0.0000001f) {
-                        aniso = V3d{1., 0., 0.};
-                        o.gp_id = last_gp_id; o.ok = 0;
-                        finished = true;
-                    } else {
-                        const float col = M.color.enabled ? (float)ramp_eval(M.color, ray_at(R.ro, R.rdn, t)) : 1.f;
-                        o.weight[0] = o.weight[1] = o.weight[2] = col;
-                        o.continued_weight[0] = o.continued_weight[1] = o.continued_weight[2] = col;
-                    }
-                } else {
-                    aniso = ws_gradient(W, L, B, ray_at(R.ro, R.rdn, t), lane, overflow, tally);   // GPM.cpp:319
-                    o.weight[0] = o.weight[1] = o.weight[2] = 1.f;
-                    o.continued_weight[0] = o.continued_weight[1] = o.continued_weight[2] = 1.f;
-                }
-                if (!finished) {
-                    const float ft = (float)t;
-                    o.sample_t = ft < maxT ? ft : maxT;
-                    o.continued_t = (float)t;
-                    for (int c = 0; c < 3; ++c) {
-                        o.weight[c] *= M.sigma_s_over_t[c];
-                        o.continued_weight[c] *= M.sigma_s_over_t[c];
-                    }
-                    o.scheme = GPIS_UNI;
-                }
-            }
-        }
-        if (!finished) {
-            const V3 pp = R.pos + R.dir * o.sample_t;
-            o.p[0] = pp.x; o.p[1] = pp.y; o.p[2] = pp.z;
-            o.gp_id = last_gp_id;
-            o.ok = 1;
-        }
-        o.last_val = ray.last_val;
-        o.aniso[0] = aniso.x; o.aniso[1] = aniso.y; o.aniso[2] = aniso.z;
+        const gpis_seg_out o = ws_sample_distance(W, L, B, ray, lane, overflow, tally);
         if (lane == 0) outs[idx] = o;
     }
     if (lane == 0 && counters && segs) {

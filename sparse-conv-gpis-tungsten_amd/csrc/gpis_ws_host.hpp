@@ -1,0 +1,106 @@
+// gpis_ws_host.hpp — host side of a weight-space handle, shared by the translation units that implement gpis_ws_* entries
+// (tu_ws.hip: handle, batch entries; tu_ws_scene.hip: the scene-S frame driver).
+//
+// A weight-space handle is its own object (WsHandle) behind the opaque gpis_medium pointer; its first word is kWsHandleTag,
+// where a sparse-convolution handle holds gpis_params::abi_version, so either family of entries can refuse the other's handles.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <mutex>
+
+#include "gpis.h"
+#include "gpis_ws.hpp"
+
+namespace gpis {
+// gpis_hip.hip
+int host_build_model(const gpis_params &P, DevModel &M);
+int host_set_err(int code, const char *msg);
+bool ws_is_handle(const void *m);
+int ws_destroy(gpis_medium *m);
+
+struct WsHandle {
+    uint32_t tag = kWsHandleTag;          // must stay the first member
+    int device = 0;
+    gpis_params params{};
+    gpis_ws_params wsp{};
+    WsModel host{};
+    WsModel *d_model = nullptr;
+    WsCounters *d_counters = nullptr;
+    double *d_basis = nullptr;            // single realization: [6][N]
+    double *d_work = nullptr;             // per-path realizations: one [6][N] slice per resident workgroup
+    unsigned work_blocks = 0;
+    unsigned grid_cap = 0;                // resident one-wave workgroups of k_ws_march on this device
+    unsigned scene_grid_cap = 0;          // ... of k_ws_scene (tu_ws_scene.hip; 0 until the first frame)
+    unsigned *d_scene_next = nullptr;     // k_ws_scene's work counter: the next sample of the chunk
+    std::mutex mu;                        // serialises the entries of one handle (workspace, staging, counters)
+    void *stage[3] = {nullptr, nullptr, nullptr};     // 0, 1: the *_host entries' rays / results; 2: the frame driver's sample records
+    size_t stage_bytes[3] = {0, 0, 0};
+};
+
+inline int ws_err(int code, const char *fmt, ...)
+{
+    char buf[480];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return host_set_err(code, buf);
+}
+
+#define WS_HIP_TRY(expr)                                                                                              \
+    do {                                                                                                              \
+        hipError_t e_ = (expr);                                                                                       \
+        if (e_ != hipSuccess) return ws_err(GPIS_ERR_DEVICE, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+inline WsHandle *as_ws(gpis_medium *m) { return ws_is_handle(m) ? reinterpret_cast<WsHandle *>(m) : nullptr; }
+
+#define WS_HANDLE(m)                                                                                            \
+    WsHandle *h = as_ws(m);                                                                                     \
+    if (!h) return ws_err(GPIS_ERR_INVALID_ARG, "%s: not a weight-space handle (gpis_ws_create)", __func__)
+
+inline int ws_launch_check(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ws_err(GPIS_ERR_DEVICE, "%s launch: %s", what, hipGetErrorString(e));
+    return GPIS_OK;
+}
+
+// the per-path workspace: one realization slice per resident workgroup
+inline int ws_ensure_work(WsHandle *h, unsigned blocks)
+{
+    if (h->host.single || h->host.n == 0 || h->work_blocks >= blocks) return GPIS_OK;
+    if (h->d_work) { WS_HIP_TRY(hipDeviceSynchronize()); WS_HIP_TRY(hipFree(h->d_work)); h->d_work = nullptr; h->work_blocks = 0; }
+    WS_HIP_TRY(hipMalloc(&h->d_work, (size_t)blocks * 6 * (size_t)h->host.n * sizeof(double)));
+    h->work_blocks = blocks;
+    return GPIS_OK;
+}
+
+// the arguments of cos / sin stayed inside the restated range (include/gpis.h): read after the stream drained
+inline int ws_check_overflow(WsHandle *h, hipStream_t s)
+{
+    unsigned long long ov = 0;
+    WS_HIP_TRY(hipMemcpyAsync(&ov, &h->d_counters->arg_overflow, sizeof ov, hipMemcpyDeviceToHost, s));
+    WS_HIP_TRY(hipStreamSynchronize(s));
+    if (ov) {
+        WS_HIP_TRY(hipMemsetAsync(&h->d_counters->arg_overflow, 0, sizeof ov, s));
+        WS_HIP_TRY(hipStreamSynchronize(s));
+        return ws_err(GPIS_ERR_UNSUPPORTED, "weight-space medium: a cos / sin argument reached |x| >= 105414350, where glibc's large-argument "
+                                            "reduction (not restated on the device) applies; the results of this call are not valid");
+    }
+    return GPIS_OK;
+}
+
+inline int ws_stage(WsHandle *h, int k, size_t bytes)
+{
+    if (h->stage_bytes[k] >= bytes) return GPIS_OK;
+    if (h->stage[k]) { WS_HIP_TRY(hipFree(h->stage[k])); h->stage[k] = nullptr; h->stage_bytes[k] = 0; }
+    const size_t cap = bytes + bytes / 4 + 4096;
+    WS_HIP_TRY(hipMalloc(&h->stage[k], cap));
+    h->stage_bytes[k] = cap;
+    return GPIS_OK;
+}
+
+}   // namespace gpis

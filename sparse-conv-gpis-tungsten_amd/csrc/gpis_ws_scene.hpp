@@ -1,0 +1,149 @@
+// gpis_ws_scene.hpp — scene S rendered through the weight-space GP medium: one fused kernel, one wave per sample.
+//
+// The estimator is gpis_render_scene_s's (gpis_hip.hip: k_scene_primary, k_scene_shade, k_scene_accumulate), bit for bit: the
+// camera ray and its four draws, the bounding-sphere chord, a primary sampleDistance, Lambert shading against the directional
+// light and one shadow transmittance per lit hit.  What differs is where the intermediate records live.  The staged drivers keep
+// a gpis_ray_in and a gpis_seg_out per sample in HBM between five launches; here a wave carries its sample from the camera to one
+// 8-byte record (WsSceneRec), and k_ws_scene_sum adds a pixel's records in sample order, so the image depends neither on the
+// order in which waves finish nor on how a frame is cut into calls.
+//
+// Two things the staged composition of gpis_ws_sample_distance_batch + gpis_ws_transmittance_batch cannot do:
+//   realization reuse — under single_realization or context GLOBAL the shadow segment's pixelSampleSegment is the primary's
+//       (ws_pss: w = 0), so the realization built for the primary march serves the shadow march; the other contexts rebuild for
+//       segment + 1, as the batch entries do;
+//   dynamic work fetch — a sample costs nothing (a miss), a few batches (a hit near the chord's start) or the whole chord and
+//       a shadow march; waves take the next sample index from a global counter (one atomic per wave per sample) instead of
+//       k_ws_march's static stride, so no wave idles behind a neighbour's long samples at the end of a launch.
+#pragma once
+#include "gpis_scene.hpp"
+#include "gpis_ws.hpp"
+
+#pragma clang fp contract(off)
+
+namespace gpis {
+
+// one sample's contribution: cos(normal, light) * visible, and bit 0 = the primary segment hit the surface,
+// bit 1 = lit (a shadow segment was marched; cv takes part in the pixel's sum)
+struct WsSceneRec { float cv; uint32_t flags; };
+
+GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_scene(const WsModel *__restrict__ Wp, SceneConst sc, size_t first_pixel, uint32_t n_samples,
+                                                                uint32_t *__restrict__ next, WsSceneRec *__restrict__ recs,
+                                                                double *__restrict__ workspace, WsCounters *__restrict__ counters)
+{
+    __shared__ WsLds L;
+    const WsModel &W = *Wp;
+    const gpis_scene_s &s = sc.s;
+    const int lane = (int)threadIdx.x;
+    double *own = workspace ? workspace + (size_t)blockIdx.x * 6 * (size_t)W.n : nullptr;
+    const bool reuse = W.single || W.ctx == GPIS_CTX_GLOBAL;      // the shadow segment's realization is the primary's
+    const V3 l = v3(sc.light[0], sc.light[1], sc.light[2]);
+    WsTally tally{0, 0};
+    bool overflow = false;
+    unsigned long long segs = 0;
+    for (;;) {
+        uint32_t i = 0;
+        if (lane == 0) i = atomicAdd(next, 1u);
+        i = __builtin_amdgcn_readfirstlane(i);
+        if (i >= n_samples) break;
+        // ---- k_scene_primary
+        const size_t pix = scene_pixel(s, first_pixel + i / s.spp_count);
+        const uint32_t x = (uint32_t)(pix % s.width), y = (uint32_t)(pix / s.width);
+        const uint32_t spp = s.spp_begin + i % s.spp_count;
+        Pcg32 g;
+        g.set_state((uint64_t)(uint32_t)(xxhash32_4(x, y, spp, s.scene_seed) + 1u));
+        const float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
+        const float u0 = normalized_uint(g.next_i()), u1 = normalized_uint(g.next_i());
+        const V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
+        const V3 d = v3(local.x, local.y, -local.z);
+        const V3 o = v3(s.cam_pos[0], s.cam_pos[1], s.cam_pos[2]);
+        WsSceneRec rec{0.f, 0u};
+        float t0 = 0.f, t1 = 0.f;
+        if (sphere_chord(o, d, s.bound_radius, t0, t1)) {
+            gpis_ray_in ray{};
+            ray.pos[0] = o.x; ray.pos[1] = o.y; ray.pos[2] = o.z;
+            ray.dir[0] = d.x; ray.dir[1] = d.y; ray.dir[2] = d.z;
+            ray.near_t = t0; ray.far_t = t1;
+            ray.pixel[0] = x; ray.pixel[1] = y; ray.spp = spp; ray.segment = 0;
+            ray.scene_seed = s.scene_seed; ray.info_t = 0.f; ray.u_jitter = u0;
+            ray.first_scatter = 1;
+            const double *B = W.basis;
+            if (!W.single) {
+                uint32_t pss[4];
+                ws_pss(W, x, y, spp, ray.segment, pss);
+                ws_build(W, pss, own, W.n, lane);        // each lane reads back only the functions it wrote
+                B = own;
+            }
+            segs++;
+            __syncthreads();
+            const gpis_seg_out r = ws_sample_distance(W, L, B, ray, lane, overflow, tally);
+            // ---- k_scene_shade
+            if (r.ok && !r.exited) {
+                rec.flags = 1u;
+                const double ax = r.aniso[0], ay = r.aniso[1], az = r.aniso[2];
+                const double len = sqrt(ax * ax + ay * ay + az * az);
+                const V3 nn = v3((float)(ax / len), (float)(ay / len), (float)(az / len));
+                const float c = dot(nn, l);
+                float s0, s1;
+                if (c > 0.f && sphere_chord(v3(r.p[0], r.p[1], r.p[2]), l, s.bound_radius, s0, s1)) {
+                    gpis_ray_in sh{};
+                    sh.pos[0] = r.p[0]; sh.pos[1] = r.p[1]; sh.pos[2] = r.p[2];
+                    sh.dir[0] = l.x; sh.dir[1] = l.y; sh.dir[2] = l.z;
+                    sh.near_t = 0.f; sh.far_t = s1;
+                    sh.pixel[0] = x; sh.pixel[1] = y; sh.spp = spp;
+                    sh.segment = ray.segment + 1;
+                    sh.scene_seed = ray.scene_seed;
+                    sh.info_t = ray.info_t + r.sample_t;
+                    sh.u_jitter = u1;
+                    sh.first_scatter = 0;
+                    sh.bounce = ray.bounce + 1;
+                    sh.last_val = r.last_val;
+                    sh.last_gp_id = r.gp_id;
+                    sh.last_aniso[0] = r.aniso[0]; sh.last_aniso[1] = r.aniso[1]; sh.last_aniso[2] = r.aniso[2];
+                    if (!reuse) {
+                        uint32_t pss[4];
+                        ws_pss(W, x, y, spp, sh.segment, pss);
+                        ws_build(W, pss, own, W.n, lane);
+                    }
+                    segs++;
+                    bool first_scatter = false;
+                    int last_gp_id = sh.last_gp_id;
+                    V3d last_aniso{sh.last_aniso[0], sh.last_aniso[1], sh.last_aniso[2]};
+                    __syncthreads();
+                    const bool vis = ws_transmittance_one(W, L, B, sh, first_scatter, last_gp_id, last_aniso, lane, overflow, tally);
+                    rec.cv = c * (vis ? 1.f : 0.f);
+                    rec.flags = 3u;
+                }
+            }
+        }
+        if (lane == 0) recs[i] = rec;
+    }
+    if (lane == 0 && counters && segs) {
+        atomicAdd(&counters->n_eval, tally.eval);
+        atomicAdd(&counters->n_spec, tally.spec);
+        atomicAdd(&counters->n_seg, segs);
+    }
+    if (lane == 0 && overflow && counters)
+        atomicAdd(&counters->arg_overflow, 1ull);
+}
+
+// one lane per pixel: sequential sum over its samples, in sample order (k_scene_accumulate's sum)
+GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_ws_scene_sum(SceneConst sc, size_t first_pixel, size_t n_pixels, const WsSceneRec *__restrict__ recs,
+                                                                     float *__restrict__ radiance_sum, uint32_t *__restrict__ hit_count)
+{
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_pixels) return;
+    const uint32_t spp = sc.s.spp_count;
+    float acc = 0.f;
+    uint32_t hits = 0;
+    for (uint32_t k = 0; k < spp; ++k) {
+        const WsSceneRec r = recs[j * spp + k];
+        hits += r.flags & 1u;
+        if (r.flags & 2u)
+            acc += r.cv * sc.s.light_radiance;
+    }
+    const size_t pix = scene_pixel(sc.s, first_pixel + j);
+    radiance_sum[pix] += acc;
+    if (hit_count) hit_count[pix] += hits;
+}
+
+}   // namespace gpis

@@ -1,67 +1,21 @@
 // tu_ws.hip — the weight-space GP medium (gpis_ws.hpp): its kernels and its gpis_ws_* entry points (include/gpis.h).
 //
-// A weight-space handle is its own object (WsHandle) behind the opaque gpis_medium pointer; its first word is kWsHandleTag,
-// where a sparse-convolution handle holds gpis_params::abi_version, so either family of entries can refuse the other's handles.
+// The handle (WsHandle) and the helpers every gpis_ws_* translation unit shares are in gpis_ws_host.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <mutex>
 #include <new>
 
 #include "gpis.h"
 #include "gpis_ws.hpp"
+#include "gpis_ws_host.hpp"
 
 #pragma clang fp contract(off)
-
-namespace gpis {
-// gpis_hip.hip
-int host_build_model(const gpis_params &P, DevModel &M);
-int host_set_err(int code, const char *msg);
-bool ws_is_handle(const void *m);
-int ws_destroy(gpis_medium *m);
-}   // namespace gpis
 
 using namespace gpis;
 
 namespace {
-
-struct WsHandle {
-    uint32_t tag = kWsHandleTag;          // must stay the first member
-    int device = 0;
-    gpis_params params{};
-    gpis_ws_params wsp{};
-    WsModel host{};
-    WsModel *d_model = nullptr;
-    WsCounters *d_counters = nullptr;
-    double *d_basis = nullptr;            // single realization: [6][N]
-    double *d_work = nullptr;             // per-path realizations: one [6][N] slice per resident workgroup
-    unsigned work_blocks = 0;
-    unsigned grid_cap = 0;                // resident one-wave workgroups of k_ws_march on this device
-    std::mutex mu;                        // serialises the entries of one handle (workspace, staging, counters)
-    void *stage[3] = {nullptr, nullptr, nullptr};
-    size_t stage_bytes[3] = {0, 0, 0};
-};
-
-int ws_err(int code, const char *fmt, ...)
-{
-    char buf[480];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return host_set_err(code, buf);
-}
-
-#define WS_HIP_TRY(expr)                                                                                              \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess) return ws_err(GPIS_ERR_DEVICE, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-WsHandle *as_ws(gpis_medium *m) { return ws_is_handle(m) ? reinterpret_cast<WsHandle *>(m) : nullptr; }
 
 // the refusals of the built scope (include/gpis.h); no device needed
 int ws_validate(const gpis_params &P, const gpis_ws_params &S)
@@ -95,59 +49,18 @@ int ws_validate(const gpis_params &P, const gpis_ws_params &S)
     return GPIS_OK;
 }
 
-int launch_check(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ws_err(GPIS_ERR_DEVICE, "%s launch: %s", what, hipGetErrorString(e));
-    return GPIS_OK;
-}
-
-int ensure_work(WsHandle *h, unsigned blocks)
-{
-    if (h->host.single || h->host.n == 0 || h->work_blocks >= blocks) return GPIS_OK;
-    if (h->d_work) { WS_HIP_TRY(hipDeviceSynchronize()); WS_HIP_TRY(hipFree(h->d_work)); h->d_work = nullptr; h->work_blocks = 0; }
-    WS_HIP_TRY(hipMalloc(&h->d_work, (size_t)blocks * 6 * (size_t)h->host.n * sizeof(double)));
-    h->work_blocks = blocks;
-    return GPIS_OK;
-}
-
-// the arguments of cos / sin stayed inside the restated range (include/gpis.h): read after the stream drained
-int check_overflow(WsHandle *h, hipStream_t s)
-{
-    unsigned long long ov = 0;
-    WS_HIP_TRY(hipMemcpyAsync(&ov, &h->d_counters->arg_overflow, sizeof ov, hipMemcpyDeviceToHost, s));
-    WS_HIP_TRY(hipStreamSynchronize(s));
-    if (ov) {
-        WS_HIP_TRY(hipMemsetAsync(&h->d_counters->arg_overflow, 0, sizeof ov, s));
-        WS_HIP_TRY(hipStreamSynchronize(s));
-        return ws_err(GPIS_ERR_UNSUPPORTED, "weight-space medium: a cos / sin argument reached |x| >= 105414350, where glibc's large-argument "
-                                            "reduction (not restated on the device) applies; the results of this call are not valid");
-    }
-    return GPIS_OK;
-}
-
 int march(WsHandle *h, bool want_sample, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, uint8_t *visible, hipStream_t s)
 {
     if (n == 0) return GPIS_OK;
     WS_HIP_TRY(hipSetDevice(h->device));
     const unsigned grid = (unsigned)(n < h->grid_cap ? n : h->grid_cap);
-    if (int st = ensure_work(h, grid)) return st;
+    if (int st = ws_ensure_work(h, grid)) return st;
     if (want_sample)
         k_ws_march<true><<<grid, 64, 0, s>>>(h->d_model, n, rays, out, nullptr, h->d_work, h->d_counters);
     else
         k_ws_march<false><<<grid, 64, 0, s>>>(h->d_model, n, rays, nullptr, visible, h->d_work, h->d_counters);
-    if (int st = launch_check("k_ws_march")) return st;
-    return check_overflow(h, s);
-}
-
-int stage(WsHandle *h, int k, size_t bytes)
-{
-    if (h->stage_bytes[k] >= bytes) return GPIS_OK;
-    if (h->stage[k]) { WS_HIP_TRY(hipFree(h->stage[k])); h->stage[k] = nullptr; h->stage_bytes[k] = 0; }
-    const size_t cap = bytes + bytes / 4 + 4096;
-    WS_HIP_TRY(hipMalloc(&h->stage[k], cap));
-    h->stage_bytes[k] = cap;
-    return GPIS_OK;
+    if (int st = ws_launch_check("k_ws_march")) return st;
+    return ws_check_overflow(h, s);
 }
 
 int march_host(WsHandle *h, bool want_sample, size_t n, const gpis_ray_in *rays, void *out)
@@ -155,8 +68,8 @@ int march_host(WsHandle *h, bool want_sample, size_t n, const gpis_ray_in *rays,
     if (n == 0) return GPIS_OK;
     WS_HIP_TRY(hipSetDevice(h->device));
     const size_t rec = want_sample ? sizeof(gpis_seg_out) : 1;
-    if (int st = stage(h, 0, n * sizeof(gpis_ray_in))) return st;
-    if (int st = stage(h, 1, n * rec)) return st;
+    if (int st = ws_stage(h, 0, n * sizeof(gpis_ray_in))) return st;
+    if (int st = ws_stage(h, 1, n * rec)) return st;
     WS_HIP_TRY(hipMemcpy(h->stage[0], rays, n * sizeof(gpis_ray_in), hipMemcpyHostToDevice));
     const int st = march(h, want_sample, n, (const gpis_ray_in *)h->stage[0], want_sample ? (gpis_seg_out *)h->stage[1] : nullptr,
                          want_sample ? nullptr : (uint8_t *)h->stage[1], nullptr);
@@ -178,6 +91,7 @@ int ws_destroy(gpis_medium *m)
     if (h->d_counters) (void)hipFree(h->d_counters);
     if (h->d_basis) (void)hipFree(h->d_basis);
     if (h->d_work) (void)hipFree(h->d_work);
+    if (h->d_scene_next) (void)hipFree(h->d_scene_next);
     for (int k = 0; k < 3; ++k)
         if (h->stage[k]) (void)hipFree(h->stage[k]);
     h->tag = 0;
@@ -242,7 +156,7 @@ extern "C" int gpis_ws_create(const gpis_params *params, const gpis_ws_params *w
         return fail(ws_err(GPIS_ERR_DEVICE, "gpis_ws_create: upload failed"));
     if (W.single && W.n > 0) {
         k_ws_basis<0><<<(W.n + 255) / 256, 256>>>(h->d_model, 1, nullptr, h->d_basis, 0);     // pss (0,0,0,0)
-        if ((st = launch_check("k_ws_basis"))) return fail(st);
+        if ((st = ws_launch_check("k_ws_basis"))) return fail(st);
         if (hipDeviceSynchronize() != hipSuccess) return fail(ws_err(GPIS_ERR_DEVICE, "gpis_ws_create: basis build failed"));
     }
     int per_cu = 0;
@@ -251,10 +165,6 @@ extern "C" int gpis_ws_create(const gpis_params *params, const gpis_ws_params *w
     *out = reinterpret_cast<gpis_medium *>(h);
     return GPIS_OK;
 }
-
-#define WS_HANDLE(m)                                                                                            \
-    WsHandle *h = as_ws(m);                                                                                     \
-    if (!h) return ws_err(GPIS_ERR_INVALID_ARG, "%s: not a weight-space handle (gpis_ws_create)", __func__)
 
 extern "C" int gpis_ws_sample_distance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, void *stream)
 {
@@ -292,10 +202,10 @@ extern "C" int gpis_ws_eval_batch(gpis_medium *m, size_t n, const gpis_ws_query 
     std::lock_guard<std::mutex> lock(h->mu);
     WS_HIP_TRY(hipSetDevice(h->device));
     const unsigned grid = (unsigned)(n < h->grid_cap ? n : h->grid_cap);
-    if (int st = ensure_work(h, grid)) return st;
+    if (int st = ws_ensure_work(h, grid)) return st;
     k_ws_eval<0><<<grid, 64, 0, (hipStream_t)stream>>>(h->d_model, n, q, value, grad3, gp_id, h->d_work, h->d_counters);
-    if (int st = launch_check("k_ws_eval")) return st;
-    return check_overflow(h, (hipStream_t)stream);
+    if (int st = ws_launch_check("k_ws_eval")) return st;
+    return ws_check_overflow(h, (hipStream_t)stream);
 }
 extern "C" int gpis_ws_basis_batch(gpis_medium *m, size_t n, const uint32_t *pss4, double *out, void *stream)
 {
@@ -306,7 +216,7 @@ extern "C" int gpis_ws_basis_batch(gpis_medium *m, size_t n, const uint32_t *pss
     WS_HIP_TRY(hipSetDevice(h->device));
     const size_t blocks = (total + 255) / 256;
     k_ws_basis<0><<<(unsigned)(blocks < 65536 ? blocks : 65536), 256, 0, (hipStream_t)stream>>>(h->d_model, n, pss4, out, 1);
-    return launch_check("k_ws_basis");
+    return ws_launch_check("k_ws_basis");
 }
 extern "C" int gpis_ws_get_counters(gpis_medium *m, uint64_t *n_eval, uint64_t *n_spec, uint64_t *n_seg)
 {
