@@ -701,6 +701,29 @@ int gpis_ws_reset_counters(gpis_medium *m);
  * above, for which it synchronises `stream` once per call.  gpis_ws_get_counters: n_eval counts the reference's evaluations,
  * n_seg the primary segments marched plus the shadow segments marched. */
 int gpis_ws_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radiance_sum, uint32_t *hit_count, void *stream);
+/* gpis_render_scene_s_paths over the weight-space medium: the same estimator, operation for operation.  Rows, tile-row shard and
+ * spp range as gpis_ws_render_scene_s.  Per sample: PCG32 seeded with xxhash32(x, y, spp, scene_seed) + 1, the draws jx, jy,
+ * u_march, the camera ray and its bounding-sphere chord; then for bounce = 0 .. max_path_bounces-1 a sampleDistance with segment
+ * word = bounce (!ok ends the path; throughput *= weight[0]; exited ends the path).  On a hit, while bounce < max_path_bounces-1:
+ * next-event estimation when wi.z > 0, wo.z > 0 (Duff frame about the normalised aniso) and the light direction has a chord —
+ * one shadow transmittance through a state copy with segment bounce+1, first_scatter = 0 and last_aniso / last_gp_id / last_val /
+ * info_t / bounce carried from the result, its jitter the next draw of the stream, contributing
+ * throughput * (albedo * (1/3.1415926536f) * wo.z * light_radiance) when visible; then the cosine bounce by unit-disk rejection
+ * (sqrt only), throughput *= albedo, and — only if the path lives on — the next chord, segment bounce+1 and the next jitter.  The
+ * segment of bounce max_path_bounces-1 is marched (it counts below) although nothing after it reaches the image, so
+ * max_path_bounces = 1 adds zeros.  A sample's emission is the sum of its contributions in bounce order; ACCUMULATES each pixel's
+ * sum of emissions, taken in sample order, into radiance_sum[height*width] (float, device pointer, indexed y*width+x).  The image
+ * does not depend on how a frame is cut into calls, nor on the order in which waves finish.  max_path_bounces >= 1, else
+ * GPIS_ERR_INVALID_ARG; albedo is taken as given.
+ * One fused kernel, one wave per sample, the whole path in the wave: no ray or segment records in device memory.  Under
+ * single_realization or context GLOBAL one realization serves the whole path; under the other contexts the shadow segment of
+ * bounce b and the path segment of bounce b+1 carry the same segment word b+1 and are marched from one realization.
+ * Weight-space handles only (any other handle: GPIS_ERR_INVALID_ARG; gpis_render_scene_s_paths keeps refusing weight-space
+ * handles).  Returns GPIS_ERR_UNSUPPORTED under the cos / sin argument rule above, for which it synchronises `stream` once per
+ * call.  gpis_ws_get_counters: n_eval counts the reference's evaluations, n_seg the path segments marched plus the shadow
+ * segments marched. */
+int gpis_ws_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo,
+                                 float *radiance_sum, void *stream);
 
 #ifdef __cplusplus
 }

@@ -334,7 +334,7 @@ class GpisLib:
         "gpis_set_variance_grid", "gpis_default_scene_s", "gpis_reserve_scene_workspace", "gpis_render_scene_s", "gpis_render_scene_s_paths", "gpis_render_scene_s_nee",
         "gpis_ws_default_params", "gpis_ws_create", "gpis_ws_sample_distance_batch", "gpis_ws_transmittance_batch",
         "gpis_ws_sample_distance_host", "gpis_ws_transmittance_host", "gpis_ws_eval_batch", "gpis_ws_basis_batch",
-        "gpis_ws_get_counters", "gpis_ws_reset_counters", "gpis_ws_render_scene_s",
+        "gpis_ws_get_counters", "gpis_ws_reset_counters", "gpis_ws_render_scene_s", "gpis_ws_render_scene_s_paths",
     ]
 
     def __init__(self, path=None):
@@ -406,6 +406,7 @@ class GpisLib:
         L.gpis_default_scene_s.restype = None
         L.gpis_render_scene_s.argtypes = [vp, vp, vp, vp, vp]
         L.gpis_ws_render_scene_s.argtypes = [vp, vp, vp, vp, vp]
+        L.gpis_ws_render_scene_s_paths.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
         L.gpis_render_scene_s_paths.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
         L.gpis_render_scene_s_nee.argtypes = [vp, vp, vp, vp, vp]
         L.gpis_ws_default_params.argtypes = [vp]
@@ -805,6 +806,20 @@ class WeightSpaceMedium:
         if not want_hits:
             return rad
         return rad, d_hit.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
+
+    def render_scene_s_paths(self, scene, max_bounces, albedo):
+        """One call of the multi-bounce path driver (gpis_ws_render_scene_s_paths) into a zeroed device buffer: the float32
+        sum-of-radiance image (height, width) of the rows, shard and samples `scene` selects."""
+        import torch
+        scene = np.array(scene, dtype=SCENE_S).reshape(())
+        hgt, wid = int(scene["height"]), int(scene["width"])
+        dev = torch.device("cuda", self.device)
+        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.L.check(self.L.lib.gpis_ws_render_scene_s_paths(self.h, _ptr(scene), int(max_bounces), ctypes.c_float(albedo),
+                                                             ctypes.c_void_p(d_rad.data_ptr()), None), "gpis_ws_render_scene_s_paths")
+        torch.cuda.synchronize(dev)
+        return d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy()
 
     def counters(self):
         e, s, g = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()

@@ -1,5 +1,5 @@
 // gpis_ws_host.hpp — host side of a weight-space handle, shared by the translation units that implement gpis_ws_* entries
-// (tu_ws.hip: handle, batch entries; tu_ws_scene.hip: the scene-S frame driver).
+// (tu_ws.hip: handle, batch entries; tu_ws_scene.hip: the scene-S frame driver; tu_ws_paths.hip: the multi-bounce path driver).
 //
 // A weight-space handle is its own object (WsHandle) behind the opaque gpis_medium pointer; its first word is kWsHandleTag,
 // where a sparse-convolution handle holds gpis_params::abi_version, so either family of entries can refuse the other's handles.
@@ -33,9 +33,10 @@ struct WsHandle {
     unsigned work_blocks = 0;
     unsigned grid_cap = 0;                // resident one-wave workgroups of k_ws_march on this device
     unsigned scene_grid_cap = 0;          // ... of k_ws_scene (tu_ws_scene.hip; 0 until the first frame)
-    unsigned *d_scene_next = nullptr;     // k_ws_scene's work counter: the next sample of the chunk
+    unsigned paths_grid_cap = 0;          // ... of k_ws_paths (tu_ws_paths.hip; 0 until the first frame)
+    unsigned *d_scene_next = nullptr;     // the frame drivers' work counter (k_ws_scene, k_ws_paths): the next sample of the chunk
     std::mutex mu;                        // serialises the entries of one handle (workspace, staging, counters)
-    void *stage[3] = {nullptr, nullptr, nullptr};     // 0, 1: the *_host entries' rays / results; 2: the frame driver's sample records
+    void *stage[3] = {nullptr, nullptr, nullptr};     // 0, 1: the *_host entries' rays / results; 2: the frame drivers' sample records
     size_t stage_bytes[3] = {0, 0, 0};
 };
 

@@ -1,0 +1,186 @@
+// gpis_ws_paths.hpp — multi-bounce paths on scene S through the weight-space GP medium: one fused kernel, one wave per sample.
+//
+// The estimator is gpis_render_scene_s_paths's (gpis_hip.hip: k_paths_begin, k_paths_shade, k_paths_nee_add, k_paths_accumulate),
+// operation for operation: the camera ray and its three draws, the bounding-sphere chord, then per bounce a sampleDistance with
+// segment word = bounce, next-event estimation of the directional light through a state copy with segment + 1 (one shadow
+// transmittance), and a cosine bounce drawn by unit-disk rejection.  The draw order of the
+// sample's PCG32 stream is jx, jy, u_march, then per bounce [u_shadow when NEE runs], the disk pairs, [u_march of the next
+// segment when the path lives on].  The segment of bounce max - 1 is marched as the reference marches it (it counts in n_eval and
+// n_seg) although nothing after it can reach the image: no NEE runs there and the light is a Dirac delta.
+//
+// The whole path stays in the wave: ray, carried state (last_aniso, last_gp_id, last_val, info_t, bounce), PCG state, throughput
+// and emission are wave-uniform, and no gpis_ray_in / gpis_seg_out record goes to HBM.  A sample ends in one 4-byte record (its
+// emission); k_ws_paths_sum adds a pixel's records in sample order, so the image depends neither on the order in which waves
+// finish nor on how a frame is cut into calls.  Work fetch is k_ws_scene's: the next sample index comes from a global counter.
+//
+// Realization reuse, which a staged composition of gpis_ws_sample_distance_batch + gpis_ws_transmittance_batch cannot do (every
+// batch entry rebuilds the realization of every ray):
+//   single_realization — the handle's basis serves everything;
+//   context GLOBAL — pss.w = 0 for every segment (ws_pss), so one realization is built per sample and serves the whole path;
+//   the other contexts — the shadow segment of bounce b and the path segment of bounce b + 1 carry the SAME segment word b + 1,
+//       so one ws_build serves both: the shadow segment and the next path segment are marched from the same basis.  A path of k
+//       hits builds k + 1 realizations where the staged form builds up to 2k + 1.
+// One realization per wave at a time is enough: the workspace is the handle's one [6][N] slice per workgroup.
+//
+// The shading arithmetic (Duff frame, wi / wo, disk rejection, next-ray fill) restates k_paths_shade's line for line rather than
+// sharing a function with it: k_paths_shade is left as it is, and the tests pin the two against the same C.
+#pragma once
+#include "gpis_scene.hpp"
+#include "gpis_ws.hpp"
+
+#pragma clang fp contract(off)
+
+namespace gpis {
+
+// one sample's emission: the sum of its NEE contributions in bounce order (0 for a sample that misses the bound)
+struct WsPathsRec { float emission; };
+
+GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_paths(const WsModel *__restrict__ Wp, SceneConst sc, size_t first_pixel, uint32_t n_samples,
+                                                                int max_bounces, float albedo, uint32_t *__restrict__ next_sample,
+                                                                WsPathsRec *__restrict__ recs, double *__restrict__ workspace,
+                                                                WsCounters *__restrict__ counters)
+{
+    __shared__ WsLds L;
+    const WsModel &W = *Wp;
+    const gpis_scene_s &s = sc.s;
+    const int lane = (int)threadIdx.x;
+    double *own = workspace ? workspace + (size_t)blockIdx.x * 6 * (size_t)W.n : nullptr;
+    const bool per_path = !W.single;
+    const bool whole_path = W.ctx == GPIS_CTX_GLOBAL;             // per-path realizations: one for all segments of a sample
+    const double *B = per_path ? own : W.basis;
+    const V3 l = v3(sc.light[0], sc.light[1], sc.light[2]);
+    WsTally tally{0, 0};
+    bool overflow = false;
+    unsigned long long segs = 0;
+    for (;;) {
+        uint32_t i = 0;
+        if (lane == 0) i = atomicAdd(next_sample, 1u);
+        i = __builtin_amdgcn_readfirstlane(i);
+        if (i >= n_samples) break;
+        // ---- k_paths_begin
+        const size_t pix = scene_pixel(s, first_pixel + i / s.spp_count);
+        const uint32_t x = (uint32_t)(pix % s.width), y = (uint32_t)(pix / s.width);
+        const uint32_t spp = s.spp_begin + i % s.spp_count;
+        Pcg32 g;
+        g.set_state((uint64_t)(uint32_t)(xxhash32_4(x, y, spp, s.scene_seed) + 1u));
+        const float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
+        const float u0 = normalized_uint(g.next_i());
+        const V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
+        const V3 d0 = v3(local.x, local.y, -local.z);
+        const V3 o0 = v3(s.cam_pos[0], s.cam_pos[1], s.cam_pos[2]);
+        float emission = 0.f;
+        float c0 = 0.f, c1 = 0.f;
+        if (sphere_chord(o0, d0, s.bound_radius, c0, c1)) {
+            gpis_ray_in ray{};
+            ray.pos[0] = o0.x; ray.pos[1] = o0.y; ray.pos[2] = o0.z;
+            ray.dir[0] = d0.x; ray.dir[1] = d0.y; ray.dir[2] = d0.z;
+            ray.near_t = c0; ray.far_t = c1;
+            ray.pixel[0] = x; ray.pixel[1] = y; ray.spp = spp; ray.segment = 0;
+            ray.scene_seed = s.scene_seed; ray.info_t = 0.f; ray.u_jitter = u0;
+            ray.first_scatter = 1;
+            float thr = 1.f;
+            int built = -1;                  // segment word of the realization in `own` (any word under GLOBAL once built)
+            for (int bounce = 0; bounce < max_bounces; ++bounce) {
+                if (per_path && (whole_path ? built < 0 : built != bounce)) {
+                    uint32_t pss[4];
+                    ws_pss(W, x, y, spp, (uint32_t)bounce, pss);
+                    ws_build(W, pss, own, W.n, lane);        // each lane reads back only the functions it wrote
+                    built = bounce;
+                }
+                segs++;
+                __syncthreads();
+                const gpis_seg_out r = ws_sample_distance(W, L, B, ray, lane, overflow, tally);
+                // ---- k_paths_shade
+                if (!r.ok) break;
+                thr = thr * r.weight[0];
+                if (r.exited) break;
+                if (bounce + 1 >= max_bounces) break;        // no NEE at the last bounce, and the bounce itself cannot be seen
+                const double ax = r.aniso[0], ay = r.aniso[1], az = r.aniso[2];
+                const double len = sqrt(ax * ax + ay * ay + az * az);
+                const V3 n = v3((float)(ax / len), (float)(ay / len), (float)(az / len));
+                const Frame fr = frame_from_normal(n);
+                const V3 dir = v3(ray.dir[0], ray.dir[1], ray.dir[2]);
+                const V3 wi = normalized(to_local(fr, v3(-dir.x, -dir.y, -dir.z)));
+                const V3 p = v3(r.p[0], r.p[1], r.p[2]);
+                gpis_ray_in nx{};
+                nx.pos[0] = p.x; nx.pos[1] = p.y; nx.pos[2] = p.z;
+                nx.near_t = 0.f;
+                nx.pixel[0] = x; nx.pixel[1] = y; nx.spp = spp;
+                nx.scene_seed = ray.scene_seed;
+                nx.info_t = ray.info_t + r.sample_t;
+                nx.first_scatter = 0;
+                nx.bounce = ray.bounce + 1;
+                nx.last_val = r.last_val;
+                nx.last_gp_id = r.gp_id;
+                nx.last_aniso[0] = r.aniso[0]; nx.last_aniso[1] = r.aniso[1]; nx.last_aniso[2] = r.aniso[2];
+                nx.segment = (uint32_t)bounce + 1;
+                {
+                    const V3 wo = normalized(to_local(fr, l));
+                    if (wi.z > 0.0f && wo.z > 0.0f) {
+                        const float f = albedo * (1.0f / 3.1415926536f) * wo.z;
+                        float t0, t1;
+                        if (sphere_chord(p, l, s.bound_radius, t0, t1)) {
+                            gpis_ray_in sh = nx;
+                            sh.dir[0] = l.x; sh.dir[1] = l.y; sh.dir[2] = l.z;
+                            sh.far_t = t1;
+                            sh.u_jitter = normalized_uint(g.next_i());
+                            const float contrib = thr * (f * s.light_radiance);
+                            if (per_path && !whole_path) {   // segment word bounce + 1: also the next path segment's realization
+                                uint32_t pss[4];
+                                ws_pss(W, x, y, spp, sh.segment, pss);
+                                ws_build(W, pss, own, W.n, lane);
+                                built = bounce + 1;
+                            }
+                            segs++;
+                            bool first_scatter = false;
+                            int last_gp_id = sh.last_gp_id;
+                            V3d last_aniso{sh.last_aniso[0], sh.last_aniso[1], sh.last_aniso[2]};
+                            __syncthreads();
+                            const bool vis = ws_transmittance_one(W, L, B, sh, first_scatter, last_gp_id, last_aniso, lane, overflow, tally);
+                            emission += vis ? contrib : 0.f;
+                        }
+                    }
+                }
+                if (!(wi.z > 0.0f)) break;
+                float dx, dy, d2;
+                do {
+                    dx = 2.f * normalized_uint(g.next_i()) - 1.f;
+                    dy = 2.f * normalized_uint(g.next_i()) - 1.f;
+                    d2 = dx * dx + dy * dy;
+                } while (!(d2 < 1.f));
+                const float rem = 1.0f - d2;
+                const V3 w = normalized(to_global(fr, v3(dx, dy, sqrtf(rem > 0.f ? rem : 0.f))));
+                thr *= albedo;
+                float t0, t1;
+                if (!sphere_chord(p, w, s.bound_radius, t0, t1)) break;
+                nx.dir[0] = w.x; nx.dir[1] = w.y; nx.dir[2] = w.z;
+                nx.far_t = t1;
+                nx.u_jitter = normalized_uint(g.next_i());
+                ray = nx;
+            }
+        }
+        if (lane == 0) recs[i] = WsPathsRec{emission};
+    }
+    if (lane == 0 && counters && segs) {
+        atomicAdd(&counters->n_eval, tally.eval);
+        atomicAdd(&counters->n_spec, tally.spec);
+        atomicAdd(&counters->n_seg, segs);
+    }
+    if (lane == 0 && overflow && counters)
+        atomicAdd(&counters->arg_overflow, 1ull);
+}
+
+// one lane per pixel: sequential sum over its samples' emissions, in sample order (k_paths_accumulate's sum)
+GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_ws_paths_sum(SceneConst sc, size_t first_pixel, size_t n_pixels, const WsPathsRec *__restrict__ recs,
+                                                                     float *__restrict__ radiance_sum)
+{
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_pixels) return;
+    const uint32_t spp = sc.s.spp_count;
+    float acc = 0.f;
+    for (uint32_t k = 0; k < spp; ++k)
+        acc += recs[j * spp + k].emission;
+    radiance_sum[scene_pixel(sc.s, first_pixel + j)] += acc;
+}
+
+}   // namespace gpis
