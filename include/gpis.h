@@ -405,7 +405,8 @@ int gpis_mean_color_emission_host(gpis_medium *m, size_t n, const double *p3, fl
 /* Medium::sampleDistance / transmittance of the function-space medium (GaussianProcessMedium.cpp:221-393 over
  * FunctionSpaceGaussianProcessMedium::intersectGP / sampleGradient).  rays[i].u_jitter is not used (every variate comes from
  * states[i].sampler_state); states are read and written in place (device pointers).  The two entries share one device
- * workspace per handle: launches of the SAME handle must be ordered (one stream, or an event between them). */
+ * workspace per handle: launches of the SAME handle must be ordered (one stream, or an event between them).  The frame of this
+ * medium: gpis_fs_render_scene_s, at the end of this header. */
 int gpis_fs_sample_distance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_fs_state *states, gpis_seg_out *out, void *stream);
 int gpis_fs_transmittance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_fs_state *states, uint8_t *visible, void *stream);
 /* The same two entries for host pointers (synchronous; what the Medium binding of the function-space medium calls with a batch
@@ -724,6 +725,32 @@ int gpis_ws_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radianc
  * segments marched. */
 int gpis_ws_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo,
                                  float *radiance_sum, void *stream);
+
+/* gpis_render_scene_s over the function-space medium: the frame of gpis_ws_render_scene_s (above) with this medium's sampler and
+ * state.  Covers the rows [y_begin, y_begin+y_count), the tile-row shard (shard_index / shard_count) and the samples
+ * [spp_begin, spp_begin+spp_count) that `s` selects.  Per sample (x, y, k): ONE PCG32 stream, set_state(xxhash32(x, y, k,
+ * scene_seed) + 1); its first two draws are jx, jy, and the medium draws every later variate from it, as the reference's medium
+ * draws from the path's PathSampleGenerator (no u_march / u_shadow is drawn; u_jitter is not read).  The camera ray and its
+ * bounding-sphere chord are gpis_render_scene_s's (first_scatter = 1, bounce = 0, segment = 0); a miss contributes nothing.  The
+ * primary segment is a sampleDistance from an empty state (has_context = 0) whose sampler_state is the stream after jx, jy; a hit
+ * is ok && !exited (!ok is neither a hit nor lit).  Lambert shading against the directional light: n = float(aniso / |aniso|),
+ * c = n . l; when c > 0 and (p, l) meets the bounding sphere, one shadow transmittance with near 0, far t1, segment + 1,
+ * first_scatter = 0, bounce + 1 and last_aniso / last_gp_id / last_val / info_t + sample_t carried from the primary result.  The
+ * shadow segment CONTINUES from the state the primary left — its context (points, derivs, values, sampled_grad, is_intersect)
+ * and the sampler where the primary stopped — as in the reference, so Renewal, Renewal+ and Global condition it on the primary's
+ * values.  It runs in place on the sample's one state; nothing follows it in this estimator, so that equals running on a copy.
+ * Contribution (c * (visible ? 1 : 0)) * light_radiance.
+ * ACCUMULATES each pixel's sum, taken in sample order from zero and added once per call, into radiance_sum[height*width] (float,
+ * device pointer, indexed y*width+x; the caller divides by the total spp) and the per-pixel hits into hit_count (device pointer,
+ * may be NULL).  The image does not depend on how a frame is cut into calls (rows, shards, spp ranges, chunks) nor on the order
+ * in which workgroups finish; nothing is added atomically into the image.
+ * One fused kernel, one wave per sample in flight, work taken from a global counter: no state, ray or segment record per sample in
+ * device memory (one state slot per resident workgroup, 8 B of records per sample of a chunk; GPIS_OPT_CHUNK_LOG2 sets the chunk,
+ * 0 = 2^22 samples).  Handles of gpis_create whose parameters the gpis_fs_* entries accept (squared-exponential covariance,
+ * analytic mean, 2..64 sample points); anything else, a weight-space handle included: GPIS_ERR_INVALID_ARG.  The entry shares the
+ * handle's function-space workspace with the gpis_fs_* batch entries: launches of the SAME handle must be ordered (one stream, or
+ * an event between them). */
+int gpis_fs_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radiance_sum, uint32_t *hit_count, void *stream);
 
 #ifdef __cplusplus
 }

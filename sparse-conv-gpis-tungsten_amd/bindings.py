@@ -335,6 +335,7 @@ class GpisLib:
         "gpis_ws_default_params", "gpis_ws_create", "gpis_ws_sample_distance_batch", "gpis_ws_transmittance_batch",
         "gpis_ws_sample_distance_host", "gpis_ws_transmittance_host", "gpis_ws_eval_batch", "gpis_ws_basis_batch",
         "gpis_ws_get_counters", "gpis_ws_reset_counters", "gpis_ws_render_scene_s", "gpis_ws_render_scene_s_paths",
+        "gpis_fs_render_scene_s",
     ]
 
     def __init__(self, path=None):
@@ -406,6 +407,7 @@ class GpisLib:
         L.gpis_default_scene_s.restype = None
         L.gpis_render_scene_s.argtypes = [vp, vp, vp, vp, vp]
         L.gpis_ws_render_scene_s.argtypes = [vp, vp, vp, vp, vp]
+        L.gpis_fs_render_scene_s.argtypes = [vp, vp, vp, vp, vp]
         L.gpis_ws_render_scene_s_paths.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
         L.gpis_render_scene_s_paths.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
         L.gpis_render_scene_s_nee.argtypes = [vp, vp, vp, vp, vp]
@@ -569,6 +571,25 @@ class Medium:
 
     def fs_transmittance(self, rays, states):
         return self._fs_call("gpis_fs_transmittance_batch", rays, states, False)
+
+    def fs_render_scene_s(self, scene, want_hits=False):
+        """One call of the function-space scene-S frame driver (gpis_fs_render_scene_s) into zeroed device buffers: the float32
+        sum-of-radiance image (height, width) of the rows, shard and samples `scene` selects, and the per-pixel hit counts when
+        asked."""
+        import torch
+        scene = np.array(scene, dtype=SCENE_S).reshape(())
+        hgt, wid = int(scene["height"]), int(scene["width"])
+        dev = torch.device("cuda", self.device)
+        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
+        d_hit = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_hits else None
+        torch.cuda.synchronize(dev)
+        self.L.check(self.L.lib.gpis_fs_render_scene_s(self.h, _ptr(scene), ctypes.c_void_p(d_rad.data_ptr()),
+                                                       ctypes.c_void_p(d_hit.data_ptr()) if want_hits else None, None), "gpis_fs_render_scene_s")
+        torch.cuda.synchronize(dev)
+        rad = d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy()
+        if not want_hits:
+            return rad
+        return rad, d_hit.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
 
     def mean_color_emission(self, points):
         """(color, emission) of the mean at double-precision points (n, 3)"""

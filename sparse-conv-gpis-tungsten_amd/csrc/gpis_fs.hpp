@@ -789,6 +789,119 @@ GPIS_DEV bool fs_transmittance_one(const DevModel &M, FsLds &L, FsGlob &G, Pcg32
     return exited;
 }
 
+// GaussianProcessMedium::sampleDistance over the function-space intersectGP, GPM.cpp:221-341 -> the segment record (wave-uniform).
+// `st` is read and rewritten in place; it may be a record of a batch (k_fs_march) or the workgroup's own slot (k_fs_scene).
+GPIS_DEV gpis_seg_out fs_sample_distance_one(const DevModel &M, FsLds &L, FsGlob &G, Pcg32 &s, const gpis_ray_in *ray, gpis_fs_state *st, FsState &state, int lane)
+{
+    gpis_seg_out o{};
+    const V3 pos = v3(ray->pos[0], ray->pos[1], ray->pos[2]), dir = v3(ray->dir[0], ray->dir[1], ray->dir[2]);
+    double startT = (double)ray->near_t;
+    float farT = ray->far_t;
+    if (!__builtin_isfinite(farT)) farT = (float)(startT + 2000);
+    const float maxT = farT;
+    o.gp_id = state.last_gp_id;
+    o.last_val = ray->last_val;
+    V3d aniso = state.last_aniso;
+    bool finished = false;
+    if (ray->bounce >= M.max_bounces) {
+        o.ok = 0;
+        finished = true;
+    } else if (maxT == 0.f) {
+        o.sample_t = maxT;
+        o.weight[0] = o.weight[1] = o.weight[2] = 1.f;
+        o.exited = 1;
+        const V3 pp = pos + dir * o.sample_t;
+        o.p[0] = pp.x; o.p[1] = pp.y; o.p[2] = pp.z;
+        o.scheme = GPIS_UNI;
+        o.ok = 1;
+        finished = true;
+    } else if (M.absorption_only) {
+        if (maxT == __builtin_huge_valf()) {
+            o.ok = 0;
+            finished = true;
+        } else {
+            o.sample_t = maxT;
+            const bool vis = fs_transmittance_one(M, L, G, s, ray, st, state, lane);
+            o.weight[0] = o.weight[1] = o.weight[2] = vis ? 1.f : 0.f;
+            o.exited = 1;
+            o.scheme = GPIS_UNI;
+            aniso = state.last_aniso;
+        }
+    } else {
+        double t = (double)maxT;
+        const V3d ro = to_d(pos);
+        V3d rd = to_d(dir);
+        { const double inv = 1.0 / length_d(rd); rd.x *= inv; rd.y *= inv; rd.z *= inv; }
+        bool exited, first = true;
+        do {
+            exited = !fs_intersect_gp(M, L, G, s, pos, dir, (float)startT, farT, state.first_scatter, first, st, state.last_gp_id, t, lane);
+            first = false;
+            if (t < (double)maxT) {
+                V3d grad;
+                if (!fs_sample_gradient(M, L, G, s, to_d(dir), ray_at(ro, rd, t), st, grad, lane)) {
+                    o.t = t; o.exited = exited; o.ok = 0; o.gp_id = state.last_gp_id;
+                    finished = true;
+                    break;
+                }
+                aniso = grad;
+                state.last_aniso = aniso;
+                state.first_scatter = false;
+                if (!__builtin_isfinite((aniso.x + aniso.y + aniso.z) / 3.0)) {
+                    aniso = V3d{1., 0., 0.};
+                    o.t = t; o.exited = exited; o.ok = 0; o.gp_id = state.last_gp_id;
+                    finished = true;
+                    break;
+                }
+            }
+            startT = t;
+        } while (t < (double)maxT && exited);
+        if (!finished) {
+            o.t = t;
+            o.exited = exited;
+            if (!exited) {
+                double d = aniso.x * (double)dir.x; d += aniso.y * (double)dir.y; d += aniso.z * (double)dir.z;
+                double l2 = 0.; l2 += aniso.x * aniso.x; l2 += aniso.y * aniso.y; l2 += aniso.z * aniso.z;
+                if (d > 0) {
+                    o.gp_id = state.last_gp_id; o.ok = 0;
+                    finished = true;
+                } else if (l2 < (double)0.0000001f) {
+                    aniso = V3d{1., 0., 0.};
+                    o.gp_id = state.last_gp_id; o.ok = 0;
+                    finished = true;
+                } else {
+                    const float col = M.color.enabled ? (float)ramp_eval(M.color, ray_at(ro, rd, t)) : 1.f;     // ramp noises (fs_check refuses a sandstone / rust colour here)
+                    o.weight[0] = o.weight[1] = o.weight[2] = col;
+                    o.continued_weight[0] = o.continued_weight[1] = o.continued_weight[2] = col;
+                }
+            } else {
+                V3d grad = aniso;
+                (void)fs_sample_gradient(M, L, G, s, to_d(dir), ray_at(ro, rd, t), st, grad, lane);   // GPM.cpp:319
+                aniso = grad;
+                o.weight[0] = o.weight[1] = o.weight[2] = 1.f;
+                o.continued_weight[0] = o.continued_weight[1] = o.continued_weight[2] = 1.f;
+            }
+            if (!finished) {
+                const float ft = (float)t;
+                o.sample_t = ft < maxT ? ft : maxT;
+                o.continued_t = (float)t;
+                for (int c = 0; c < 3; ++c) {
+                    o.weight[c] *= M.sigma_s_over_t[c];
+                    o.continued_weight[c] *= M.sigma_s_over_t[c];
+                }
+                o.scheme = GPIS_UNI;
+            }
+        }
+    }
+    if (!finished) {
+        const V3 pp = pos + dir * o.sample_t;
+        o.p[0] = pp.x; o.p[1] = pp.y; o.p[2] = pp.z;
+        o.gp_id = state.last_gp_id;
+        o.ok = 1;
+    }
+    o.aniso[0] = aniso.x; o.aniso[1] = aniso.y; o.aniso[2] = aniso.z;
+    return o;
+}
+
 template <bool WANT_SAMPLE>
 __global__ void __launch_bounds__(64) k_fs_march(const DevModel *__restrict__ Mp, size_t n_rays, const gpis_ray_in *__restrict__ rays,
                                                  gpis_fs_state *__restrict__ states, gpis_seg_out *__restrict__ outs, uint8_t *__restrict__ visible,
@@ -814,113 +927,7 @@ __global__ void __launch_bounds__(64) k_fs_march(const DevModel *__restrict__ Mp
             if (lane == 0) { visible[idx] = vis ? 1 : 0; st->sampler_state = s.state; }
             continue;
         }
-        // GaussianProcessMedium::sampleDistance, GPM.cpp:221-341
-        gpis_seg_out o{};
-        const V3 pos = v3(ray->pos[0], ray->pos[1], ray->pos[2]), dir = v3(ray->dir[0], ray->dir[1], ray->dir[2]);
-        double startT = (double)ray->near_t;
-        float farT = ray->far_t;
-        if (!__builtin_isfinite(farT)) farT = (float)(startT + 2000);
-        const float maxT = farT;
-        o.gp_id = state.last_gp_id;
-        o.last_val = ray->last_val;
-        V3d aniso = state.last_aniso;
-        bool finished = false;
-        if (ray->bounce >= M.max_bounces) {
-            o.ok = 0;
-            finished = true;
-        } else if (maxT == 0.f) {
-            o.sample_t = maxT;
-            o.weight[0] = o.weight[1] = o.weight[2] = 1.f;
-            o.exited = 1;
-            const V3 pp = pos + dir * o.sample_t;
-            o.p[0] = pp.x; o.p[1] = pp.y; o.p[2] = pp.z;
-            o.scheme = GPIS_UNI;
-            o.ok = 1;
-            finished = true;
-        } else if (M.absorption_only) {
-            if (maxT == __builtin_huge_valf()) {
-                o.ok = 0;
-                finished = true;
-            } else {
-                o.sample_t = maxT;
-                const bool vis = fs_transmittance_one(M, L, G, s, ray, st, state, lane);
-                o.weight[0] = o.weight[1] = o.weight[2] = vis ? 1.f : 0.f;
-                o.exited = 1;
-                o.scheme = GPIS_UNI;
-                aniso = state.last_aniso;
-            }
-        } else {
-            double t = (double)maxT;
-            const V3d ro = to_d(pos);
-            V3d rd = to_d(dir);
-            { const double inv = 1.0 / length_d(rd); rd.x *= inv; rd.y *= inv; rd.z *= inv; }
-            bool exited, first = true;
-            do {
-                exited = !fs_intersect_gp(M, L, G, s, pos, dir, (float)startT, farT, state.first_scatter, first, st, state.last_gp_id, t, lane);
-                first = false;
-                if (t < (double)maxT) {
-                    V3d grad;
-                    if (!fs_sample_gradient(M, L, G, s, to_d(dir), ray_at(ro, rd, t), st, grad, lane)) {
-                        o.t = t; o.exited = exited; o.ok = 0; o.gp_id = state.last_gp_id;
-                        finished = true;
-                        break;
-                    }
-                    aniso = grad;
-                    state.last_aniso = aniso;
-                    state.first_scatter = false;
-                    if (!__builtin_isfinite((aniso.x + aniso.y + aniso.z) / 3.0)) {
-                        aniso = V3d{1., 0., 0.};
-                        o.t = t; o.exited = exited; o.ok = 0; o.gp_id = state.last_gp_id;
-                        finished = true;
-                        break;
-                    }
-                }
-                startT = t;
-            } while (t < (double)maxT && exited);
-            if (!finished) {
-                o.t = t;
-                o.exited = exited;
-                if (!exited) {
-                    double d = aniso.x * (double)dir.x; d += aniso.y * (double)dir.y; d += aniso.z * (double)dir.z;
-                    double l2 = 0.; l2 += aniso.x * aniso.x; l2 += aniso.y * aniso.y; l2 += aniso.z * aniso.z;
-                    if (d > 0) {
-                        o.gp_id = state.last_gp_id; o.ok = 0;
-                        finished = true;
-                    } else if (l2 < (double)0.0000001f) {
-                        aniso = V3d{1., 0., 0.};
-                        o.gp_id = state.last_gp_id; o.ok = 0;
-                        finished = true;
-                    } else {
-                        const float col = M.color.enabled ? (float)ramp_eval(M.color, ray_at(ro, rd, t)) : 1.f;     // ramp noises (fs_check refuses a sandstone / rust colour here)
-                        o.weight[0] = o.weight[1] = o.weight[2] = col;
-                        o.continued_weight[0] = o.continued_weight[1] = o.continued_weight[2] = col;
-                    }
-                } else {
-                    V3d grad = aniso;
-                    (void)fs_sample_gradient(M, L, G, s, to_d(dir), ray_at(ro, rd, t), st, grad, lane);   // GPM.cpp:319
-                    aniso = grad;
-                    o.weight[0] = o.weight[1] = o.weight[2] = 1.f;
-                    o.continued_weight[0] = o.continued_weight[1] = o.continued_weight[2] = 1.f;
-                }
-                if (!finished) {
-                    const float ft = (float)t;
-                    o.sample_t = ft < maxT ? ft : maxT;
-                    o.continued_t = (float)t;
-                    for (int c = 0; c < 3; ++c) {
-                        o.weight[c] *= M.sigma_s_over_t[c];
-                        o.continued_weight[c] *= M.sigma_s_over_t[c];
-                    }
-                    o.scheme = GPIS_UNI;
-                }
-            }
-        }
-        if (!finished) {
-            const V3 pp = pos + dir * o.sample_t;
-            o.p[0] = pp.x; o.p[1] = pp.y; o.p[2] = pp.z;
-            o.gp_id = state.last_gp_id;
-            o.ok = 1;
-        }
-        o.aniso[0] = aniso.x; o.aniso[1] = aniso.y; o.aniso[2] = aniso.z;
+        const gpis_seg_out o = fs_sample_distance_one(M, L, G, s, ray, st, state, lane);
         if (lane == 0) { outs[idx] = o; st->sampler_state = s.state; }
         FS_T(10);
     }

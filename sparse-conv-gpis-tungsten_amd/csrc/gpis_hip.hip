@@ -90,6 +90,10 @@ struct gpis_medium {
     unsigned lambert_calls = 0;       // gpis_render_scene_s calls so far (the first one works in small chunks, see lambert_ws_plan)
     void *fs_ws = nullptr;            // function-space workspace: one FsGlob per resident workgroup (gpis_fs.hpp)
     unsigned fs_ws_blocks = 0;
+    gpis_fs_state *fs_slots = nullptr;   // ... followed by one gpis_fs_state per resident workgroup: the frame driver's states (gpis_fs_scene.hpp)
+    void *fs_scene_recs = nullptr;    // gpis_fs_render_scene_s: one record per sample of a chunk, and the chunk's work counter
+    size_t fs_scene_rec_bytes = 0;
+    uint32_t *fs_scene_next = nullptr;
     // staging for the *_host entries and workspace for the renderer (grown on demand)
     // slots 0-2: *_host staging; 3: renderer workspace (Lambert driver: primary rays + jitters + mask); 4: wavefront march;
     // 5, 6: the Lambert driver's segment results and its shadow-ray arrays — separate allocations, so that each can be made while
@@ -1150,6 +1154,8 @@ extern "C" int gpis_destroy(gpis_medium *m)
     if (m->d_guide_cnt) (void)hipFree(m->d_guide_cnt);
     if (m->d_guide) (void)hipFree(m->d_guide);
     if (m->fs_ws) (void)hipFree(m->fs_ws);
+    if (m->fs_scene_recs) (void)hipFree(m->fs_scene_recs);
+    if (m->fs_scene_next) (void)hipFree(m->fs_scene_next);
     if (m->d_grid_vox) (void)hipFree(m->d_grid_vox);
     for (int k = 0; k < 3; ++k)
         if (m->fs_stage[k]) (void)hipFree(m->fs_stage[k]);
@@ -1545,15 +1551,27 @@ static int fs_check(gpis_medium *m)
     return GPIS_OK;
 }
 // 37 KB of LDS per workgroup: four one-wave workgroups (one per SIMD) are resident per CU and walk the batch; each owns one
-// slice of the L2-resident workspace
-static int fs_workspace(gpis_medium *m, unsigned &cap)
+// slice of the L2-resident workspace and, behind the slices, one state slot (the frame driver's; 2.4 KB each).  scene_rec_bytes:
+// the frame driver's record array and work counter, grown here under the same lock.
+static int fs_workspace(gpis_medium *m, unsigned &cap, size_t scene_rec_bytes = 0)
 {
     cap = (unsigned)(m->n_cus > 0 ? m->n_cus : 256) * 4u;
     std::lock_guard<std::mutex> lock(m->mu);
     if (m->fs_ws_blocks < cap) {
-        if (m->fs_ws) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(m->fs_ws); m->fs_ws = nullptr; m->fs_ws_blocks = 0; }
-        if (hipMalloc(&m->fs_ws, (size_t)cap * launch::fs_workspace_bytes_per_block()) != hipSuccess) { (void)hipGetLastError(); return set_err(GPIS_ERR_DEVICE, "function-space workspace allocation failed"); }
+        if (m->fs_ws) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(m->fs_ws); m->fs_ws = nullptr; m->fs_slots = nullptr; m->fs_ws_blocks = 0; }
+        const size_t slices = (size_t)cap * launch::fs_workspace_bytes_per_block();
+        if (hipMalloc(&m->fs_ws, slices + (size_t)cap * sizeof(gpis_fs_state)) != hipSuccess) { (void)hipGetLastError(); return set_err(GPIS_ERR_DEVICE, "function-space workspace allocation failed"); }
+        m->fs_slots = (gpis_fs_state *)((char *)m->fs_ws + slices);
         m->fs_ws_blocks = cap;
+    }
+    if (scene_rec_bytes && !m->fs_scene_next && hipMalloc(&m->fs_scene_next, sizeof(uint32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(GPIS_ERR_DEVICE, "function-space frame counter allocation failed");
+    }
+    if (m->fs_scene_rec_bytes < scene_rec_bytes) {
+        if (m->fs_scene_recs) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(m->fs_scene_recs); m->fs_scene_recs = nullptr; m->fs_scene_rec_bytes = 0; }
+        if (hipMalloc(&m->fs_scene_recs, scene_rec_bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(GPIS_ERR_DEVICE, "function-space frame records: no memory for %zu bytes", scene_rec_bytes); }
+        m->fs_scene_rec_bytes = scene_rec_bytes;
     }
     return GPIS_OK;
 }
@@ -2194,6 +2212,39 @@ extern "C" int gpis_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float 
         if ((rc = launch_check("k_scene_accumulate"))) return rc;
     }
     return ws_release(m, 0, st);
+}
+
+// Scene S through the function-space medium (gpis_fs_scene.hpp): per chunk of samples one fused launch over the resident set of
+// the function-space workspace and the per-pixel sum of its records.  Samples per chunk: GPIS_OPT_CHUNK_LOG2, else 2^22 as the
+// weight-space frame driver's (8 B of records per sample: 32 MB).
+extern "C" int gpis_fs_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radiance_sum, uint32_t *hit_count, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && radiance_sum);
+    CHECK_ARGS(scene_args_ok(s));
+    if (int rc = fs_check(m)) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = (hipStream_t)stream;
+    const SceneConst sc = make_scene_const(s);
+    const size_t total_pixels = scene_rows(*s) * s->width;
+    if (total_pixels == 0) return GPIS_OK;
+    size_t chunk_pixels = ((size_t)1 << chunk_log2(m, 22)) / s->spp_count;
+    if (chunk_pixels < 1) chunk_pixels = 1;
+    if (chunk_pixels > total_pixels) chunk_pixels = total_pixels;
+    const size_t ns_max = chunk_pixels * s->spp_count;
+    unsigned cap = 0;
+    if (int rc = fs_workspace(m, cap, ns_max * launch::fs_scene_rec_bytes())) return rc;
+    // the work counter runs to at most n_samples + grid
+    if (ns_max + cap >= ((size_t)1 << 32)) return set_err(GPIS_ERR_UNSUPPORTED, "gpis_fs_render_scene_s: spp_count %u", s->spp_count);
+    for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
+        const size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
+        const size_t ns = np * s->spp_count;
+        HIP_TRY(hipMemsetAsync(m->fs_scene_next, 0, sizeof(uint32_t), st));
+        launch::fs_scene((unsigned)(ns < cap ? ns : cap), m->d_model, sc, p0, (uint32_t)ns, m->fs_scene_next, m->fs_scene_recs, m->fs_ws, m->fs_slots, st);
+        if (int rc = launch_check("k_fs_scene")) return rc;
+        launch::fs_scene_sum(sc, p0, np, m->fs_scene_recs, radiance_sum, hit_count, st);
+        if (int rc = launch_check("k_fs_scene_sum")) return rc;
+    }
+    return GPIS_OK;
 }
 
 extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo, float *radiance_sum, void *stream)

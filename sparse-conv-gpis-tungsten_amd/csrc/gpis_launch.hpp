@@ -16,6 +16,7 @@ struct Counters;
 struct FastTable;
 struct GuideField;
 struct PersistArgs;
+struct SceneConst;
 
 // radix sort of (key, value) pairs (gpis_sort.hip); two-call convention: temp == nullptr only reports the scratch size
 hipError_t sort_pairs_u32(void *temp, size_t &temp_bytes, const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
@@ -92,6 +93,11 @@ void fs_march(bool want_sample, unsigned grid, const DevModel *d_model, size_t n
 int fs_prof_read(unsigned long long *out16, int reset);         // GPIS_FS_PROF builds only
 void libm_eval(int fn, size_t n, const double *x, const double *y, double *out, double *out2, hipStream_t s);   // test surface (tu_libm.hip)
 void fs_linalg(unsigned grid, int op, int n, size_t count, const double *in, double *out, double *evals, void *workspace, hipStream_t s);   // test surface
+// ---- scene-S frame of the function-space medium (tu_fs_scene.hip): grid <= the workspace's blocks; slots: one gpis_fs_state per block
+size_t fs_scene_rec_bytes();
+void fs_scene(unsigned grid, const DevModel *d_model, const SceneConst &sc, size_t first_pixel, uint32_t n_samples, uint32_t *next, void *recs,
+              void *workspace, gpis_fs_state *slots, hipStream_t s);
+void fs_scene_sum(const SceneConst &sc, size_t first_pixel, size_t n_pixels, const void *recs, float *radiance_sum, uint32_t *hit_count, hipStream_t s);
 inline unsigned grid_of(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 }   // namespace launch

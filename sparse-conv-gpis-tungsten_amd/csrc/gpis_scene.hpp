@@ -1,5 +1,5 @@
 // gpis_scene.hpp — what the scene-S frame drivers of every medium share (gpis_hip.hip: the sparse-convolution drivers;
-// tu_ws_scene.hip: the weight-space driver): the host-precomputed camera constants, the pixel order of a call, the argument
+// tu_ws_scene.hip: the weight-space driver; gpis_fs_scene.hpp: the function-space driver): the host-precomputed camera constants, the pixel order of a call, the argument
 // check and the bounding-sphere chord.  One definition, so that the drivers cannot drift apart in a single bit.
 #pragma once
 #include <cmath>
