@@ -406,7 +406,7 @@ int gpis_mean_color_emission_host(gpis_medium *m, size_t n, const double *p3, fl
  * FunctionSpaceGaussianProcessMedium::intersectGP / sampleGradient).  rays[i].u_jitter is not used (every variate comes from
  * states[i].sampler_state); states are read and written in place (device pointers).  The two entries share one device
  * workspace per handle: launches of the SAME handle must be ordered (one stream, or an event between them).  The frame of this
- * medium: gpis_fs_render_scene_s, at the end of this header. */
+ * medium: gpis_fs_render_scene_s and gpis_fs_render_scene_s_paths, at the end of this header. */
 int gpis_fs_sample_distance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_fs_state *states, gpis_seg_out *out, void *stream);
 int gpis_fs_transmittance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_fs_state *states, uint8_t *visible, void *stream);
 /* The same two entries for host pointers (synchronous; what the Medium binding of the function-space medium calls with a batch
@@ -751,6 +751,38 @@ int gpis_ws_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_
  * handle's function-space workspace with the gpis_fs_* batch entries: launches of the SAME handle must be ordered (one stream, or
  * an event between them). */
 int gpis_fs_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radiance_sum, uint32_t *hit_count, void *stream);
+/* gpis_render_scene_s_paths over the function-space medium: the estimator of gpis_ws_render_scene_s_paths (above), operation for
+ * operation, with this medium's sampler and state as in gpis_fs_render_scene_s.  Rows, tile-row shard and spp range as the other
+ * frame entries.  Per sample (x, y, k): ONE PCG32 stream, set_state(xxhash32(x, y, k, scene_seed) + 1); its first two draws are
+ * jx, jy, and every later draw belongs to the medium or to the bounce, in program order (no u_march / u_shadow is drawn; u_jitter
+ * is not read).  Camera ray and bounding-sphere chord as gpis_fs_render_scene_s; a miss contributes nothing and marches nothing.
+ * The path state starts empty (has_context = 0) with the stream after jx, jy as its sampler.  For bounce b = 0 ..
+ * max_path_bounces-1: a sampleDistance on the path state with segment word b (!ok ends the path; throughput *= weight[0]; exited
+ * ends the path).  On a hit, while b < max_path_bounces-1: next-event estimation when wi.z > 0, wo.z > 0 (Duff frame about the
+ * normalised aniso) and (p, l) has a chord — one shadow transmittance (near 0, far t1, segment b+1, first_scatter = 0, bounce + 1,
+ * last_aniso / last_gp_id / last_val / info_t + sample_t carried from the result) on a COPY of the path's state: gpis_fs_state is
+ * a value, and the shadow segment never alters the path's context.  The sampler is not copied: the shadow segment draws from the
+ * path's stream where the path segment stopped, and the path goes on from where the shadow segment stopped.  Contribution
+ * throughput * (((albedo * (1/3.1415926536f)) * wo.z) * light_radiance) when visible.  Then, if wi.z <= 0 the path ends; otherwise
+ * the cosine bounce by unit-disk rejection (sqrt only) from the same stream, throughput *= albedo, and — if (p, w) has a chord —
+ * segment b+1 on the path's own context: the one the path segment of bounce b left, so Renewal, Renewal+ and Global condition it
+ * on that segment's values and not on the shadow segment's.  The segment of bounce max_path_bounces-1 is marched and counted;
+ * nothing after it is observable and the driver stops there, so max_path_bounces = 1 adds zeros.
+ * A sample's emission is the sum of its contributions in bounce order.  ACCUMULATES each pixel's sum of emissions, taken in sample
+ * order from zero and added once per call, into radiance_sum[height*width] (float, device pointer, indexed y*width+x), and per
+ * pixel the segments marched, path segments plus shadow segments, into seg_count (device pointer, may be NULL).  The image
+ * depends neither on how a frame is cut into calls and chunks nor on the order in which workgroups finish; nothing is added
+ * atomically into the image.
+ * One fused kernel, one wave per sample in flight, the whole path in the workgroup, work taken from a global counter: no ray,
+ * segment or state record per sample in device memory (two state slots per resident workgroup — the path's and the shadow
+ * segment's copy — and 8 B of records per sample of a chunk; GPIS_OPT_CHUNK_LOG2 sets the chunk, 0 = 2^22 samples).
+ * max_path_bounces >= 1, else GPIS_ERR_INVALID_ARG; albedo is taken as given.  Handles as gpis_fs_render_scene_s: anything it
+ * refuses, a weight-space handle included, is GPIS_ERR_INVALID_ARG here (gpis_render_scene_s_paths and
+ * gpis_ws_render_scene_s_paths keep their own refusals).  The entry shares the handle's function-space workspace with
+ * gpis_fs_render_scene_s and the gpis_fs_* batch entries: launches of the SAME handle must be ordered (one stream, or an event
+ * between them). */
+int gpis_fs_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo,
+                                 float *radiance_sum, uint32_t *seg_count, void *stream);
 
 #ifdef __cplusplus
 }

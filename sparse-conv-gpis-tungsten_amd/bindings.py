@@ -335,7 +335,7 @@ class GpisLib:
         "gpis_ws_default_params", "gpis_ws_create", "gpis_ws_sample_distance_batch", "gpis_ws_transmittance_batch",
         "gpis_ws_sample_distance_host", "gpis_ws_transmittance_host", "gpis_ws_eval_batch", "gpis_ws_basis_batch",
         "gpis_ws_get_counters", "gpis_ws_reset_counters", "gpis_ws_render_scene_s", "gpis_ws_render_scene_s_paths",
-        "gpis_fs_render_scene_s",
+        "gpis_fs_render_scene_s", "gpis_fs_render_scene_s_paths",
     ]
 
     def __init__(self, path=None):
@@ -408,6 +408,7 @@ class GpisLib:
         L.gpis_render_scene_s.argtypes = [vp, vp, vp, vp, vp]
         L.gpis_ws_render_scene_s.argtypes = [vp, vp, vp, vp, vp]
         L.gpis_fs_render_scene_s.argtypes = [vp, vp, vp, vp, vp]
+        L.gpis_fs_render_scene_s_paths.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp, vp]
         L.gpis_ws_render_scene_s_paths.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
         L.gpis_render_scene_s_paths.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
         L.gpis_render_scene_s_nee.argtypes = [vp, vp, vp, vp, vp]
@@ -590,6 +591,25 @@ class Medium:
         if not want_hits:
             return rad
         return rad, d_hit.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
+
+    def fs_render_scene_s_paths(self, scene, max_bounces, albedo, want_segs=False):
+        """One call of the function-space multi-bounce path driver (gpis_fs_render_scene_s_paths) into zeroed device buffers: the
+        float32 sum-of-radiance image (height, width) of the rows, shard and samples `scene` selects, and per pixel the segments
+        marched (path plus shadow) when asked."""
+        import torch
+        scene = np.array(scene, dtype=SCENE_S).reshape(())
+        hgt, wid = int(scene["height"]), int(scene["width"])
+        dev = torch.device("cuda", self.device)
+        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
+        d_seg = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_segs else None
+        torch.cuda.synchronize(dev)
+        self.L.check(self.L.lib.gpis_fs_render_scene_s_paths(self.h, _ptr(scene), int(max_bounces), ctypes.c_float(albedo), ctypes.c_void_p(d_rad.data_ptr()),
+                                                             ctypes.c_void_p(d_seg.data_ptr()) if want_segs else None, None), "gpis_fs_render_scene_s_paths")
+        torch.cuda.synchronize(dev)
+        rad = d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy()
+        if not want_segs:
+            return rad
+        return rad, d_seg.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
 
     def mean_color_emission(self, points):
         """(color, emission) of the mean at double-precision points (n, 3)"""

@@ -12,7 +12,8 @@
 //       of it for the shadow segment.  Here the state lives in ONE slot per resident workgroup, next to its FsGlob: the primary
 //       segment starts it empty (has_context = 0), and the shadow segment continues in place from what the primary left —
 //       context (points, derivs, values, sampled_grad, is_intersect) and sampler.  Nothing follows the shadow segment in this
-//       estimator, so running in place equals running on a copy;
+//       estimator, so running in place equals running on a copy (where the path goes on after it, the copy is real: k_fs_paths,
+//       gpis_fs_paths.hpp, keeps a second slot per workgroup for it);
 //   dynamic work fetch — a sample costs nothing (a miss of the bounding sphere) up to tens of eigen-solves (a grazing chord
 //       with fs_step_size > 0 and its shadow segment); workgroups take the next sample index from a global counter (one atomic
 //       per workgroup per sample) instead of k_fs_march's static stride.

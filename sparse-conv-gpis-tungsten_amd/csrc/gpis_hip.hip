@@ -90,7 +90,8 @@ struct gpis_medium {
     unsigned lambert_calls = 0;       // gpis_render_scene_s calls so far (the first one works in small chunks, see lambert_ws_plan)
     void *fs_ws = nullptr;            // function-space workspace: one FsGlob per resident workgroup (gpis_fs.hpp)
     unsigned fs_ws_blocks = 0;
-    gpis_fs_state *fs_slots = nullptr;   // ... followed by one gpis_fs_state per resident workgroup: the frame driver's states (gpis_fs_scene.hpp)
+    gpis_fs_state *fs_slots = nullptr;   // ... followed by two banks of fs_ws_blocks states: the frame drivers' path states (gpis_fs_scene.hpp),
+                                         // then the path driver's shadow copies (gpis_fs_paths.hpp)
     void *fs_scene_recs = nullptr;    // gpis_fs_render_scene_s: one record per sample of a chunk, and the chunk's work counter
     size_t fs_scene_rec_bytes = 0;
     uint32_t *fs_scene_next = nullptr;
@@ -1551,8 +1552,9 @@ static int fs_check(gpis_medium *m)
     return GPIS_OK;
 }
 // 37 KB of LDS per workgroup: four one-wave workgroups (one per SIMD) are resident per CU and walk the batch; each owns one
-// slice of the L2-resident workspace and, behind the slices, one state slot (the frame driver's; 2.4 KB each).  scene_rec_bytes:
-// the frame driver's record array and work counter, grown here under the same lock.
+// slice of the L2-resident workspace and, behind the slices, two state slots (2.4 KB each): bank 0 holds the frame drivers' path
+// states, bank 1 the path driver's shadow copies (k_fs_scene uses bank 0 alone).  scene_rec_bytes: the frame drivers' record array
+// and work counter, grown here under the same lock.
 static int fs_workspace(gpis_medium *m, unsigned &cap, size_t scene_rec_bytes = 0)
 {
     cap = (unsigned)(m->n_cus > 0 ? m->n_cus : 256) * 4u;
@@ -1560,7 +1562,7 @@ static int fs_workspace(gpis_medium *m, unsigned &cap, size_t scene_rec_bytes = 
     if (m->fs_ws_blocks < cap) {
         if (m->fs_ws) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(m->fs_ws); m->fs_ws = nullptr; m->fs_slots = nullptr; m->fs_ws_blocks = 0; }
         const size_t slices = (size_t)cap * launch::fs_workspace_bytes_per_block();
-        if (hipMalloc(&m->fs_ws, slices + (size_t)cap * sizeof(gpis_fs_state)) != hipSuccess) { (void)hipGetLastError(); return set_err(GPIS_ERR_DEVICE, "function-space workspace allocation failed"); }
+        if (hipMalloc(&m->fs_ws, slices + 2 * (size_t)cap * sizeof(gpis_fs_state)) != hipSuccess) { (void)hipGetLastError(); return set_err(GPIS_ERR_DEVICE, "function-space workspace allocation failed"); }
         m->fs_slots = (gpis_fs_state *)((char *)m->fs_ws + slices);
         m->fs_ws_blocks = cap;
     }
@@ -2243,6 +2245,40 @@ extern "C" int gpis_fs_render_scene_s(gpis_medium *m, const gpis_scene_s *s, flo
         if (int rc = launch_check("k_fs_scene")) return rc;
         launch::fs_scene_sum(sc, p0, np, m->fs_scene_recs, radiance_sum, hit_count, st);
         if (int rc = launch_check("k_fs_scene_sum")) return rc;
+    }
+    return GPIS_OK;
+}
+
+// Multi-bounce paths on scene S through the function-space medium (gpis_fs_paths.hpp): the host loop of gpis_fs_render_scene_s,
+// with the second bank of state slots for the shadow segments' copies.
+extern "C" int gpis_fs_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo, float *radiance_sum,
+                                            uint32_t *seg_count, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && radiance_sum && max_path_bounces >= 1);
+    CHECK_ARGS(scene_args_ok(s));
+    if (int rc = fs_check(m)) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = (hipStream_t)stream;
+    const SceneConst sc = make_scene_const(s);
+    const size_t total_pixels = scene_rows(*s) * s->width;
+    if (total_pixels == 0) return GPIS_OK;
+    size_t chunk_pixels = ((size_t)1 << chunk_log2(m, 22)) / s->spp_count;
+    if (chunk_pixels < 1) chunk_pixels = 1;
+    if (chunk_pixels > total_pixels) chunk_pixels = total_pixels;
+    const size_t ns_max = chunk_pixels * s->spp_count;
+    unsigned cap = 0;
+    if (int rc = fs_workspace(m, cap, ns_max * launch::fs_paths_rec_bytes())) return rc;
+    // the work counter runs to at most n_samples + grid
+    if (ns_max + cap >= ((size_t)1 << 32)) return set_err(GPIS_ERR_UNSUPPORTED, "gpis_fs_render_scene_s_paths: spp_count %u", s->spp_count);
+    for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
+        const size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
+        const size_t ns = np * s->spp_count;
+        HIP_TRY(hipMemsetAsync(m->fs_scene_next, 0, sizeof(uint32_t), st));
+        launch::fs_paths((unsigned)(ns < cap ? ns : cap), m->d_model, sc, p0, (uint32_t)ns, max_path_bounces, albedo, m->fs_scene_next, m->fs_scene_recs, m->fs_ws,
+                         m->fs_slots, m->fs_slots + m->fs_ws_blocks, st);
+        if (int rc = launch_check("k_fs_paths")) return rc;
+        launch::fs_paths_sum(sc, p0, np, m->fs_scene_recs, radiance_sum, seg_count, st);
+        if (int rc = launch_check("k_fs_paths_sum")) return rc;
     }
     return GPIS_OK;
 }
