@@ -759,6 +759,28 @@ GPIS_DEV bool fs_sample_gradient(const DevModel &M, FsLds &L, FsGlob &G, Pcg32 &
 
 struct FsState { bool first_scatter; int last_gp_id; V3d last_aniso; };
 
+// the march state a segment starts from: what its ray carries over from the segment before it
+GPIS_DEV FsState fs_state_of(const gpis_ray_in &ray)
+{
+    FsState state;
+    state.first_scatter = ray.first_scatter != 0;
+    state.last_gp_id = ray.last_gp_id;
+    state.last_aniso = V3d{ray.last_aniso[0], ray.last_aniso[1], ray.last_aniso[2]};
+    return state;
+}
+
+// The empty state of a path's first segment, written over whatever context the slot still holds.  Every lane calls this (the
+// first FS_SYNC is a barrier); the caller's next FS_SYNC makes the reset visible to the wave.
+GPIS_DEV void fs_reset_state(gpis_fs_state *st, int lane)
+{
+    FS_SYNC();
+    if (lane == 0) {
+        st->has_context = 0; st->is_intersect = 0; st->n_points = 0; st->n_values = 0;
+        st->sampled_grad[0] = 0.; st->sampled_grad[1] = 0.; st->sampled_grad[2] = 0.;
+    }
+    __threadfence_block();
+}
+
 // GaussianProcessMedium::transmittance over the function-space intersectGP, GPM.cpp:343-393 -> exited (false = blocked or failed)
 GPIS_DEV bool fs_transmittance_one(const DevModel &M, FsLds &L, FsGlob &G, Pcg32 &s, const gpis_ray_in *ray, gpis_fs_state *st, FsState &state, int lane)
 {
@@ -916,10 +938,7 @@ __global__ void __launch_bounds__(64) k_fs_march(const DevModel *__restrict__ Mp
         gpis_fs_state *st = states + idx;
         Pcg32 s;
         s.state = st->sampler_state;
-        FsState state;
-        state.first_scatter = ray->first_scatter != 0;
-        state.last_gp_id = ray->last_gp_id;
-        state.last_aniso = V3d{ray->last_aniso[0], ray->last_aniso[1], ray->last_aniso[2]};
+        FsState state = fs_state_of(*ray);
         FS_SYNC();
         FS_T0();
         if (!WANT_SAMPLE) {

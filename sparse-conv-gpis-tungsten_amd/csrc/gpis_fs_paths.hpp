@@ -22,17 +22,20 @@
 // Wave-uniform control flow.  A workgroup is one wave and FS_SYNC is a barrier, so every branch around one must be taken by all
 // 64 lanes alike.  Every value that steers control flow is computed by every lane from the same inputs: the sample index is
 // broadcast from lane 0 (readfirstlane); x, y, spp, the Pcg32, the ray, the FsState, throughput and emission derive from it and
-// from kernel arguments; fs_sample_distance_one and fs_transmittance_one return wave-uniform results (gpis_fs.hpp).  The loop
-// exits:
+// from kernel arguments; fs_sample_distance_one and fs_transmittance_one return wave-uniform results (gpis_fs.hpp).  The
+// sample's pixel and stream and the hit normal are gpis_scene.hpp's helpers (scene_sample, hit_normal): they hold no barrier and
+// no branch on the lane and read only their arguments, so on uniform arguments their results are uniform.  Of the medium's own
+// helpers, fs_state_of is arithmetic on the ray; fs_reset_state holds an FS_SYNC and a lane-0 store, and is called by all 64
+// lanes from a uniform branch.  The loop exits:
 //   the fetch loop ends when i >= n_samples — i is the broadcast value;
 //   the bounce loop ends on its trip count (a kernel argument), on !r.ok / r.exited (fields of the uniform segment record), on
 //       !(wi.z > 0) (float arithmetic on the uniform ray and record) and on a missing chord (sphere_chord on uniform p, w);
 //   the rejection loop ends when d2 < 1 — dx, dy are draws of the uniform Pcg32, so its trip count is the same in every lane;
 //   the copy loop runs w = lane, lane + 64, ... < 303: a per-lane trip count, but it holds no barrier; the FS_SYNCs sit outside.
 //
-// The shading arithmetic (Duff frame, wi / wo, disk rejection, next-ray fill) restates k_ws_paths's, and with it
-// k_paths_shade's, line for line rather than sharing a function with them: those kernels are left as they are, and the tests pin
-// all of them against the same C (tests/native/ws_paths_shade.c, tests/native/fs_paths_shade.c).
+// The camera ray and the shade step (Duff frame, wi / wo, next-event estimation, disk rejection, next-ray fill) are stated here
+// in full, the shade step as in k_ws_paths and k_paths_shade: as functions around the marches they made this kernel slower
+// (gpis_scene.hpp).  The tests pin all three against the same C (tests/native/ws_paths_shade.c, tests/native/fs_paths_shade.c).
 #pragma once
 #include "gpis_fs.hpp"
 #include "gpis_scene.hpp"
@@ -68,11 +71,8 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_paths(const DevModel *
         i = __builtin_amdgcn_readfirstlane(i);
         if (i >= n_samples) break;
         // ---- the camera step of k_fs_scene: the path's sampler gives jx, jy and is then the medium's and the bounce's
-        const size_t pix = scene_pixel(s, first_pixel + i / s.spp_count);
-        const uint32_t x = (uint32_t)(pix % s.width), y = (uint32_t)(pix / s.width);
-        const uint32_t spp = s.spp_begin + i % s.spp_count;
-        Pcg32 g;
-        g.set_state((uint64_t)(uint32_t)(xxhash32_4(x, y, spp, s.scene_seed) + 1u));
+        uint32_t x, y, spp;
+        Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
         const float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
         const V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
         const V3 d0 = v3(local.x, local.y, -local.z);
@@ -87,19 +87,10 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_paths(const DevModel *
             ray.pixel[0] = x; ray.pixel[1] = y; ray.spp = spp; ray.segment = 0;
             ray.scene_seed = s.scene_seed; ray.info_t = 0.f;
             ray.first_scatter = 1;
-            // the empty state of a path's first segment; the slot still holds the previous sample's context
-            FS_SYNC();
-            if (lane == 0) {
-                st->has_context = 0; st->is_intersect = 0; st->n_points = 0; st->n_values = 0;
-                st->sampled_grad[0] = 0.; st->sampled_grad[1] = 0.; st->sampled_grad[2] = 0.;
-            }
-            __threadfence_block();
+            fs_reset_state(st, lane);            // the slot still holds the previous sample's context
             float thr = 1.f;
             for (int bounce = 0; bounce < max_bounces; ++bounce) {
-                FsState state;
-                state.first_scatter = ray.first_scatter != 0;
-                state.last_gp_id = ray.last_gp_id;
-                state.last_aniso = V3d{ray.last_aniso[0], ray.last_aniso[1], ray.last_aniso[2]};
+                FsState state = fs_state_of(ray);
                 rec.segs++;
                 FS_SYNC();
                 const gpis_seg_out r = fs_sample_distance_one(M, L, G, g, &ray, st, state, lane);
@@ -108,9 +99,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_paths(const DevModel *
                 thr = thr * r.weight[0];
                 if (r.exited) break;
                 if (bounce + 1 >= max_bounces) break;        // no NEE at the last bounce, and the bounce itself cannot be seen
-                const double ax = r.aniso[0], ay = r.aniso[1], az = r.aniso[2];
-                const double len = sqrt(ax * ax + ay * ay + az * az);
-                const V3 n = v3((float)(ax / len), (float)(ay / len), (float)(az / len));
+                const V3 n = hit_normal(r);
                 const Frame fr = frame_from_normal(n);
                 const V3 dir = v3(ray.dir[0], ray.dir[1], ray.dir[2]);
                 const V3 wi = normalized(to_local(fr, v3(-dir.x, -dir.y, -dir.z)));
@@ -146,10 +135,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_paths(const DevModel *
                                     __builtin_memcpy(dst + 8 * w, src + 8 * w, 8);       // an 8-byte load and store: no lvalue of another type
                             }
                             __threadfence_block();
-                            FsState shadow;
-                            shadow.first_scatter = sh.first_scatter != 0;
-                            shadow.last_gp_id = sh.last_gp_id;
-                            shadow.last_aniso = V3d{sh.last_aniso[0], sh.last_aniso[1], sh.last_aniso[2]};
+                            FsState shadow = fs_state_of(sh);
                             rec.segs++;
                             FS_SYNC();
                             const bool vis = fs_transmittance_one(M, L, G, g, &sh, st_shadow, shadow, lane);

@@ -50,65 +50,27 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_scene(const DevModel *
         i = __builtin_amdgcn_readfirstlane(i);
         if (i >= n_samples) break;
         // ---- k_scene_primary, with the path's sampler in place of the four per-sample draws
-        const size_t pix = scene_pixel(s, first_pixel + i / s.spp_count);
-        const uint32_t x = (uint32_t)(pix % s.width), y = (uint32_t)(pix / s.width);
-        const uint32_t spp = s.spp_begin + i % s.spp_count;
-        Pcg32 g;
-        g.set_state((uint64_t)(uint32_t)(xxhash32_4(x, y, spp, s.scene_seed) + 1u));
+        uint32_t x, y, spp;
+        Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
         const float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
-        const V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
-        const V3 d = v3(local.x, local.y, -local.z);
-        const V3 o = v3(s.cam_pos[0], s.cam_pos[1], s.cam_pos[2]);
         FsSceneRec rec{0.f, 0u};
-        float t0 = 0.f, t1 = 0.f;
-        if (sphere_chord(o, d, s.bound_radius, t0, t1)) {
-            gpis_ray_in ray{};
-            ray.pos[0] = o.x; ray.pos[1] = o.y; ray.pos[2] = o.z;
-            ray.dir[0] = d.x; ray.dir[1] = d.y; ray.dir[2] = d.z;
-            ray.near_t = t0; ray.far_t = t1;
-            ray.pixel[0] = x; ray.pixel[1] = y; ray.spp = spp; ray.segment = 0;
-            ray.scene_seed = s.scene_seed; ray.info_t = 0.f;
-            ray.first_scatter = 1;
-            // the empty state of a path's first segment; the slot still holds the previous sample's context
-            FS_SYNC();
-            if (lane == 0) {
-                st->has_context = 0; st->is_intersect = 0; st->n_points = 0; st->n_values = 0;
-                st->sampled_grad[0] = 0.; st->sampled_grad[1] = 0.; st->sampled_grad[2] = 0.;
-            }
-            __threadfence_block();
-            FsState state;
-            state.first_scatter = ray.first_scatter != 0;
-            state.last_gp_id = ray.last_gp_id;
-            state.last_aniso = V3d{ray.last_aniso[0], ray.last_aniso[1], ray.last_aniso[2]};
+        gpis_ray_in ray;
+        if (scene_camera_ray(sc, x, y, spp, jx, jy, ray)) {
+            fs_reset_state(st, lane);            // the slot still holds the previous sample's context
+            FsState state = fs_state_of(ray);
             FS_SYNC();
             const gpis_seg_out r = fs_sample_distance_one(M, L, G, g, &ray, st, state, lane);
             // ---- k_scene_shade
             if (r.ok && !r.exited) {
                 rec.flags = 1u;
-                const double ax = r.aniso[0], ay = r.aniso[1], az = r.aniso[2];
-                const double len = sqrt(ax * ax + ay * ay + az * az);
-                const V3 nn = v3((float)(ax / len), (float)(ay / len), (float)(az / len));
-                const float c = dot(nn, l);
+                const float c = dot(hit_normal(r), l);
                 float s0, s1;
                 if (c > 0.f && sphere_chord(v3(r.p[0], r.p[1], r.p[2]), l, s.bound_radius, s0, s1)) {
-                    gpis_ray_in sh{};
-                    sh.pos[0] = r.p[0]; sh.pos[1] = r.p[1]; sh.pos[2] = r.p[2];
+                    gpis_ray_in sh = scene_next_ray(ray, r);
                     sh.dir[0] = l.x; sh.dir[1] = l.y; sh.dir[2] = l.z;
-                    sh.near_t = 0.f; sh.far_t = s1;
-                    sh.pixel[0] = x; sh.pixel[1] = y; sh.spp = spp;
-                    sh.segment = ray.segment + 1;
-                    sh.scene_seed = ray.scene_seed;
-                    sh.info_t = ray.info_t + r.sample_t;
-                    sh.first_scatter = 0;
-                    sh.bounce = ray.bounce + 1;
-                    sh.last_val = r.last_val;
-                    sh.last_gp_id = r.gp_id;
-                    sh.last_aniso[0] = r.aniso[0]; sh.last_aniso[1] = r.aniso[1]; sh.last_aniso[2] = r.aniso[2];
+                    sh.far_t = s1;
                     // the shadow segment: in place on the state (context and sampler) the primary segment left
-                    FsState shadow;
-                    shadow.first_scatter = sh.first_scatter != 0;
-                    shadow.last_gp_id = sh.last_gp_id;
-                    shadow.last_aniso = V3d{sh.last_aniso[0], sh.last_aniso[1], sh.last_aniso[2]};
+                    FsState shadow = fs_state_of(sh);
                     FS_SYNC();
                     const bool vis = fs_transmittance_one(M, L, G, g, &sh, st, shadow, lane);
                     rec.cv = c * (vis ? 1.f : 0.f);

@@ -471,28 +471,13 @@ __global__ void __launch_bounds__(256) k_scene_primary(SceneConst sc, size_t fir
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_samples) return;
-    const gpis_scene_s &s = sc.s;
-    size_t pix = scene_pixel(s, first_pixel + i / s.spp_count);
-    uint32_t k = (uint32_t)(i % s.spp_count);
-    uint32_t x = (uint32_t)(pix % s.width), y = (uint32_t)(pix / s.width);
-    uint32_t spp = s.spp_begin + k;
-    Pcg32 g;
-    g.set_state((uint64_t)(uint32_t)(xxhash32_4(x, y, spp, s.scene_seed) + 1u));
+    uint32_t x, y, spp;
+    Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
     float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
     float u0 = normalized_uint(g.next_i()), u1 = normalized_uint(g.next_i());
-    V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
-    V3 d = v3(local.x, local.y, -local.z);
-    V3 o = v3(s.cam_pos[0], s.cam_pos[1], s.cam_pos[2]);
     gpis_ray_in r;
-    memset(&r, 0, sizeof r);
-    r.pos[0] = o.x; r.pos[1] = o.y; r.pos[2] = o.z;
-    r.dir[0] = d.x; r.dir[1] = d.y; r.dir[2] = d.z;
-    r.pixel[0] = x; r.pixel[1] = y; r.spp = spp; r.segment = 0;
-    r.scene_seed = s.scene_seed; r.info_t = 0.f; r.u_jitter = u0;
-    r.first_scatter = 1;
-    float t0 = 0.f, t1 = 0.f;
-    bool hit = sphere_chord(o, d, s.bound_radius, t0, t1);
-    r.near_t = t0; r.far_t = t1;
+    bool hit = scene_camera_ray(sc, x, y, spp, jx, jy, r);
+    r.u_jitter = u0;
     rays[i] = r;
     u_shadow[i] = u1;
     valid[i] = hit ? 1 : 0;
@@ -514,28 +499,14 @@ __global__ void __launch_bounds__(256) k_scene_shade(SceneConst sc, size_t n_sam
         if (o.ok && !o.exited) {
             h = 1;
             V3 l = v3(sc.light[0], sc.light[1], sc.light[2]);
-            double ax = o.aniso[0], ay = o.aniso[1], az = o.aniso[2];
-            double len = sqrt(ax * ax + ay * ay + az * az);
-            V3 nn = v3((float)(ax / len), (float)(ay / len), (float)(az / len));
-            c = dot(nn, l);
+            c = dot(hit_normal(o), l);
             float t0, t1;
             if (c > 0.f && sphere_chord(v3(o.p[0], o.p[1], o.p[2]), l, sc.s.bound_radius, t0, t1)) {
                 gpis_ray_in p = prim[i];
-                gpis_ray_in sh;
-                memset(&sh, 0, sizeof sh);
-                sh.pos[0] = o.p[0]; sh.pos[1] = o.p[1]; sh.pos[2] = o.p[2];
+                gpis_ray_in sh = scene_next_ray(p, o);
                 sh.dir[0] = l.x; sh.dir[1] = l.y; sh.dir[2] = l.z;
-                sh.near_t = 0.f; sh.far_t = t1;
-                sh.pixel[0] = p.pixel[0]; sh.pixel[1] = p.pixel[1]; sh.spp = p.spp;
-                sh.segment = p.segment + 1;
-                sh.scene_seed = p.scene_seed;
-                sh.info_t = p.info_t + o.sample_t;
+                sh.far_t = t1;
                 sh.u_jitter = u_shadow[i];
-                sh.first_scatter = 0;
-                sh.bounce = p.bounce + 1;
-                sh.last_val = o.last_val;
-                sh.last_gp_id = o.gp_id;
-                sh.last_aniso[0] = o.aniso[0]; sh.last_aniso[1] = o.aniso[1]; sh.last_aniso[2] = o.aniso[2];
                 shadow[i] = sh;
                 v2 = 1;
             }
@@ -605,28 +576,13 @@ __global__ void __launch_bounds__(256) k_paths_begin(SceneConst sc, size_t first
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_samples) return;
-    const gpis_scene_s &s = sc.s;
-    size_t pix = scene_pixel(s, first_pixel + i / s.spp_count);
-    uint32_t k = (uint32_t)(i % s.spp_count);
-    uint32_t x = (uint32_t)(pix % s.width), y = (uint32_t)(pix / s.width);
-    uint32_t spp = s.spp_begin + k;
-    Pcg32 g;
-    g.set_state((uint64_t)(uint32_t)(xxhash32_4(x, y, spp, s.scene_seed) + 1u));
+    uint32_t x, y, spp;
+    Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
     float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
     float u0 = normalized_uint(g.next_i());
-    V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
-    V3 d = v3(local.x, local.y, -local.z);
-    V3 o = v3(s.cam_pos[0], s.cam_pos[1], s.cam_pos[2]);
     gpis_ray_in r;
-    memset(&r, 0, sizeof r);
-    r.pos[0] = o.x; r.pos[1] = o.y; r.pos[2] = o.z;
-    r.dir[0] = d.x; r.dir[1] = d.y; r.dir[2] = d.z;
-    r.pixel[0] = x; r.pixel[1] = y; r.spp = spp; r.segment = 0;
-    r.scene_seed = s.scene_seed; r.info_t = 0.f; r.u_jitter = u0;
-    r.first_scatter = 1;
-    float t0 = 0.f, t1 = 0.f;
-    bool hit = sphere_chord(o, d, s.bound_radius, t0, t1);
-    r.near_t = t0; r.far_t = t1;
+    bool hit = scene_camera_ray(sc, x, y, spp, jx, jy, r);
+    r.u_jitter = u0;
     a.rays[i] = r;
     a.rng[i] = g.state;
     a.throughput[i] = 1.f;
@@ -708,9 +664,7 @@ __global__ void __launch_bounds__(256) k_paths_shade(SceneConst sc, size_t n_sam
     Pcg32 g;
     g.state = a.rng[i];
     const V3 l = v3(sc.light[0], sc.light[1], sc.light[2]);
-    const double ax = o.aniso[0], ay = o.aniso[1], az = o.aniso[2];
-    const double len = sqrt(ax * ax + ay * ay + az * az);
-    const V3 n = v3((float)(ax / len), (float)(ay / len), (float)(az / len));
+    const V3 n = hit_normal(o);
     const Frame fr = frame_from_normal(n);
     const V3 dir = v3(ray.dir[0], ray.dir[1], ray.dir[2]);
     const V3 wi = normalized(to_local(fr, v3(-dir.x, -dir.y, -dir.z)));
@@ -849,9 +803,7 @@ __global__ void __launch_bounds__(256) k_nee_setup(SceneConst sc, gpis_surface_s
         NeeAux x;
         x.scheme = o.scheme;
         const V3 capDir = v3(sc.light[0], sc.light[1], sc.light[2]);
-        const double ax = o.aniso[0], ay = o.aniso[1], az = o.aniso[2];
-        const double len = sqrt(ax * ax + ay * ay + az * az);
-        const V3 n = v3((float)(ax / len), (float)(ay / len), (float)(az / len));
+        const V3 n = hit_normal(o);
         const Frame fr = frame_from_normal(n);
         const V3 dir = v3(ray.dir[0], ray.dir[1], ray.dir[2]);
         const V3 wi = normalized(to_local(fr, v3(-dir.x, -dir.y, -dir.z)));
@@ -2216,16 +2168,16 @@ extern "C" int gpis_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float 
     return ws_release(m, 0, st);
 }
 
-// Scene S through the function-space medium (gpis_fs_scene.hpp): per chunk of samples one fused launch over the resident set of
-// the function-space workspace and the per-pixel sum of its records.  Samples per chunk: GPIS_OPT_CHUNK_LOG2, else 2^22 as the
-// weight-space frame driver's (8 B of records per sample: 32 MB).
-extern "C" int gpis_fs_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radiance_sum, uint32_t *hit_count, void *stream)
+// The frame loop of the function-space scene-S drivers: per chunk of samples one fused launch over the resident set of the
+// function-space workspace (`march`: scene constants, grid, first pixel, samples) and the per-pixel sum of its records (`sum`:
+// scene constants, first pixel, pixels); each launches and returns its launch_check.  Samples per chunk: GPIS_OPT_CHUNK_LOG2,
+// else 2^22 as the weight-space frame drivers' (rec_bytes per sample: 32 MB at 8 B).  The entry has checked its arguments (its
+// CHECK_ARGS name it and quote its own condition); `entry` names it in the message of the 2^32 guard.
+template <typename March, typename Sum>
+static int fs_frame(gpis_medium *m, const gpis_scene_s *s, size_t rec_bytes, const char *entry, hipStream_t st, March march, Sum sum)
 {
-    CHECK_ARGS(std_handle(m) && s && radiance_sum);
-    CHECK_ARGS(scene_args_ok(s));
     if (int rc = fs_check(m)) return rc;
     HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = (hipStream_t)stream;
     const SceneConst sc = make_scene_const(s);
     const size_t total_pixels = scene_rows(*s) * s->width;
     if (total_pixels == 0) return GPIS_OK;
@@ -2234,53 +2186,54 @@ extern "C" int gpis_fs_render_scene_s(gpis_medium *m, const gpis_scene_s *s, flo
     if (chunk_pixels > total_pixels) chunk_pixels = total_pixels;
     const size_t ns_max = chunk_pixels * s->spp_count;
     unsigned cap = 0;
-    if (int rc = fs_workspace(m, cap, ns_max * launch::fs_scene_rec_bytes())) return rc;
+    if (int rc = fs_workspace(m, cap, ns_max * rec_bytes)) return rc;
     // the work counter runs to at most n_samples + grid
-    if (ns_max + cap >= ((size_t)1 << 32)) return set_err(GPIS_ERR_UNSUPPORTED, "gpis_fs_render_scene_s: spp_count %u", s->spp_count);
+    if (ns_max + cap >= ((size_t)1 << 32)) return set_err(GPIS_ERR_UNSUPPORTED, "%s: spp_count %u", entry, s->spp_count);
     for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
         const size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
         const size_t ns = np * s->spp_count;
         HIP_TRY(hipMemsetAsync(m->fs_scene_next, 0, sizeof(uint32_t), st));
-        launch::fs_scene((unsigned)(ns < cap ? ns : cap), m->d_model, sc, p0, (uint32_t)ns, m->fs_scene_next, m->fs_scene_recs, m->fs_ws, m->fs_slots, st);
-        if (int rc = launch_check("k_fs_scene")) return rc;
-        launch::fs_scene_sum(sc, p0, np, m->fs_scene_recs, radiance_sum, hit_count, st);
-        if (int rc = launch_check("k_fs_scene_sum")) return rc;
+        if (int rc = march(sc, (unsigned)(ns < cap ? ns : cap), p0, (uint32_t)ns)) return rc;
+        if (int rc = sum(sc, p0, np)) return rc;
     }
     return GPIS_OK;
 }
 
-// Multi-bounce paths on scene S through the function-space medium (gpis_fs_paths.hpp): the host loop of gpis_fs_render_scene_s,
-// with the second bank of state slots for the shadow segments' copies.
+// Scene S through the function-space medium (gpis_fs_scene.hpp).
+extern "C" int gpis_fs_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radiance_sum, uint32_t *hit_count, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && radiance_sum);
+    CHECK_ARGS(scene_args_ok(s));
+    hipStream_t st = (hipStream_t)stream;
+    return fs_frame(m, s, launch::fs_scene_rec_bytes(), __func__, st,
+                    [&](const SceneConst &sc, unsigned grid, size_t p0, uint32_t ns) {
+                        launch::fs_scene(grid, m->d_model, sc, p0, ns, m->fs_scene_next, m->fs_scene_recs, m->fs_ws, m->fs_slots, st);
+                        return launch_check("k_fs_scene");
+                    },
+                    [&](const SceneConst &sc, size_t p0, size_t np) {
+                        launch::fs_scene_sum(sc, p0, np, m->fs_scene_recs, radiance_sum, hit_count, st);
+                        return launch_check("k_fs_scene_sum");
+                    });
+}
+
+// Multi-bounce paths on scene S through the function-space medium (gpis_fs_paths.hpp): the second bank of state slots holds the
+// shadow segments' copies.
 extern "C" int gpis_fs_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo, float *radiance_sum,
                                             uint32_t *seg_count, void *stream)
 {
     CHECK_ARGS(std_handle(m) && s && radiance_sum && max_path_bounces >= 1);
     CHECK_ARGS(scene_args_ok(s));
-    if (int rc = fs_check(m)) return rc;
-    HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = (hipStream_t)stream;
-    const SceneConst sc = make_scene_const(s);
-    const size_t total_pixels = scene_rows(*s) * s->width;
-    if (total_pixels == 0) return GPIS_OK;
-    size_t chunk_pixels = ((size_t)1 << chunk_log2(m, 22)) / s->spp_count;
-    if (chunk_pixels < 1) chunk_pixels = 1;
-    if (chunk_pixels > total_pixels) chunk_pixels = total_pixels;
-    const size_t ns_max = chunk_pixels * s->spp_count;
-    unsigned cap = 0;
-    if (int rc = fs_workspace(m, cap, ns_max * launch::fs_paths_rec_bytes())) return rc;
-    // the work counter runs to at most n_samples + grid
-    if (ns_max + cap >= ((size_t)1 << 32)) return set_err(GPIS_ERR_UNSUPPORTED, "gpis_fs_render_scene_s_paths: spp_count %u", s->spp_count);
-    for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
-        const size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
-        const size_t ns = np * s->spp_count;
-        HIP_TRY(hipMemsetAsync(m->fs_scene_next, 0, sizeof(uint32_t), st));
-        launch::fs_paths((unsigned)(ns < cap ? ns : cap), m->d_model, sc, p0, (uint32_t)ns, max_path_bounces, albedo, m->fs_scene_next, m->fs_scene_recs, m->fs_ws,
-                         m->fs_slots, m->fs_slots + m->fs_ws_blocks, st);
-        if (int rc = launch_check("k_fs_paths")) return rc;
-        launch::fs_paths_sum(sc, p0, np, m->fs_scene_recs, radiance_sum, seg_count, st);
-        if (int rc = launch_check("k_fs_paths_sum")) return rc;
-    }
-    return GPIS_OK;
+    return fs_frame(m, s, launch::fs_paths_rec_bytes(), __func__, st,
+                    [&](const SceneConst &sc, unsigned grid, size_t p0, uint32_t ns) {
+                        launch::fs_paths(grid, m->d_model, sc, p0, ns, max_path_bounces, albedo, m->fs_scene_next, m->fs_scene_recs, m->fs_ws, m->fs_slots,
+                                         m->fs_slots + m->fs_ws_blocks, st);
+                        return launch_check("k_fs_paths");
+                    },
+                    [&](const SceneConst &sc, size_t p0, size_t np) {
+                        launch::fs_paths_sum(sc, p0, np, m->fs_scene_recs, radiance_sum, seg_count, st);
+                        return launch_check("k_fs_paths_sum");
+                    });
 }
 
 extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo, float *radiance_sum, void *stream)

@@ -1,6 +1,19 @@
-// gpis_scene.hpp — what the scene-S frame drivers of every medium share (gpis_hip.hip: the sparse-convolution drivers;
-// tu_ws_scene.hip: the weight-space driver; gpis_fs_scene.hpp: the function-space driver): the host-precomputed camera constants, the pixel order of a call, the argument
-// check and the bounding-sphere chord.  One definition, so that the drivers cannot drift apart in a single bit.
+// gpis_scene.hpp — what the scene-S drivers of every medium share.  One definition, so that the drivers cannot drift apart in a
+// single bit.
+//   host: the host-precomputed camera constants (SceneConst, make_scene_const), the pixel order of a call (scene_pixel,
+//       scene_rows) and the argument check (scene_args_ok) — gpis_hip.hip, tu_ws_scene.hip, tu_ws_paths.hip;
+//   camera step: scene_sample (pixel, spp index, seeded stream) — k_scene_primary, k_paths_begin, k_ws_scene, k_ws_paths,
+//       k_fs_scene, k_fs_paths — and scene_camera_ray (direction, bounding-sphere chord, the first gpis_ray_in) — the same but
+//       k_fs_paths;
+//   hit_normal — the six shading kernels (k_scene_shade, k_paths_shade, k_ws_scene, k_ws_paths, k_fs_scene, k_fs_paths) and
+//       k_nee_setup;
+//   scene_next_ray, the ray that continues a path from a hit — the Lambert shadow rays of k_scene_shade, k_ws_scene and
+//       k_fs_scene.
+// The device helpers draw nothing, hold no barrier and branch only on their arguments: called with wave-uniform arguments they
+// return wave-uniform results (gpis_fs_scene.hpp and gpis_fs_paths.hpp rest on this).
+// Not here: the shade step of the three path kernels (k_paths_shade, k_ws_paths, k_fs_paths: Duff frame, wi / wo, next-event
+// estimation, disk rejection, the `next` template) and the camera ray of k_fs_paths, which those kernels state in full.  As
+// functions around the inlined marches they changed the code of the whole kernel and made k_ws_paths and k_fs_paths slower.
 #pragma once
 #include <cmath>
 
@@ -80,6 +93,66 @@ __device__ __forceinline__ bool sphere_chord(V3 o, V3 d, float R, float &t0, flo
     if (ta < 0.0) ta = 0.0;
     t0 = (float)ta; t1 = (float)tb;
     return true;
+}
+
+// ---- the camera step.  Sample i of a driver call -> its pixel, its spp index and the sample's PCG32 stream, freshly seeded.
+template <typename Index>
+GPIS_DEV Pcg32 scene_sample(const SceneConst &sc, size_t first_pixel, Index i, uint32_t &x, uint32_t &y, uint32_t &spp)
+{
+    const gpis_scene_s &s = sc.s;
+    const size_t pix = scene_pixel(s, first_pixel + i / s.spp_count);
+    x = (uint32_t)(pix % s.width); y = (uint32_t)(pix / s.width);
+    spp = s.spp_begin + (uint32_t)(i % s.spp_count);
+    Pcg32 g;
+    g.set_state((uint64_t)(uint32_t)(xxhash32_4(x, y, spp, s.scene_seed) + 1u));
+    return g;
+}
+// The camera ray through pixel (x, y) jittered by (jx, jy), clipped to the bounding sphere: every field of the path's first
+// gpis_ray_in but u_jitter (the caller's own draw).  false: the ray misses the bound (near_t = far_t = 0).
+GPIS_DEV bool scene_camera_ray(const SceneConst &sc, uint32_t x, uint32_t y, uint32_t spp, float jx, float jy, gpis_ray_in &ray)
+{
+    const gpis_scene_s &s = sc.s;
+    const V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
+    const V3 d = v3(local.x, local.y, -local.z);
+    const V3 o = v3(s.cam_pos[0], s.cam_pos[1], s.cam_pos[2]);
+    memset(&ray, 0, sizeof ray);
+    ray.pos[0] = o.x; ray.pos[1] = o.y; ray.pos[2] = o.z;
+    ray.dir[0] = d.x; ray.dir[1] = d.y; ray.dir[2] = d.z;
+    ray.pixel[0] = x; ray.pixel[1] = y; ray.spp = spp; ray.segment = 0;
+    ray.scene_seed = s.scene_seed; ray.info_t = 0.f;
+    ray.first_scatter = 1;
+    float t0 = 0.f, t1 = 0.f;
+    const bool hit = sphere_chord(o, d, s.bound_radius, t0, t1);
+    ray.near_t = t0; ray.far_t = t1;
+    return hit;
+}
+
+// the sampled gradient at a hit, normalised in double and rounded per component
+GPIS_DEV V3 hit_normal(const gpis_seg_out &o)
+{
+    const double ax = o.aniso[0], ay = o.aniso[1], az = o.aniso[2];
+    const double len = sqrt(ax * ax + ay * ay + az * az);
+    return v3((float)(ax / len), (float)(ay / len), (float)(az / len));
+}
+
+// The shadow ray that continues the path of `ray` from the hit `o`: everything but dir, far_t and u_jitter, which the caller
+// fills.
+GPIS_DEV gpis_ray_in scene_next_ray(const gpis_ray_in &ray, const gpis_seg_out &o)
+{
+    gpis_ray_in next;
+    memset(&next, 0, sizeof next);
+    next.pos[0] = o.p[0]; next.pos[1] = o.p[1]; next.pos[2] = o.p[2];
+    next.near_t = 0.f;
+    next.pixel[0] = ray.pixel[0]; next.pixel[1] = ray.pixel[1]; next.spp = ray.spp;
+    next.segment = ray.segment + 1;
+    next.scene_seed = ray.scene_seed;
+    next.info_t = ray.info_t + o.sample_t;
+    next.first_scatter = 0;
+    next.bounce = ray.bounce + 1;
+    next.last_val = o.last_val;
+    next.last_gp_id = o.gp_id;
+    next.last_aniso[0] = o.aniso[0]; next.last_aniso[1] = o.aniso[1]; next.last_aniso[2] = o.aniso[2];
+    return next;
 }
 
 }   // namespace gpis

@@ -517,6 +517,19 @@ GPIS_DEV gpis_seg_out ws_sample_distance(const WsModel &W, WsLds &L, const doubl
     return o;
 }
 
+// the end of a marching kernel: lane 0 adds the wave's work counts to the handle's counters
+GPIS_DEV void ws_flush_counters(WsCounters *__restrict__ counters, const WsTally &tally, unsigned long long segs, bool overflow, int lane)
+{
+    if (lane == 0 && counters && segs) {
+        atomicAdd(&counters->n_eval, tally.eval);
+        atomicAdd(&counters->n_spec, tally.spec);
+        atomicAdd(&counters->n_seg, segs);
+    }
+    // a kept point met an argument beyond the restated range (the flag is wave-uniform: read from LDS by every lane)
+    if (lane == 0 && overflow && counters)
+        atomicAdd(&counters->arg_overflow, 1ull);
+}
+
 template <bool WANT_SAMPLE>
 __global__ void __launch_bounds__(64) k_ws_march(const WsModel *__restrict__ Wp, size_t n_rays, const gpis_ray_in *__restrict__ rays,
                                                  gpis_seg_out *__restrict__ outs, uint8_t *__restrict__ visible, double *__restrict__ workspace,
@@ -551,14 +564,7 @@ __global__ void __launch_bounds__(64) k_ws_march(const WsModel *__restrict__ Wp,
         const gpis_seg_out o = ws_sample_distance(W, L, B, ray, lane, overflow, tally);
         if (lane == 0) outs[idx] = o;
     }
-    if (lane == 0 && counters && segs) {
-        atomicAdd(&counters->n_eval, tally.eval);
-        atomicAdd(&counters->n_spec, tally.spec);
-        atomicAdd(&counters->n_seg, segs);
-    }
-    // a kept point met an argument beyond the restated range (the flag is wave-uniform: read from LDS by every lane)
-    if (lane == 0 && overflow && counters)
-        atomicAdd(&counters->arg_overflow, 1ull);
+    ws_flush_counters(counters, tally, segs, overflow, lane);
 }
 
 // test surface: value, gradient and gp id of the realization of each query (one wave per query)

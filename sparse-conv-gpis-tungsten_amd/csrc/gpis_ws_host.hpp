@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "gpis.h"
+#include "gpis_scene.hpp"
 #include "gpis_ws.hpp"
 
 namespace gpis {
@@ -102,6 +103,45 @@ inline int ws_stage(WsHandle *h, int k, size_t bytes)
     WS_HIP_TRY(hipMalloc(&h->stage[k], cap));
     h->stage_bytes[k] = cap;
     return GPIS_OK;
+}
+
+// The frame loop of the weight-space scene-S drivers (tu_ws_scene.hip, tu_ws_paths.hip), under the handle's lock: per chunk of
+// samples one fused launch (`march`: grid, first pixel, samples, records) and the per-pixel sum of its records (`sum`: first
+// pixel, pixels, records); each launches and returns its ws_launch_check.  The record array is 8 B per sample at most (32 MB a
+// chunk), and a chunk fills the grid of resident waves (2048) two thousand times over; frames of this medium are about 10^6
+// samples (about 1 M segments/s), so most frames are one chunk.  grid_cap: the handle's count of resident one-wave workgroups
+// of `kernel`, queried on the first frame.  `entry` names the caller in messages.
+template <typename Kernel, typename March, typename Sum>
+inline int ws_frame(WsHandle *h, const gpis_scene_s *s, size_t rec_bytes, const char *entry, Kernel kernel, unsigned &grid_cap, hipStream_t st, March march, Sum sum)
+{
+    constexpr size_t kFrameChunk = (size_t)1 << 22;      // samples per chunk
+    const size_t total_pixels = scene_rows(*s) * s->width;
+    if (total_pixels == 0) return GPIS_OK;
+    if (!grid_cap) {
+        hipDeviceProp_t prop;
+        WS_HIP_TRY(hipGetDeviceProperties(&prop, h->device));
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 8;
+        grid_cap = (unsigned)(per_cu * (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1));
+    }
+    if (!h->d_scene_next) WS_HIP_TRY(hipMalloc(&h->d_scene_next, sizeof(uint32_t)));
+    size_t chunk_pixels = kFrameChunk / s->spp_count;
+    if (chunk_pixels < 1) chunk_pixels = 1;
+    if (chunk_pixels > total_pixels) chunk_pixels = total_pixels;
+    const size_t ns_max = chunk_pixels * s->spp_count;
+    if (ns_max + grid_cap >= ((size_t)1 << 32)) return ws_err(GPIS_ERR_UNSUPPORTED, "%s: spp_count %u", entry, s->spp_count);
+    if (int rc = ws_stage(h, 2, ns_max * rec_bytes)) return rc;
+    void *recs = h->stage[2];
+    const unsigned grid = (unsigned)(ns_max < grid_cap ? ns_max : grid_cap);
+    if (int rc = ws_ensure_work(h, grid)) return rc;
+    for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
+        const size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
+        const size_t ns = np * s->spp_count;
+        WS_HIP_TRY(hipMemsetAsync(h->d_scene_next, 0, sizeof(uint32_t), st));
+        if (int rc = march((unsigned)(ns < grid ? ns : grid), p0, (uint32_t)ns, recs)) return rc;
+        if (int rc = sum(p0, np, recs)) return rc;
+    }
+    return ws_check_overflow(h, st);
 }
 
 }   // namespace gpis

@@ -22,8 +22,9 @@
 //       hits builds k + 1 realizations where the staged form builds up to 2k + 1.
 // One realization per wave at a time is enough: the workspace is the handle's one [6][N] slice per workgroup.
 //
-// The shading arithmetic (Duff frame, wi / wo, disk rejection, next-ray fill) restates k_paths_shade's line for line rather than
-// sharing a function with it: k_paths_shade is left as it is, and the tests pin the two against the same C.
+// The camera step and the hit normal are gpis_scene.hpp's helpers, the counter flush is gpis_ws.hpp's.  The shade step (Duff
+// frame, wi / wo, next-event estimation, disk rejection, next-ray fill) is stated here in full, as in k_paths_shade and
+// k_fs_paths: shared as functions around the marches it made this kernel slower (gpis_scene.hpp).
 #pragma once
 #include "gpis_scene.hpp"
 #include "gpis_ws.hpp"
@@ -58,26 +59,14 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_paths(const WsModel *_
         i = __builtin_amdgcn_readfirstlane(i);
         if (i >= n_samples) break;
         // ---- k_paths_begin
-        const size_t pix = scene_pixel(s, first_pixel + i / s.spp_count);
-        const uint32_t x = (uint32_t)(pix % s.width), y = (uint32_t)(pix / s.width);
-        const uint32_t spp = s.spp_begin + i % s.spp_count;
-        Pcg32 g;
-        g.set_state((uint64_t)(uint32_t)(xxhash32_4(x, y, spp, s.scene_seed) + 1u));
+        uint32_t x, y, spp;
+        Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
         const float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
         const float u0 = normalized_uint(g.next_i());
-        const V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
-        const V3 d0 = v3(local.x, local.y, -local.z);
-        const V3 o0 = v3(s.cam_pos[0], s.cam_pos[1], s.cam_pos[2]);
         float emission = 0.f;
-        float c0 = 0.f, c1 = 0.f;
-        if (sphere_chord(o0, d0, s.bound_radius, c0, c1)) {
-            gpis_ray_in ray{};
-            ray.pos[0] = o0.x; ray.pos[1] = o0.y; ray.pos[2] = o0.z;
-            ray.dir[0] = d0.x; ray.dir[1] = d0.y; ray.dir[2] = d0.z;
-            ray.near_t = c0; ray.far_t = c1;
-            ray.pixel[0] = x; ray.pixel[1] = y; ray.spp = spp; ray.segment = 0;
-            ray.scene_seed = s.scene_seed; ray.info_t = 0.f; ray.u_jitter = u0;
-            ray.first_scatter = 1;
+        gpis_ray_in ray;
+        if (scene_camera_ray(sc, x, y, spp, jx, jy, ray)) {
+            ray.u_jitter = u0;
             float thr = 1.f;
             int built = -1;                  // segment word of the realization in `own` (any word under GLOBAL once built)
             for (int bounce = 0; bounce < max_bounces; ++bounce) {
@@ -95,9 +84,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_paths(const WsModel *_
                 thr = thr * r.weight[0];
                 if (r.exited) break;
                 if (bounce + 1 >= max_bounces) break;        // no NEE at the last bounce, and the bounce itself cannot be seen
-                const double ax = r.aniso[0], ay = r.aniso[1], az = r.aniso[2];
-                const double len = sqrt(ax * ax + ay * ay + az * az);
-                const V3 n = v3((float)(ax / len), (float)(ay / len), (float)(az / len));
+                const V3 n = hit_normal(r);
                 const Frame fr = frame_from_normal(n);
                 const V3 dir = v3(ray.dir[0], ray.dir[1], ray.dir[2]);
                 const V3 wi = normalized(to_local(fr, v3(-dir.x, -dir.y, -dir.z)));
@@ -161,13 +148,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_paths(const WsModel *_
         }
         if (lane == 0) recs[i] = WsPathsRec{emission};
     }
-    if (lane == 0 && counters && segs) {
-        atomicAdd(&counters->n_eval, tally.eval);
-        atomicAdd(&counters->n_spec, tally.spec);
-        atomicAdd(&counters->n_seg, segs);
-    }
-    if (lane == 0 && overflow && counters)
-        atomicAdd(&counters->arg_overflow, 1ull);
+    ws_flush_counters(counters, tally, segs, overflow, lane);
 }
 
 // one lane per pixel: sequential sum over its samples' emissions, in sample order (k_paths_accumulate's sum)

@@ -46,26 +46,14 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_scene(const WsModel *_
         i = __builtin_amdgcn_readfirstlane(i);
         if (i >= n_samples) break;
         // ---- k_scene_primary
-        const size_t pix = scene_pixel(s, first_pixel + i / s.spp_count);
-        const uint32_t x = (uint32_t)(pix % s.width), y = (uint32_t)(pix / s.width);
-        const uint32_t spp = s.spp_begin + i % s.spp_count;
-        Pcg32 g;
-        g.set_state((uint64_t)(uint32_t)(xxhash32_4(x, y, spp, s.scene_seed) + 1u));
+        uint32_t x, y, spp;
+        Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
         const float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
         const float u0 = normalized_uint(g.next_i()), u1 = normalized_uint(g.next_i());
-        const V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
-        const V3 d = v3(local.x, local.y, -local.z);
-        const V3 o = v3(s.cam_pos[0], s.cam_pos[1], s.cam_pos[2]);
         WsSceneRec rec{0.f, 0u};
-        float t0 = 0.f, t1 = 0.f;
-        if (sphere_chord(o, d, s.bound_radius, t0, t1)) {
-            gpis_ray_in ray{};
-            ray.pos[0] = o.x; ray.pos[1] = o.y; ray.pos[2] = o.z;
-            ray.dir[0] = d.x; ray.dir[1] = d.y; ray.dir[2] = d.z;
-            ray.near_t = t0; ray.far_t = t1;
-            ray.pixel[0] = x; ray.pixel[1] = y; ray.spp = spp; ray.segment = 0;
-            ray.scene_seed = s.scene_seed; ray.info_t = 0.f; ray.u_jitter = u0;
-            ray.first_scatter = 1;
+        gpis_ray_in ray;
+        if (scene_camera_ray(sc, x, y, spp, jx, jy, ray)) {
+            ray.u_jitter = u0;
             const double *B = W.basis;
             if (!W.single) {
                 uint32_t pss[4];
@@ -79,26 +67,13 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_scene(const WsModel *_
             // ---- k_scene_shade
             if (r.ok && !r.exited) {
                 rec.flags = 1u;
-                const double ax = r.aniso[0], ay = r.aniso[1], az = r.aniso[2];
-                const double len = sqrt(ax * ax + ay * ay + az * az);
-                const V3 nn = v3((float)(ax / len), (float)(ay / len), (float)(az / len));
-                const float c = dot(nn, l);
+                const float c = dot(hit_normal(r), l);
                 float s0, s1;
                 if (c > 0.f && sphere_chord(v3(r.p[0], r.p[1], r.p[2]), l, s.bound_radius, s0, s1)) {
-                    gpis_ray_in sh{};
-                    sh.pos[0] = r.p[0]; sh.pos[1] = r.p[1]; sh.pos[2] = r.p[2];
+                    gpis_ray_in sh = scene_next_ray(ray, r);
                     sh.dir[0] = l.x; sh.dir[1] = l.y; sh.dir[2] = l.z;
-                    sh.near_t = 0.f; sh.far_t = s1;
-                    sh.pixel[0] = x; sh.pixel[1] = y; sh.spp = spp;
-                    sh.segment = ray.segment + 1;
-                    sh.scene_seed = ray.scene_seed;
-                    sh.info_t = ray.info_t + r.sample_t;
+                    sh.far_t = s1;
                     sh.u_jitter = u1;
-                    sh.first_scatter = 0;
-                    sh.bounce = ray.bounce + 1;
-                    sh.last_val = r.last_val;
-                    sh.last_gp_id = r.gp_id;
-                    sh.last_aniso[0] = r.aniso[0]; sh.last_aniso[1] = r.aniso[1]; sh.last_aniso[2] = r.aniso[2];
                     if (!reuse) {
                         uint32_t pss[4];
                         ws_pss(W, x, y, spp, sh.segment, pss);
@@ -117,13 +92,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_scene(const WsModel *_
         }
         if (lane == 0) recs[i] = rec;
     }
-    if (lane == 0 && counters && segs) {
-        atomicAdd(&counters->n_eval, tally.eval);
-        atomicAdd(&counters->n_spec, tally.spec);
-        atomicAdd(&counters->n_seg, segs);
-    }
-    if (lane == 0 && overflow && counters)
-        atomicAdd(&counters->arg_overflow, 1ull);
+    ws_flush_counters(counters, tally, segs, overflow, lane);
 }
 
 // one lane per pixel: sequential sum over its samples, in sample order (k_scene_accumulate's sum)

@@ -10,14 +10,6 @@
 
 using namespace gpis;
 
-namespace {
-
-// Samples per chunk: the record array is 8 B per sample (32 MB), and a chunk fills the grid of resident waves (2048) two
-// thousand times over.  Frames of this medium are about 10^6 samples (about 1 M segments/s), so most frames are one chunk.
-constexpr size_t kSceneChunk = (size_t)1 << 22;
-
-}   // namespace
-
 extern "C" int gpis_ws_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radiance_sum, uint32_t *hit_count, void *stream)
 {
     WS_HANDLE(m);
@@ -27,33 +19,13 @@ extern "C" int gpis_ws_render_scene_s(gpis_medium *m, const gpis_scene_s *s, flo
     WS_HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     const SceneConst sc = make_scene_const(s);
-    const size_t total_pixels = scene_rows(*s) * s->width;
-    if (total_pixels == 0) return GPIS_OK;
-    if (!h->scene_grid_cap) {
-        hipDeviceProp_t prop;
-        WS_HIP_TRY(hipGetDeviceProperties(&prop, h->device));
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ws_scene<0>, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 8;
-        h->scene_grid_cap = (unsigned)(per_cu * (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1));
-    }
-    if (!h->d_scene_next) WS_HIP_TRY(hipMalloc(&h->d_scene_next, sizeof(uint32_t)));
-    size_t chunk_pixels = kSceneChunk / s->spp_count;
-    if (chunk_pixels < 1) chunk_pixels = 1;
-    if (chunk_pixels > total_pixels) chunk_pixels = total_pixels;
-    const size_t ns_max = chunk_pixels * s->spp_count;
-    if (ns_max + h->scene_grid_cap >= ((size_t)1 << 32)) return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_render_scene_s: spp_count %u", s->spp_count);
-    if (int rc = ws_stage(h, 2, ns_max * sizeof(WsSceneRec))) return rc;
-    WsSceneRec *recs = (WsSceneRec *)h->stage[2];
-    const unsigned grid = (unsigned)(ns_max < h->scene_grid_cap ? ns_max : h->scene_grid_cap);
-    if (int rc = ws_ensure_work(h, grid)) return rc;
-    for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
-        const size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
-        const size_t ns = np * s->spp_count;
-        WS_HIP_TRY(hipMemsetAsync(h->d_scene_next, 0, sizeof(uint32_t), st));
-        k_ws_scene<0><<<(unsigned)(ns < grid ? ns : grid), 64, 0, st>>>(h->d_model, sc, p0, (uint32_t)ns, h->d_scene_next, recs, h->d_work, h->d_counters);
-        if (int rc = ws_launch_check("k_ws_scene")) return rc;
-        k_ws_scene_sum<0><<<(unsigned)((np + 255) / 256), 256, 0, st>>>(sc, p0, np, recs, radiance_sum, hit_count);
-        if (int rc = ws_launch_check("k_ws_scene_sum")) return rc;
-    }
-    return ws_check_overflow(h, st);
+    return ws_frame(h, s, sizeof(WsSceneRec), __func__, k_ws_scene<0>, h->scene_grid_cap, st,
+                    [&](unsigned grid, size_t p0, uint32_t ns, void *recs) {
+                        k_ws_scene<0><<<grid, 64, 0, st>>>(h->d_model, sc, p0, ns, h->d_scene_next, (WsSceneRec *)recs, h->d_work, h->d_counters);
+                        return ws_launch_check("k_ws_scene");
+                    },
+                    [&](size_t p0, size_t np, const void *recs) {
+                        k_ws_scene_sum<0><<<(unsigned)((np + 255) / 256), 256, 0, st>>>(sc, p0, np, (const WsSceneRec *)recs, radiance_sum, hit_count);
+                        return ws_launch_check("k_ws_scene_sum");
+                    });
 }

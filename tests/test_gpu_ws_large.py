@@ -13,7 +13,7 @@ from test_gpu_ws_scene import _accumulate, _bits, _non_vacuous
 
 pytestmark = pytest.mark.gpu
 
-CHUNK = 2 ** 22                 # kSceneChunk (csrc/tu_ws_scene.hip)
+CHUNK = 2 ** 22                 # kFrameChunk (ws_frame, csrc/gpis_ws_host.hpp)
 
 # name -> ws_params keywords.  N <= 65 except the one N = 300 per-path case.
 BATCH_CASES = {
