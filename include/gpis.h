@@ -604,6 +604,36 @@ typedef struct gpis_surface_s {
 int gpis_render_scene_s_nee(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_s *surf,
                             float *radiance_sum, void *stream);
 
+/* Multi-bounce paths with the estimator of gpis_render_scene_s_nee at every hit: PathTracer::traceSample
+ * (PathTracer.cpp:62-169) over TraceBase::handleVolume (TraceBase.cpp:539-563) for the conductor micro-surface and the cap
+ * light.  Accepts and refuses what gpis_render_scene_s_nee does (handles, surf, rows, tile-row shards, spp ranges) and refuses
+ * max_path_bounces < 1.  Per sample (x, y, k): one PCG32 stream, set_state(xxhash32(x, y, k, scene_seed) + 1); the draws jx, jy
+ * and the first march jitter; the camera ray clipped to the bounding sphere (a miss adds nothing and marches nothing);
+ * thr = 1, E = 0.  Then for b = 0; b + 1 < max_path_bounces; ++b:
+ *   1. sampleDistance of the current ray with segment word b (its gpis_cond_coeff is kept).  !ok ends the path;
+ *      thr = thr * weight[0]; `exited` ends the path (the light seen directly is never added).
+ *   2. L = volumeLightSample + volumePhaseSample exactly as gpis_render_scene_s_nee computes them for this segment; the shadow
+ *      segments run on the state copy with segment b+1, bounce+1, first_scatter = 0 (lastAniso = neeGrad(half vector) for the
+ *      light sample, the sampled aniso for the phase sample).  Draws in the serial order: z and the disk pairs (schemes NEE,
+ *      MIS), then ONE jitter per shadow segment that is marched, the light's first.  E = E + thr * L.
+ *   3. The bounce (ConductorBsdf::sample, ConductorBsdf.cpp:59-76): thr = thr * F with the F = albedo * conductorReflectance(eta,
+ *      k, wi.z) that went into L; thr == 0 ends the path (PathTracer.cpp:143); w = normalized(toGlobal(-wi.x, -wi.y, wi.z)) for
+ *      every scheme; no chord of (p, w) through the bounding sphere ends the path.  The reference evaluates neePDF for the
+ *      sampled direction and does not use the value; no such evaluation is made (or counted) here.
+ *   4. Only if b + 2 < max_path_bounces, the next ray: pos = p, dir = w, near = 0, far = the chord's end, segment b+1,
+ *      first_scatter = 0, bounce+1, last_val / last_gp_id / last_aniso from the segment's result, info_t + sample_t, and
+ *      u_jitter = the stream's next draw.  Otherwise nothing follows and nothing is drawn.
+ * There is NO Russian roulette (PathTracer.cpp:145-151 is left out, as in the Lambert path drivers: nextBoolean would add a
+ * draw per bounce).  The segment of bounce max_path_bounces - 1 is not marched, since it cannot contribute (TraceBase.cpp:546):
+ * max_path_bounces = 1 adds zeros, and with max_path_bounces = 2 on a medium whose weight[0] is exactly 1 the image equals
+ * gpis_render_scene_s_nee's bit for bit.  All float arithmetic runs with contraction off.
+ * Each pixel's sum of E, taken in sample order from zero, is ACCUMULATED into radiance_sum[height*width] once per chunk of
+ * samples, and per pixel the segments marched (path, light shadow and phase shadow segments) into seg_count[height*width]
+ * (device pointers; seg_count may be NULL).  Image and counts depend neither on how a frame is cut into calls (rows, shards,
+ * spp ranges) or chunks (GPIS_OPT_CHUNK_LOG2) nor on any tuning option.  Asynchronous on `stream`. */
+int gpis_render_scene_s_nee_paths(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_s *surf, int max_path_bounces,
+                                  float *radiance_sum, uint32_t *seg_count, void *stream);
+
 /* Multi-bounce wavefront driver on scene S: per sample, up to `max_path_bounces`
  * medium interactions following PathTracer::traceSample / TraceBase::handleVolume
  * (PathTracer.cpp:62-75, TraceBase.cpp:539-563):

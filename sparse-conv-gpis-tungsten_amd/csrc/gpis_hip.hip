@@ -790,6 +790,127 @@ struct NeeArrays {
     uint8_t *want_light, *want_phase, *want_pdf_normal, *go_light, *go_phase, *vis_light, *vis_phase;
 };
 
+// ---- the light and phase estimators of one hit, stated once for the single-bounce driver (k_nee_setup, k_nee_shade,
+// k_nee_gather) and the path driver (k_nee_paths_setup, k_nee_paths_shade, k_nee_paths_gather).
+
+// Before the neePDF / neeGrad launches, at the hit `o` of `ray` (sample i): F, the light direction (volumeLightSample: a direction
+// inside the cap, drawn from g — z, then the disk pairs — for the schemes NEE and MIS) with its half-vector query, and the mirror
+// direction of ConductorBsdf::sample for EVERY scheme (the path driver bounces along it) with, for UNI and MIS, the test whether
+// it sees the cap and the query at the sampled normal.  Fills x but v1 / v2; writes b.q_half[i] / b.q_normal[i] where wanted.
+__device__ __forceinline__ void nee_setup_sample(const SceneConst &sc, const gpis_surface_s &sf, const gpis_ray_in &ray, const gpis_seg_out &o,
+                                                 Pcg32 &g, size_t i, const NeeArrays &b, NeeAux &x, uint8_t &wl, uint8_t &wp, uint8_t &wn)
+{
+    x.scheme = o.scheme;
+    const V3 capDir = v3(sc.light[0], sc.light[1], sc.light[2]);
+    const V3 n = hit_normal(o);
+    const Frame fr = frame_from_normal(n);
+    const V3 dir = v3(ray.dir[0], ray.dir[1], ray.dir[2]);
+    const V3 wi = normalized(to_local(fr, v3(-dir.x, -dir.y, -dir.z)));
+    x.F = sf.albedo * conductor_reflectance(sf.eta, sf.k, wi.z);
+    gpis_nee_query q;
+    memset(&q, 0, sizeof q);
+    q.ray_dir[0] = dir.x; q.ray_dir[1] = dir.y; q.ray_dir[2] = dir.z;
+    q.p[0] = o.p[0]; q.p[1] = o.p[1]; q.p[2] = o.p[2];
+    q.t_segment = o.sample_t;
+    q.info_t = ray.info_t + o.sample_t;
+    q.pixel[0] = ray.pixel[0]; q.pixel[1] = ray.pixel[1]; q.spp = ray.spp; q.segment = ray.segment;
+    q.scene_seed = ray.scene_seed;
+    q.coeff = b.coeff[i];
+    x.d[0] = x.d[1] = x.d[2] = 0.f;
+    if (x.scheme != GPIS_UNI) {     // volumeLightSample: a direction inside the cap
+        const float z = normalized_uint(g.next_i()) * (1.0f - sf.cap_cos) + sf.cap_cos;
+        float dx, dy, d2;
+        do {
+            dx = 2.f * normalized_uint(g.next_i()) - 1.f;
+            dy = 2.f * normalized_uint(g.next_i()) - 1.f;
+            d2 = dx * dx + dy * dy;
+        } while (!(d2 < 1.f) || !(d2 > 1e-12f));
+        const float rr = 1.0f - z * z;
+        const float rad = sqrtf(rr > 0.f ? rr : 0.f) / sqrtf(d2);
+        const Frame cf = frame_from_normal(capDir);
+        const V3 d = to_global(cf, v3(dx * rad, dy * rad, z));
+        const V3 wo = normalized(to_local(fr, d));
+        const V3 nl = (wi + wo) * 0.5f;
+        const V3 nw = normalized(to_global(fr, nl));
+        x.d[0] = d.x; x.d[1] = d.y; x.d[2] = d.z;
+        gpis_nee_query qh = q;
+        qh.normal[0] = nw.x; qh.normal[1] = nw.y; qh.normal[2] = nw.z;
+        b.q_half[i] = qh;
+        wl = 1;
+    }
+    const V3 w = normalized(to_global(fr, v3(-wi.x, -wi.y, wi.z)));     // ConductorBsdf::sample: mirror about the sampled normal
+    x.w[0] = w.x; x.w[1] = w.y; x.w[2] = w.z;
+    if (x.scheme != GPIS_NEE) {     // volumePhaseSample
+        float t0, t1;
+        if (!(dot(w, capDir) < sf.cap_cos) && sphere_chord(v3(o.p[0], o.p[1], o.p[2]), w, sc.s.bound_radius, t0, t1)) {
+            wp = 1;
+            if (x.scheme != GPIS_UNI) {
+                gpis_nee_query qn = q;
+                qn.normal[0] = n.x; qn.normal[1] = n.y; qn.normal[2] = n.z;
+                b.q_normal[i] = qn;
+                wn = 1;
+            }
+        }
+    }
+}
+
+// After the neePDF / neeGrad launches, for a sample with want_light or want_phase: the shadow segments that are marched (gl, gp;
+// the light's takes the jitter x.v1, the phase's the next one) and what each adds to L when it is visible.
+__device__ __forceinline__ void nee_shade_sample(const SceneConst &sc, const gpis_surface_s &sf, const gpis_ray_in &ray, const gpis_seg_out &o,
+                                                 const NeeAux &x, size_t i, const NeeArrays &b, uint8_t &gl, uint8_t &gp)
+{
+    const float pdf_l = (0.5f * (1.0f / 3.1415926536f)) / (1.0f - sf.cap_cos);
+    const V3 p = v3(o.p[0], o.p[1], o.p[2]);
+    const gpis_ray_in sh0 = scene_next_ray(ray, o);      // handleVolume's copy of the state: segment word + 1
+    if (b.want_light[i]) {
+        const float pdf = b.pdf_half[i];
+        const float f = x.F * pdf;
+        float t0, t1;
+        const V3 d = v3(x.d[0], x.d[1], x.d[2]);
+        if (f != 0.0f && sphere_chord(p, d, sc.s.bound_radius, t0, t1)) {
+            gpis_ray_in sh = sh0;
+            sh.dir[0] = d.x; sh.dir[1] = d.y; sh.dir[2] = d.z;
+            sh.far_t = t1;
+            sh.u_jitter = x.v1;
+            sh.last_aniso[0] = (double)b.grad_half[3 * i]; sh.last_aniso[1] = (double)b.grad_half[3 * i + 1]; sh.last_aniso[2] = (double)b.grad_half[3 * i + 2];
+            b.shadow_light[i] = sh;
+            const float e = 1.f * sf.cap_radiance;
+            float lightF = f * e / pdf_l;
+            if (x.scheme != GPIS_NEE)
+                lightF *= power_heuristic(pdf_l, pdf);
+            b.contrib_light[i] = lightF;
+            gl = 1;
+        }
+    }
+    if (b.want_phase[i]) {
+        float t0, t1;
+        const V3 w = v3(x.w[0], x.w[1], x.w[2]);
+        (void)sphere_chord(p, w, sc.s.bound_radius, t0, t1);   // known to succeed (nee_setup_sample)
+        gpis_ray_in sh = sh0;
+        sh.dir[0] = w.x; sh.dir[1] = w.y; sh.dir[2] = w.z;
+        sh.far_t = t1;
+        sh.u_jitter = gl ? x.v2 : x.v1;
+        b.shadow_phase[i] = sh;
+        const float e = 1.f * sf.cap_radiance;
+        float phaseF = e * x.F;
+        if (x.scheme != GPIS_UNI)
+            phaseF *= power_heuristic(b.pdf_normal[i], pdf_l);
+        b.contrib_phase[i] = phaseF;
+        gp = 1;
+    }
+}
+
+// After the shadow marches: L of sample i
+__device__ __forceinline__ float nee_gather_sample(float cap_radiance, size_t i, const NeeArrays &b)
+{
+    float L = 0.f;
+    if (cap_radiance != 0.0f) {     // e == 0 ends both estimators (TraceBase.cpp:374, 410)
+        if (b.go_light[i] && b.vis_light[i]) L += b.contrib_light[i];
+        if (b.go_phase[i] && b.vis_phase[i]) L += b.contrib_phase[i];
+    }
+    return L;
+}
+
 __global__ void __launch_bounds__(256) k_nee_setup(SceneConst sc, gpis_surface_s sf, size_t n_samples, PathArrays a, NeeArrays b)
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -801,59 +922,7 @@ __global__ void __launch_bounds__(256) k_nee_setup(SceneConst sc, gpis_surface_s
         Pcg32 g;
         g.state = a.rng[i];
         NeeAux x;
-        x.scheme = o.scheme;
-        const V3 capDir = v3(sc.light[0], sc.light[1], sc.light[2]);
-        const V3 n = hit_normal(o);
-        const Frame fr = frame_from_normal(n);
-        const V3 dir = v3(ray.dir[0], ray.dir[1], ray.dir[2]);
-        const V3 wi = normalized(to_local(fr, v3(-dir.x, -dir.y, -dir.z)));
-        x.F = sf.albedo * conductor_reflectance(sf.eta, sf.k, wi.z);
-        gpis_nee_query q;
-        memset(&q, 0, sizeof q);
-        q.ray_dir[0] = dir.x; q.ray_dir[1] = dir.y; q.ray_dir[2] = dir.z;
-        q.p[0] = o.p[0]; q.p[1] = o.p[1]; q.p[2] = o.p[2];
-        q.t_segment = o.sample_t;
-        q.info_t = ray.info_t + o.sample_t;
-        q.pixel[0] = ray.pixel[0]; q.pixel[1] = ray.pixel[1]; q.spp = ray.spp; q.segment = ray.segment;
-        q.scene_seed = ray.scene_seed;
-        q.coeff = b.coeff[i];
-        x.d[0] = x.d[1] = x.d[2] = 0.f;
-        if (x.scheme != GPIS_UNI) {     // volumeLightSample: a direction inside the cap
-            const float z = normalized_uint(g.next_i()) * (1.0f - sf.cap_cos) + sf.cap_cos;
-            float dx, dy, d2;
-            do {
-                dx = 2.f * normalized_uint(g.next_i()) - 1.f;
-                dy = 2.f * normalized_uint(g.next_i()) - 1.f;
-                d2 = dx * dx + dy * dy;
-            } while (!(d2 < 1.f) || !(d2 > 1e-12f));
-            const float rr = 1.0f - z * z;
-            const float rad = sqrtf(rr > 0.f ? rr : 0.f) / sqrtf(d2);
-            const Frame cf = frame_from_normal(capDir);
-            const V3 d = to_global(cf, v3(dx * rad, dy * rad, z));
-            const V3 wo = normalized(to_local(fr, d));
-            const V3 nl = (wi + wo) * 0.5f;
-            const V3 nw = normalized(to_global(fr, nl));
-            x.d[0] = d.x; x.d[1] = d.y; x.d[2] = d.z;
-            gpis_nee_query qh = q;
-            qh.normal[0] = nw.x; qh.normal[1] = nw.y; qh.normal[2] = nw.z;
-            b.q_half[i] = qh;
-            wl = 1;
-        }
-        x.w[0] = x.w[1] = x.w[2] = 0.f;
-        if (x.scheme != GPIS_NEE) {     // volumePhaseSample: mirror about the sampled normal
-            const V3 w = normalized(to_global(fr, v3(-wi.x, -wi.y, wi.z)));
-            x.w[0] = w.x; x.w[1] = w.y; x.w[2] = w.z;
-            float t0, t1;
-            if (!(dot(w, capDir) < sf.cap_cos) && sphere_chord(v3(o.p[0], o.p[1], o.p[2]), w, sc.s.bound_radius, t0, t1)) {
-                wp = 1;
-                if (x.scheme != GPIS_UNI) {
-                    gpis_nee_query qn = q;
-                    qn.normal[0] = n.x; qn.normal[1] = n.y; qn.normal[2] = n.z;
-                    b.q_normal[i] = qn;
-                    wn = 1;
-                }
-            }
-        }
+        nee_setup_sample(sc, sf, ray, o, g, i, b, x, wl, wp, wn);
         x.v1 = normalized_uint(g.next_i());
         x.v2 = normalized_uint(g.next_i());
         b.aux[i] = x;
@@ -868,64 +937,8 @@ __global__ void __launch_bounds__(256) k_nee_shade(SceneConst sc, gpis_surface_s
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_samples) return;
     uint8_t gl = 0, gp = 0;
-    if (b.want_light[i] || b.want_phase[i]) {
-        const gpis_seg_out o = a.seg[i];
-        const gpis_ray_in ray = a.rays[i];
-        const NeeAux x = b.aux[i];
-        const float pdf_l = (0.5f * (1.0f / 3.1415926536f)) / (1.0f - sf.cap_cos);
-        const V3 p = v3(o.p[0], o.p[1], o.p[2]);
-        gpis_ray_in sh0;
-        memset(&sh0, 0, sizeof sh0);
-        sh0.pos[0] = p.x; sh0.pos[1] = p.y; sh0.pos[2] = p.z;
-        sh0.near_t = 0.f;
-        sh0.pixel[0] = ray.pixel[0]; sh0.pixel[1] = ray.pixel[1]; sh0.spp = ray.spp;
-        sh0.segment = ray.segment + 1;
-        sh0.scene_seed = ray.scene_seed;
-        sh0.info_t = ray.info_t + o.sample_t;
-        sh0.first_scatter = 0;
-        sh0.bounce = ray.bounce + 1;
-        sh0.last_val = o.last_val;
-        sh0.last_gp_id = o.gp_id;
-        sh0.last_aniso[0] = o.aniso[0]; sh0.last_aniso[1] = o.aniso[1]; sh0.last_aniso[2] = o.aniso[2];
-        bool light_drew = false;
-        if (b.want_light[i]) {
-            const float pdf = b.pdf_half[i];
-            const float f = x.F * pdf;
-            float t0, t1;
-            const V3 d = v3(x.d[0], x.d[1], x.d[2]);
-            if (f != 0.0f && sphere_chord(p, d, sc.s.bound_radius, t0, t1)) {
-                gpis_ray_in sh = sh0;
-                sh.dir[0] = d.x; sh.dir[1] = d.y; sh.dir[2] = d.z;
-                sh.far_t = t1;
-                sh.u_jitter = x.v1;
-                sh.last_aniso[0] = (double)b.grad_half[3 * i]; sh.last_aniso[1] = (double)b.grad_half[3 * i + 1]; sh.last_aniso[2] = (double)b.grad_half[3 * i + 2];
-                b.shadow_light[i] = sh;
-                const float e = 1.f * sf.cap_radiance;
-                float lightF = f * e / pdf_l;
-                if (x.scheme != GPIS_NEE)
-                    lightF *= power_heuristic(pdf_l, pdf);
-                b.contrib_light[i] = lightF;
-                light_drew = true;
-                gl = 1;
-            }
-        }
-        if (b.want_phase[i]) {
-            float t0, t1;
-            const V3 w = v3(x.w[0], x.w[1], x.w[2]);
-            (void)sphere_chord(p, w, sc.s.bound_radius, t0, t1);   // known to succeed (k_nee_setup)
-            gpis_ray_in sh = sh0;
-            sh.dir[0] = w.x; sh.dir[1] = w.y; sh.dir[2] = w.z;
-            sh.far_t = t1;
-            sh.u_jitter = light_drew ? x.v2 : x.v1;
-            b.shadow_phase[i] = sh;
-            const float e = 1.f * sf.cap_radiance;
-            float phaseF = e * x.F;
-            if (x.scheme != GPIS_UNI)
-                phaseF *= power_heuristic(b.pdf_normal[i], pdf_l);
-            b.contrib_phase[i] = phaseF;
-            gp = 1;
-        }
-    }
+    if (b.want_light[i] || b.want_phase[i])
+        nee_shade_sample(sc, sf, a.rays[i], a.seg[i], b.aux[i], i, b, gl, gp);
     b.go_light[i] = gl;
     b.go_phase[i] = gp;
 }
@@ -934,12 +947,107 @@ __global__ void __launch_bounds__(256) k_nee_gather(float cap_radiance, size_t n
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_samples) return;
-    float L = 0.f;
-    if (cap_radiance != 0.0f) {     // e == 0 ends both estimators (TraceBase.cpp:374, 410)
-        if (b.go_light[i] && b.vis_light[i]) L += b.contrib_light[i];
-        if (b.go_phase[i] && b.vis_phase[i]) L += b.contrib_phase[i];
+    a.emission[i] = nee_gather_sample(cap_radiance, i, b);
+}
+
+// ---- the bounce loop of the same estimator (gpis_render_scene_s_nee_paths): PathTracer.cpp:62-169 over TraceBase.cpp:539-563,
+// ConductorBsdf.cpp:59-76.  Per bounce: march the live paths, k_nee_paths_setup, neePDF / neeGrad, k_nee_paths_shade, the two
+// shadow marches, k_nee_paths_gather.  a.alive is the mask of each stage in turn: the paths to march, then (set-up) the paths that
+// hit, then (shade) the paths whose next segment a.rays holds.
+struct NeePathArrays {     // per sample
+    float *thr_hit;        // throughput at this bounce's hit, weight[0] included and F not: the factor of L
+    uint32_t *segs;        // segments marched so far: path, light shadow and phase shadow segments
+};
+
+__global__ void __launch_bounds__(256) k_nee_paths_setup(SceneConst sc, gpis_surface_s sf, size_t n_samples, PathArrays a, NeeArrays b, NeePathArrays c)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_samples) return;
+    uint8_t wl = 0, wp = 0, wn = 0;
+    if (a.alive[i]) {
+        c.segs[i] += 1;
+        uint8_t hit = 0;
+        const gpis_seg_out o = a.seg[i];
+        if (o.ok) {
+            const float thr = a.throughput[i] * o.weight[0];
+            a.throughput[i] = thr;
+            if (!o.exited) {        // the light seen directly is never added
+                const gpis_ray_in ray = a.rays[i];
+                Pcg32 g;
+                g.state = a.rng[i];
+                NeeAux x;
+                nee_setup_sample(sc, sf, ray, o, g, i, b, x, wl, wp, wn);
+                a.rng[i] = g.state;     // v1, v2 look ahead: how many of them the shadow segments take is known after neePDF
+                x.v1 = normalized_uint(g.next_i());
+                x.v2 = normalized_uint(g.next_i());
+                b.aux[i] = x;
+                c.thr_hit[i] = thr;
+                hit = 1;
+            }
+        }
+        a.alive[i] = hit;
     }
-    a.emission[i] = L;
+    b.want_light[i] = wl;
+    b.want_phase[i] = wp;
+    b.want_pdf_normal[i] = wn;
+}
+
+__global__ void __launch_bounds__(256) k_nee_paths_shade(SceneConst sc, gpis_surface_s sf, size_t n_samples, int bounce, int max_bounces, PathArrays a,
+                                                         NeeArrays b, NeePathArrays c)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_samples) return;
+    uint8_t gl = 0, gp = 0;
+    if (a.alive[i]) {       // hit at this bounce
+        const gpis_seg_out o = a.seg[i];
+        const gpis_ray_in ray = a.rays[i];
+        const NeeAux x = b.aux[i];
+        if (b.want_light[i] || b.want_phase[i])
+            nee_shade_sample(sc, sf, ray, o, x, i, b, gl, gp);
+        c.segs[i] += (uint32_t)gl + (uint32_t)gp;
+        Pcg32 g;
+        g.state = a.rng[i];
+        for (int k = 0; k < (int)gl + (int)gp; ++k)     // one jitter per shadow segment that is marched
+            (void)g.next_i();
+        // the bounce: no Russian roulette, no neePDF of the mirror direction (the reference's value is unused)
+        const float thr = c.thr_hit[i] * x.F;
+        a.throughput[i] = thr;
+        float t0, t1;
+        const V3 w = v3(x.w[0], x.w[1], x.w[2]);
+        bool alive = !(thr == 0.0f) && sphere_chord(v3(o.p[0], o.p[1], o.p[2]), w, sc.s.bound_radius, t0, t1) && bounce + 2 < max_bounces;
+        if (alive) {
+            gpis_ray_in next = scene_next_ray(ray, o);
+            next.dir[0] = w.x; next.dir[1] = w.y; next.dir[2] = w.z;
+            next.far_t = t1;
+            next.u_jitter = normalized_uint(g.next_i());
+            a.rays[i] = next;
+        }
+        a.rng[i] = g.state;
+        a.alive[i] = alive ? 1 : 0;
+    }
+    b.go_light[i] = gl;
+    b.go_phase[i] = gp;
+}
+
+// E = E + thr * L.  A hit without a shadow segment has L = 0 and leaves E as it is.
+__global__ void __launch_bounds__(256) k_nee_paths_gather(float cap_radiance, size_t n_samples, PathArrays a, NeeArrays b, NeePathArrays c)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_samples) return;
+    if (b.go_light[i] || b.go_phase[i])
+        a.emission[i] = a.emission[i] + c.thr_hit[i] * nee_gather_sample(cap_radiance, i, b);
+}
+
+__global__ void __launch_bounds__(256) k_nee_paths_segs(SceneConst sc, size_t first_pixel, size_t n_pixels, const uint32_t *__restrict__ segs,
+                                                        uint32_t *__restrict__ seg_count)
+{
+    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_pixels) return;
+    const uint32_t spp = sc.s.spp_count;
+    uint32_t acc = 0;
+    for (uint32_t k = 0; k < spp; ++k)
+        acc += segs[j * spp + k];
+    seg_count[scene_pixel(sc.s, first_pixel + j)] += acc;
 }
 
 // ======================================================================================
@@ -2333,23 +2441,25 @@ extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, 
     return ws_release(m, 0, st);
 }
 
-extern "C" int gpis_render_scene_s_nee(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_s *surf, float *radiance_sum, void *stream)
+// The frames of the two conductor NEE / MIS drivers.  max_path_bounces == 0: the single-interaction estimator of
+// gpis_render_scene_s_nee; otherwise the bounce loop of gpis_render_scene_s_nee_paths over the same stages.
+static int nee_frames(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_s *surf, int max_path_bounces, float *radiance_sum, uint32_t *seg_count,
+                      hipStream_t st)
 {
-    CHECK_ARGS(std_handle(m) && s && surf && radiance_sum);
-    CHECK_ARGS(scene_args_ok(s));
-    CHECK_ARGS(surf->cap_cos < 1.0f && surf->cap_cos > -1.0f);
+    const bool paths = max_path_bounces > 0;
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = (hipStream_t)stream;
     SceneConst sc = make_scene_const(s);
     const size_t total_pixels = scene_rows(*s) * s->width;
-    // ≈ 800 B per sample (rays, results, the two query records, two shadow rays, masks): the largest chunk the device can hold,
-    // starting from the whole frame (2^27 samples ≈ 106 GB for C2's 1920x1080x64) — every launch ends in a tail of half-empty waves
+    // ≈ 800 B per sample (rays, results, the two query records, two shadow rays, masks; the path driver adds 8 B): the largest chunk
+    // the device can hold, starting from the whole frame (2^27 samples ≈ 106 GB for C2's 1920x1080x64) — every launch ends in a tail
+    // of half-empty waves
     PathArrays a;
     NeeArrays b;
+    NeePathArrays c;
     size_t chunk_pixels = 0, ns_max = 0, off = 0;
     size_t o_rays = 0, o_seg = 0, o_rng = 0, o_thr = 0, o_em = 0, o_alive = 0, o_coeff = 0, o_qh = 0, o_qn = 0, o_aux = 0, o_shl = 0, o_shp = 0;
-    size_t o_ph = 0, o_gh = 0, o_pn = 0, o_cl = 0, o_cp = 0, o_f[7] = {0};
+    size_t o_ph = 0, o_gh = 0, o_pn = 0, o_cl = 0, o_cp = 0, o_f[7] = {0}, o_th = 0, o_segs = 0;
     int rc = GPIS_OK;
     for (int l = chunk_log2(m, 27);; --l) {
         chunk_pixels = ((size_t)1 << l) / s->spp_count;
@@ -2364,6 +2474,7 @@ extern "C" int gpis_render_scene_s_nee(gpis_medium *m, const gpis_scene_s *s, co
         o_aux = carve(ns_max * sizeof(NeeAux)); o_shl = carve(ns_max * sizeof(gpis_ray_in)); o_shp = carve(ns_max * sizeof(gpis_ray_in));
         o_ph = carve(ns_max * 4); o_gh = carve(ns_max * 12); o_pn = carve(ns_max * 4); o_cl = carve(ns_max * 4); o_cp = carve(ns_max * 4);
         for (int k = 0; k < 7; ++k) o_f[k] = carve(ns_max);
+        if (paths) { o_th = carve(ns_max * 4); o_segs = carve(ns_max * 4); }
         if (try_stage(m, 3, off))
             break;
         if (l <= 20) return set_err(GPIS_ERR_DEVICE, "NEE driver: no memory for a 1 Mi-sample workspace");
@@ -2379,29 +2490,74 @@ extern "C" int gpis_render_scene_s_nee(gpis_medium *m, const gpis_scene_s *s, co
     b.contrib_light = (float *)(ws + o_cl); b.contrib_phase = (float *)(ws + o_cp);
     b.want_light = (uint8_t *)(ws + o_f[0]); b.want_phase = (uint8_t *)(ws + o_f[1]); b.want_pdf_normal = (uint8_t *)(ws + o_f[2]);
     b.go_light = (uint8_t *)(ws + o_f[3]); b.go_phase = (uint8_t *)(ws + o_f[4]); b.vis_light = (uint8_t *)(ws + o_f[5]); b.vis_phase = (uint8_t *)(ws + o_f[6]);
+    c.thr_hit = (float *)(ws + o_th); c.segs = (uint32_t *)(ws + o_segs);
+    // the light and the phase estimator of the hits of one march: neePDF / neeGrad between set-up and shade, then the shadow marches
+    auto nee_queries = [&](size_t ns) -> int {
+        ProfScope prof(m, 2, st);
+        launch::nee(nee_instance(m->host_model), m->d_model, ns, b.q_half, b.pdf_half, b.grad_half, m->d_counters, b.want_light, st);
+        if (int r = launch_check("k_nee")) return r;
+        launch::nee(nee_instance(m->host_model), m->d_model, ns, b.q_normal, b.pdf_normal, nullptr, m->d_counters, b.want_pdf_normal, st);
+        return launch_check("k_nee");
+    };
+    auto shadow_marches = [&](size_t ns, int hint) -> int {
+        if (int r = transmittance_impl(m, ns, b.shadow_light, b.vis_light, b.go_light, st, hint)) return r;
+        return transmittance_impl(m, ns, b.shadow_phase, b.vis_phase, b.go_phase, st, hint);
+    };
     for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
         size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
         size_t ns = np * s->spp_count;
         k_paths_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, p0, ns, a);
         if ((rc = launch_check("k_paths_begin"))) return rc;
-        if ((rc = sample_distance_impl(m, ns, a.rays, a.seg, b.coeff, a.alive, st))) return rc;
-        k_nee_setup<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b);
-        if ((rc = launch_check("k_nee_setup"))) return rc;
-        {
-            ProfScope prof(m, 2, st);
-            launch::nee(nee_instance(m->host_model), m->d_model, ns, b.q_half, b.pdf_half, b.grad_half, m->d_counters, b.want_light, st);
-            if ((rc = launch_check("k_nee"))) return rc;
-            launch::nee(nee_instance(m->host_model), m->d_model, ns, b.q_normal, b.pdf_normal, nullptr, m->d_counters, b.want_pdf_normal, st);
-            if ((rc = launch_check("k_nee"))) return rc;
+        if (!paths) {
+            if ((rc = sample_distance_impl(m, ns, a.rays, a.seg, b.coeff, a.alive, st))) return rc;
+            k_nee_setup<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b);
+            if ((rc = launch_check("k_nee_setup"))) return rc;
+            if ((rc = nee_queries(ns))) return rc;
+            k_nee_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b);
+            if ((rc = launch_check("k_nee_shade"))) return rc;
+            if ((rc = shadow_marches(ns, MARCH_COHERENT))) return rc;
+            k_nee_gather<<<grid_of(ns, 256), 256, 0, st>>>(surf->cap_radiance, ns, a, b);
+            if ((rc = launch_check("k_nee_gather"))) return rc;
+        } else {
+            HIP_TRY(hipMemsetAsync(c.segs, 0, ns * sizeof(uint32_t), st));
+            // the segment of bounce max-1 cannot contribute (no direct lighting there, TraceBase.cpp:546, and the light seen directly is
+            // never added), so it is not marched.  Dead paths stay masked in sample order; the segments after the first are scattered.
+            for (int bounce = 0; bounce + 1 < max_path_bounces; ++bounce) {
+                const int hint = bounce > 0 ? MARCH_SCATTERED : MARCH_COHERENT;
+                if ((rc = sample_distance_impl(m, ns, a.rays, a.seg, b.coeff, a.alive, st, hint))) return rc;
+                k_nee_paths_setup<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b, c);
+                if ((rc = launch_check("k_nee_paths_setup"))) return rc;
+                if ((rc = nee_queries(ns))) return rc;
+                k_nee_paths_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, bounce, max_path_bounces, a, b, c);
+                if ((rc = launch_check("k_nee_paths_shade"))) return rc;
+                if ((rc = shadow_marches(ns, hint))) return rc;
+                k_nee_paths_gather<<<grid_of(ns, 256), 256, 0, st>>>(surf->cap_radiance, ns, a, b, c);
+                if ((rc = launch_check("k_nee_paths_gather"))) return rc;
+            }
+            if (seg_count) {
+                k_nee_paths_segs<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, c.segs, seg_count);
+                if ((rc = launch_check("k_nee_paths_segs"))) return rc;
+            }
         }
-        k_nee_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b);
-        if ((rc = launch_check("k_nee_shade"))) return rc;
-        if ((rc = transmittance_impl(m, ns, b.shadow_light, b.vis_light, b.go_light, st))) return rc;
-        if ((rc = transmittance_impl(m, ns, b.shadow_phase, b.vis_phase, b.go_phase, st))) return rc;
-        k_nee_gather<<<grid_of(ns, 256), 256, 0, st>>>(surf->cap_radiance, ns, a, b);
-        if ((rc = launch_check("k_nee_gather"))) return rc;
         k_paths_accumulate<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, a.emission, radiance_sum);
         if ((rc = launch_check("k_paths_accumulate"))) return rc;
     }
     return ws_release(m, 0, st);
+}
+
+extern "C" int gpis_render_scene_s_nee(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_s *surf, float *radiance_sum, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && surf && radiance_sum);
+    CHECK_ARGS(scene_args_ok(s));
+    CHECK_ARGS(surf->cap_cos < 1.0f && surf->cap_cos > -1.0f);
+    return nee_frames(m, s, surf, 0, radiance_sum, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int gpis_render_scene_s_nee_paths(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_s *surf, int max_path_bounces, float *radiance_sum,
+                                             uint32_t *seg_count, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && surf && radiance_sum && max_path_bounces >= 1);
+    CHECK_ARGS(scene_args_ok(s));
+    CHECK_ARGS(surf->cap_cos < 1.0f && surf->cap_cos > -1.0f);
+    return nee_frames(m, s, surf, max_path_bounces, radiance_sum, seg_count, (hipStream_t)stream);
 }

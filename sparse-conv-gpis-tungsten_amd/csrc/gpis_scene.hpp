@@ -6,9 +6,10 @@
 //       k_fs_scene, k_fs_paths — and scene_camera_ray (direction, bounding-sphere chord, the first gpis_ray_in) — the same but
 //       k_fs_paths;
 //   hit_normal — the six shading kernels (k_scene_shade, k_paths_shade, k_ws_scene, k_ws_paths, k_fs_scene, k_fs_paths) and
-//       k_nee_setup;
+//       the set-up of the conductor NEE drivers (nee_setup_sample in gpis_hip.hip);
 //   scene_next_ray, the ray that continues a path from a hit — the Lambert shadow rays of k_scene_shade, k_ws_scene and
-//       k_fs_scene.
+//       k_fs_scene, the shadow rays of the conductor NEE drivers (nee_shade_sample) and the next path segment of
+//       k_nee_paths_shade.
 // The device helpers draw nothing, hold no barrier and branch only on their arguments: called with wave-uniform arguments they
 // return wave-uniform results (gpis_fs_scene.hpp and gpis_fs_paths.hpp rest on this).
 // Not here: the shade step of the three path kernels (k_paths_shade, k_ws_paths, k_fs_paths: Duff frame, wi / wo, next-event
