@@ -500,6 +500,8 @@ typedef enum gpis_option {
                                  //   in-wave refill as segments finish (multiple of 64; measured slower on camera rays)
     GPIS_OPT_DEFER_GRAD = 8,     // guided march (resident form): 0 (default) = the segment's gradient is evaluated at the end of the march kernel;
                                  //   1 = by a second kernel over the pending records (measured: DESIGN.md 8, the spill experiment)
+    GPIS_OPT_SCENE_EXIT_STATE = 9,   // gpis_render_scene_s, diagnostic: 0 (default) = the primary march of the resident guided form does not
+                                     //   evaluate lastVal and the gradient of a segment that exits (the driver reads neither); 1 = it does
     GPIS_OPT_COUNT_
 } gpis_option;
 typedef enum gpis_march_form { GPIS_MARCH_FORM_AUTO = 0, GPIS_MARCH_FORM_RESIDENT = 1, GPIS_MARCH_FORM_WAVE = 2 } gpis_march_form;
@@ -577,7 +579,10 @@ int gpis_reserve_scene_workspace(gpis_medium *m, const gpis_scene_s *s);
 /* Renders rows [y_begin, y_begin+y_count) × all columns × spp_count samples of scene S and
  * ACCUMULATES sum-of-radiance into radiance_sum[height*width] (float, device pointer,
  * indexed y*width+x; caller divides by total spp).  Runs primary sampleDistance, shading,
- * one shadow transmittance per hit.  hit_count (device, may be NULL) accumulates per-pixel hits. */
+ * one shadow transmittance per hit.  hit_count (device, may be NULL) accumulates per-pixel hits.
+ * The driver's internal segment records of primary rays that EXIT carry no state (last_val = 0, aniso = 0: lastVal and the
+ * gradient at farT are not evaluated, GPIS_OPT_SCENE_EXIT_STATE), since the estimator reads only ok / exited of them; the records
+ * gpis_sample_distance_batch returns are complete as ever.  Image and hit counts do not depend on the option. */
 int gpis_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radiance_sum,
                         uint32_t *hit_count, void *stream);
 

@@ -494,7 +494,8 @@ GPIS_DEV float mean_approx(const DevModel &M, V3 p, float perr, float &slack)
 // Exact evaluations are cooperative (coop_evaluate_value); parked lanes are served in clusters whose
 // grid cells span at most 2 per axis, so the evaluator always takes its coherent path.
 constexpr int32_t kSegPending = 0x7FFFFFF0;     // gpis_seg_out::ok of a record that waits for its gradient (k_guided_range_grad)
-enum GPhase : int { G_INIT = 0, G_MARCH = 1, X_F0 = 2, X_CUR = 3, X_PREV = 4, X_REFINE = 5, X_FINAL = 6, G_GRAD = 7, G_DONE = 8 };
+enum GPhase : int { G_INIT = 0, G_MARCH = 1, X_F0 = 2, X_CUR = 3, X_PREV = 4, X_REFINE = 5, X_FINAL = 6, G_GRAD = 7, G_DONE = 8,
+                    G_EXIT = 9 };     // EXIT_STATE = false only: done, the segment left through farT and its record carries no state
 
 GPIS_DEV V3 grid_point(const DevModel &M, const GuideField &F, V3 p, const Frame &coord)
 {
@@ -634,7 +635,11 @@ GPIS_DEV int guide_sign_at(const DevModel &M, const GuideField &F, const GuideRa
 // DEFER_GRAD (sampleDistance only; GPIS_OPT_DEFER_GRAD): the segment's gradient evaluation is left to a second kernel — the record is
 // written with ok = kSegPending and k_guided_range_grad completes it — so that the march kernel does not carry the gradient
 // evaluator (the spill experiment of DESIGN.md 8).
-template <bool WANT_SAMPLE, bool SMALLARG, bool DEFER_GRAD = false>
+// EXIT_STATE = false (sampleDistance only; the Lambert frame driver's primary march): a segment that reaches farT without a crossing
+// ends there as it does in the transmittance instance — neither lastVal at farT nor the gradient there is evaluated, and its record
+// is the exit record (ok = 1, exited = 1, t = farT) with last_val = 0 and aniso = 0.  A caller that only asks "hit or exit?" never
+// reads either; the batch ABI returns both and keeps EXIT_STATE = true.
+template <bool WANT_SAMPLE, bool SMALLARG, bool DEFER_GRAD = false, bool EXIT_STATE = true>
 GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideField &F, FastLds &lds, bool valid,
                            const gpis_ray_in *__restrict__ rayp, gpis_seg_out *out, bool &visible, uint32_t &n_eval, uint32_t &n_guide)
 {
@@ -742,6 +747,14 @@ GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideFie
             if (!WANT_SAMPLE && phase == X_FINAL) {
                 hit = false;                // transmittance: the segment exits, lastVal is not part of the result
                 phase = G_DONE;
+            }
+            if constexpr (WANT_SAMPLE && !EXIT_STATE) {
+                if (phase == X_FINAL) {
+                    hit = false;
+                    t = (double)farT;
+                    last_val = 0.f;
+                    phase = G_EXIT;
+                }
             }
             const bool stepping = phase == G_INIT || phase == G_MARCH;
             const unsigned long long step_mask = __ballot(stepping);
@@ -900,7 +913,10 @@ GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideFie
     FSTAT(19, FCLK() - clk_g0);
     if (!valid)
         return;
-    finish_sample_distance(M, rayp, pos, dir, farT, early_ok, want_grad, hit, t, last_val, gp, g, out);
+    if constexpr (EXIT_STATE)
+        finish_sample_distance(M, rayp, pos, dir, farT, early_ok, want_grad, hit, t, last_val, gp, g, out);
+    else
+        finish_sample_distance(M, rayp, pos, dir, farT, early_ok, want_grad || phase == G_EXIT, hit, t, last_val, gp, g, out);
 }
 
 struct GuideCounters { unsigned long long n_guide; };
@@ -918,6 +934,32 @@ __global__ void __launch_bounds__(kFastBlock, GPIS_GUIDE_OCC) k_guided_sample_di
     uint32_t n_eval = 0, n_guide = 0;
     bool vis;
     guided_march<true, SMALLARG>(*Mp, T, *Fp, lds, valid, rays + (valid ? i : 0), out + (valid ? i : 0), vis, n_eval, n_guide);
+    if (valid && coeff) {
+        gpis_cond_coeff c;
+        memset(&c, 0, sizeof c);
+        c.n_evals = n_eval;
+        coeff[i] = c;
+    }
+    fast_flush_counters(cnt, n_eval, valid ? 1u : 0u);
+    unsigned long long gsum = n_guide;
+    for (int off = 32; off > 0; off >>= 1) gsum += __shfl_down(gsum, off, 64);
+    if ((threadIdx.x & 63) == 0 && gsum) atomicAdd(guide_cnt, gsum);
+}
+
+// the same march without the exit state (guided_march: EXIT_STATE = false) — the primary march of gpis_render_scene_s
+template <bool SMALLARG>
+__global__ void __launch_bounds__(kFastBlock, GPIS_GUIDE_OCC) k_guided_sample_distance_noexit(const DevModel *__restrict__ Mp, FastTable T, const GuideField *__restrict__ Fp, size_t n,
+                                                                                            const gpis_ray_in *__restrict__ rays, gpis_seg_out *__restrict__ out,
+                                                                                            gpis_cond_coeff *__restrict__ coeff, const uint8_t *__restrict__ mask,
+                                                                                            Counters *cnt, unsigned long long *guide_cnt)
+{
+    __shared__ FastLds lds;
+    fast_lds_init(lds);
+    size_t i = (size_t)blockIdx.x * kFastBlock + threadIdx.x;
+    const bool valid = i < n && (!mask || mask[i]);
+    uint32_t n_eval = 0, n_guide = 0;
+    bool vis;
+    guided_march<true, SMALLARG, false, false>(*Mp, T, *Fp, lds, valid, rays + (valid ? i : 0), out + (valid ? i : 0), vis, n_eval, n_guide);
     if (valid && coeff) {
         gpis_cond_coeff c;
         memset(&c, 0, sizeof c);

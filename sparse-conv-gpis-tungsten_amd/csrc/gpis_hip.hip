@@ -1164,6 +1164,8 @@ extern "C" int gpis_create(const gpis_params *params, int device, gpis_medium **
         if (const char *e = getenv("GPIS_DEFER_GRAD")) m->opt[GPIS_OPT_DEFER_GRAD] = e[0] != '0';
         m->opt[GPIS_OPT_SOLO_MAX] = -1;
         if (const char *e = getenv("GPIS_SOLO_MAX")) m->opt[GPIS_OPT_SOLO_MAX] = atoll(e);
+        m->opt[GPIS_OPT_SCENE_EXIT_STATE] = 0;
+        if (const char *e = getenv("GPIS_SCENE_EXIT_STATE")) m->opt[GPIS_OPT_SCENE_EXIT_STATE] = e[0] != '0';
         m->opt[GPIS_OPT_CHUNK_LOG2] = 0;
         if (const char *e = getenv("GPIS_CHUNK_LOG2")) { int l = atoi(e); m->opt[GPIS_OPT_CHUNK_LOG2] = l < 16 ? 16 : (l > 28 ? 28 : l); }
     }
@@ -1442,8 +1444,10 @@ static int lane_instance(const DevModel &H)
 }
 
 static int sample_distance_impl(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, gpis_cond_coeff *coeff,
-                                const uint8_t *mask, hipStream_t s, int hint = MARCH_COHERENT)
+                                const uint8_t *mask, hipStream_t s, int hint = MARCH_COHERENT, bool exit_state = true)
 {
+    // exit_state = false (gpis_render_scene_s only): the caller reads nothing but ok / exited of a segment that left through farT, so the
+    // resident guided march may skip lastVal and the gradient there (guided_march, EXIT_STATE); every other form evaluates them as ever
     if (n == 0) return GPIS_OK;
     ProfScope prof(m, 0, s);
     if (m->guide.enabled && wave_march_selected(m, hint))
@@ -1461,6 +1465,10 @@ static int sample_distance_impl(gpis_medium *m, size_t n, const gpis_ray_in *ray
             if (rc) return rc;
             launch::range_grad(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->guide, n, rays, out, coeff, mask, m->d_counters, s);
             return launch_check("k_guided_range_grad");
+        }
+        if (!exit_state) {
+            launch::guided_sample_distance_noexit(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->d_guide, n, rays, out, coeff, mask, m->d_counters, m->d_guide_cnt, s);
+            return launch_check("k_guided_sample_distance_noexit");
         }
         launch::guided_sample_distance(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->d_guide, n, rays, out, coeff, mask, m->d_counters, m->d_guide_cnt, s);
         return launch_check("k_guided_sample_distance");
@@ -1536,7 +1544,7 @@ extern "C" int gpis_set_option(gpis_medium *m, int option, long long value)
     switch (option) {
     case GPIS_OPT_MARCH_FORM: CHECK_ARGS(value >= GPIS_MARCH_FORM_AUTO && value <= GPIS_MARCH_FORM_WAVE); break;
     case GPIS_OPT_WAVE_TAIL: CHECK_ARGS(value >= 0); break;
-    case GPIS_OPT_PATHS_SORT: case GPIS_OPT_PATHS_PRESORT: case GPIS_OPT_PERSISTENT: case GPIS_OPT_DEFER_GRAD: CHECK_ARGS(value == 0 || value == 1); break;
+    case GPIS_OPT_PATHS_SORT: case GPIS_OPT_PATHS_PRESORT: case GPIS_OPT_PERSISTENT: case GPIS_OPT_DEFER_GRAD: case GPIS_OPT_SCENE_EXIT_STATE: CHECK_ARGS(value == 0 || value == 1); break;
     case GPIS_OPT_CHUNK_LOG2: CHECK_ARGS(value == 0 || (value >= 16 && value <= 28)); break;
     case GPIS_OPT_SOLO_MAX: CHECK_ARGS(value >= -1 && value <= 64); break;
     case GPIS_OPT_RANGE_LEN: CHECK_ARGS(value >= 0 && value <= (1 << 24) && value % 64 == 0); break;
@@ -2261,7 +2269,8 @@ extern "C" int gpis_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float 
         if ((rc = launch_check("k_scene_primary"))) return rc;
         if ((rc = ensure_stage(m, 5, W.b_seg, true))) return rc;
         gpis_seg_out *seg = (gpis_seg_out *)m->stage[5];
-        if ((rc = sample_distance_impl(m, ns, prim, seg, nullptr, v1, st))) return rc;
+        // k_scene_shade reads only ok / exited of a segment that exits: its lastVal and gradient are not evaluated (GPIS_OPT_SCENE_EXIT_STATE)
+        if ((rc = sample_distance_impl(m, ns, prim, seg, nullptr, v1, st, MARCH_COHERENT, m->opt[GPIS_OPT_SCENE_EXIT_STATE] != 0))) return rc;
         if ((rc = ensure_stage(m, 6, W.b_shadow, true))) return rc;
         char *ws6 = (char *)m->stage[6];
         gpis_ray_in *sh = prim;
