@@ -652,6 +652,35 @@ int gpis_render_scene_s_nee_paths(gpis_medium *m, const gpis_scene_s *s, const g
 int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo,
                               float *radiance_sum, void *stream);
 
+/* gpis_render_scene_s_paths carried in RGB, with the medium's emission (MediumSample.emission, GPM.cpp:317): the image the
+ * per-channel quantities of the medium give — gpis_seg_out.weight[3] (mean colour, sigma_s / sigma_t per channel) and the mean's
+ * "emission" — under PathTracer::traceSample (PathTracer.cpp:72-73: emission += throughput * sample.emission; throughput *=
+ * sample.weight).  Accepts the handles, rows, tile-row shards, spp ranges, chunking and stream of gpis_render_scene_s_paths;
+ * GPIS_ERR_INVALID_ARG (nothing is written) for max_path_bounces < 1, a NULL albedo (host pointer, 3 floats) or radiance_sum3, a
+ * row range outside the image, a bad shard, a weight-space handle.
+ * Per sample, operation for operation in float with contraction off: the draws jx, jy, u_march and the camera ray of
+ * gpis_render_scene_s_paths; thr[c] = 1, em[c] = 0.  Let E = "mean_emission is enabled" and B = max_path_bounces.  For b = 0, 1, ...:
+ *   1. sampleDistance with segment word b.  The last segment marched is b = B-2 when !E (the loop of gpis_render_scene_s_paths)
+ *      and b = B-1 when E: that segment can only add its hit's emission; no NEE and no bounce follow it.
+ *   2. !ok ends the path and adds nothing.
+ *   3. On a hit (ok && !exited) when E: e = emission(ro + rd * t), ro the ray position widened to double, rd the direction
+ *      normalised in double, t = gpis_seg_out.t — the point and the evaluation of gpis_mean_color_emission_*; e rounded to float;
+ *      em[c] = em[c] + (thr[c] * e[c]) with thr BEFORE the weight and the product rounded to float on its own.
+ *   4. thr[c] = thr[c] * weight[c]; `exited` ends the path.
+ *   5. For b < B-1: next-event estimation and the cosine bounce exactly as gpis_render_scene_s_paths (same conditions, draws and
+ *      order of draws) with f[c] = albedo[c] * (1.0f/3.1415926536f) * wo.z and contrib[c] = thr[c] * (f[c] * light_radiance); after
+ *      the shadow transmittance em[c] = em[c] + (visible ? contrib[c] : 0); then thr[c] *= albedo[c].  Within a bounce the emission
+ *      term is added before the NEE term.
+ * Each pixel's sum of em[c], taken per channel in sample order from zero, is ACCUMULATED into radiance_sum3[3*(y*width+x)+c]
+ * (device pointer, 3*height*width floats) once per chunk of samples, and per pixel the segments marched (path plus shadow
+ * segments) into seg_count[height*width] (device pointer; may be NULL).  Image and counts depend neither on how a frame is cut
+ * into calls or chunks nor on GPIS_OPT_PATHS_SORT / PATHS_PRESORT / MARCH_FORM / PERSISTENT / CHUNK_LOG2.
+ * Consequences: with !E and albedo[0] == albedo, channel 0 is gpis_render_scene_s_paths bit for bit, for every medium; with E,
+ * max_path_bounces = 1 renders first-hit emission (with !E it adds zeros and marches nothing).  NaN components a field returns
+ * propagate as float arithmetic gives them.  Asynchronous on `stream`. */
+int gpis_render_scene_s_paths_rgb(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, const float albedo[3],
+                                  float *radiance_sum3, uint32_t *seg_count, void *stream);
+
 /* ---- weight-space GP medium (WeightSpaceGaussianProcessMedium.cpp, WeightSpaceGaussianProcess.cpp) --------------------
  * The field of one realization is  f(p) = sqrt(cov(p,p)) * (sqrt(2/N) * sum_i w_i cos((d_i . p) * omega_i + phi_i)) + mean(p)
  * with N random Fourier features of the squared-exponential covariance (WSG:120-127, 160-240).  A realization is fixed by the

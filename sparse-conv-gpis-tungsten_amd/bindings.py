@@ -332,7 +332,7 @@ class GpisLib:
         "gpis_get_counters", "gpis_reset_counters", "gpis_set_profiling", "gpis_get_kernel_profile",
         "gpis_set_batch_order", "gpis_set_option", "gpis_get_option", "gpis_build_guide", "gpis_drop_guide", "gpis_get_guide_info", "gpis_get_guide_steps", "gpis_guide_selfcheck", "gpis_guide_raycheck",
         "gpis_set_variance_grid", "gpis_default_scene_s", "gpis_reserve_scene_workspace", "gpis_render_scene_s", "gpis_render_scene_s_paths", "gpis_render_scene_s_nee",
-        "gpis_render_scene_s_nee_paths",
+        "gpis_render_scene_s_nee_paths", "gpis_render_scene_s_paths_rgb",
         "gpis_ws_default_params", "gpis_ws_create", "gpis_ws_sample_distance_batch", "gpis_ws_transmittance_batch",
         "gpis_ws_sample_distance_host", "gpis_ws_transmittance_host", "gpis_ws_eval_batch", "gpis_ws_basis_batch",
         "gpis_ws_get_counters", "gpis_ws_reset_counters", "gpis_ws_render_scene_s", "gpis_ws_render_scene_s_paths",
@@ -414,6 +414,7 @@ class GpisLib:
         L.gpis_render_scene_s_paths.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
         L.gpis_render_scene_s_nee.argtypes = [vp, vp, vp, vp, vp]
         L.gpis_render_scene_s_nee_paths.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+        L.gpis_render_scene_s_paths_rgb.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         L.gpis_ws_default_params.argtypes = [vp]
         L.gpis_ws_default_params.restype = None
         L.gpis_ws_create.argtypes = [vp, vp, i32, ctypes.POINTER(vp)]
@@ -629,6 +630,26 @@ class Medium:
                                                               ctypes.c_void_p(d_seg.data_ptr()) if want_segs else None, None), "gpis_render_scene_s_nee_paths")
         torch.cuda.synchronize(dev)
         rad = d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy()
+        if not want_segs:
+            return rad
+        return rad, d_seg.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
+
+    def render_scene_s_paths_rgb(self, scene, max_bounces, albedo, want_segs=False):
+        """One call of the RGB multi-bounce path driver with the medium's emission (gpis_render_scene_s_paths_rgb) into zeroed
+        device buffers: the float32 sum-of-radiance image (height, width, 3) of the rows, shard and samples `scene` selects, and
+        per pixel the segments marched (path plus shadow) when asked.  A scalar `albedo` is broadcast to the three channels."""
+        import torch
+        scene = np.array(scene, dtype=SCENE_S).reshape(())
+        alb = np.ascontiguousarray(np.broadcast_to(np.asarray(albedo, dtype=np.float32), (3,)))
+        hgt, wid = int(scene["height"]), int(scene["width"])
+        dev = torch.device("cuda", self.device)
+        d_rad = torch.zeros(max(3 * hgt * wid, 1), dtype=torch.float32, device=dev)
+        d_seg = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_segs else None
+        torch.cuda.synchronize(dev)
+        self.L.check(self.L.lib.gpis_render_scene_s_paths_rgb(self.h, _ptr(scene), int(max_bounces), _ptr(alb), ctypes.c_void_p(d_rad.data_ptr()),
+                                                              ctypes.c_void_p(d_seg.data_ptr()) if want_segs else None, None), "gpis_render_scene_s_paths_rgb")
+        torch.cuda.synchronize(dev)
+        rad = d_rad.cpu().numpy()[:3 * hgt * wid].reshape(hgt, wid, 3).copy()
         if not want_segs:
             return rad
         return rad, d_seg.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()

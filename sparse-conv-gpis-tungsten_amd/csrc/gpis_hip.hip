@@ -2353,14 +2353,24 @@ extern "C" int gpis_fs_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *
                     });
 }
 
-extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo, float *radiance_sum, void *stream)
+// The frame loop of the two Lambert path drivers (gpis_render_scene_s_paths, gpis_render_scene_s_paths_rgb): chunks of samples, per
+// bounce the regrouping of the secondary segments, the march, the driver's shade kernel, the shadow march and the driver's NEE add.
+// The loop owns the arrays the marches read and write (PathsFrame); the driver carves its own path state into the same workspace
+// (`state`, called before the allocation with the carving function and the chunk's samples) and takes its pointers from it
+// (`bind`).  Segments 0 .. n_marched - 1 are marched; next-event estimation follows the first n_nee of them.  Every callback
+// launches and returns its launch_check.
+struct PathsFrame {
+    char *ws;                          // stage[3]: the driver's arrays lie at the offsets its `state` carved
+    gpis_ray_in *rays, *shadow;        // current segment of every path; the shadow segments of the bounce (by batch slot)
+    gpis_seg_out *seg;
+    uint8_t *alive, *nee, *vis;
+};
+template <typename State, typename Bind, typename Begin, typename Shade, typename NeeAdd, typename Finish>
+static int lambert_paths_frames(gpis_medium *m, const gpis_scene_s *s, int n_marched, int n_nee, hipStream_t st, State state, Bind bind, Begin begin,
+                                Shade shade, NeeAdd nee_add, Finish finish)
 {
-    CHECK_ARGS(std_handle(m) && s && radiance_sum && max_path_bounces >= 1);
-    CHECK_ARGS(scene_args_ok(s));
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = (hipStream_t)stream;
-    SceneConst sc = make_scene_const(s);
     const size_t total_pixels = scene_rows(*s) * s->width;
     size_t chunk_pixels = ((size_t)1 << chunk_log2(m, 25)) / s->spp_count;
     if (chunk_pixels < 1) chunk_pixels = 1;
@@ -2369,10 +2379,10 @@ extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, 
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     size_t o_rays = carve(ns_max * sizeof(gpis_ray_in)), o_seg = carve(ns_max * sizeof(gpis_seg_out)), o_sh = carve(ns_max * sizeof(gpis_ray_in));
-    size_t o_rng = carve(ns_max * 8), o_thr = carve(ns_max * 4), o_em = carve(ns_max * 4), o_con = carve(ns_max * 4);
+    state(carve, ns_max);
     size_t o_alive = carve(ns_max), o_nee = carve(ns_max), o_vis = carve(ns_max);
     // regrouping of secondary segments (GPIS_PATHS_SORT=0 keeps the sample order: results are identical)
-    const bool regroup = m->opt[GPIS_OPT_PATHS_SORT] != 0 && max_path_bounces > 2;
+    const bool regroup = m->opt[GPIS_OPT_PATHS_SORT] != 0 && n_marched > 1;
     const bool presort = m->opt[GPIS_OPT_PATHS_PRESORT] != 0;
     size_t sort_temp_bytes = 0;
     size_t o_keys = 0, o_vals = 0, o_keys2 = 0, o_order = 0, o_rsorted = 0, o_live = 0, o_temp = 0, o_order2 = 0, o_live2 = 0;
@@ -2393,19 +2403,16 @@ extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, 
     uint32_t *order2 = (uint32_t *)(ws + o_order2);
     const DevModel &H = m->host_model;
     const float cell_size = H.iso3d ? (H.radius_iso > 0.f ? H.radius_iso : H.kernel_scale) : (H.radius_world > 0.f ? H.radius_world : 0.1f);
-    PathArrays a;
-    a.rays = (gpis_ray_in *)(ws + o_rays); a.seg = (gpis_seg_out *)(ws + o_seg); a.shadow = (gpis_ray_in *)(ws + o_sh);
-    a.rng = (uint64_t *)(ws + o_rng);
-    a.throughput = (float *)(ws + o_thr); a.emission = (float *)(ws + o_em); a.contrib = (float *)(ws + o_con);
-    a.alive = (uint8_t *)(ws + o_alive); a.nee = (uint8_t *)(ws + o_nee); a.vis = (uint8_t *)(ws + o_vis);
+    PathsFrame f;
+    f.ws = ws;
+    f.rays = (gpis_ray_in *)(ws + o_rays); f.seg = (gpis_seg_out *)(ws + o_seg); f.shadow = (gpis_ray_in *)(ws + o_sh);
+    f.alive = (uint8_t *)(ws + o_alive); f.nee = (uint8_t *)(ws + o_nee); f.vis = (uint8_t *)(ws + o_vis);
+    bind(f);
     for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
         size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
         size_t ns = np * s->spp_count;
-        k_paths_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, p0, ns, a);
-        if ((rc = launch_check("k_paths_begin"))) return rc;
-        // the segment of bounce max-1 cannot contribute (no NEE there, TraceBase.cpp:546, and the
-        // light is a Dirac delta), so it is not traced
-        for (int bounce = 0; bounce + 1 < max_path_bounces; ++bounce) {
+        if ((rc = begin(p0, ns))) return rc;
+        for (int bounce = 0; bounce < n_marched; ++bounce) {
             // primary segments are coherent as generated (consecutive spp of a pixel); later ones are regrouped
             // Secondary segments are regrouped here by start cell (compaction + locality of the guide steps;
             // GPIS_PATHS_PRESORT=0 skips it when the wavefront march runs, which regroups the exact work
@@ -2425,29 +2432,111 @@ extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, 
                 k_paths_gather<<<grid_of(ns, 256), 256, 0, st>>>(ns, keys2, ord, src, dst, live_out);
                 return launch_check("k_paths_gather");
             };
-            if (sorted && (rc = regroup_batch(a.rays, a.alive, order, rays_sorted, live_sorted))) return rc;
-            const gpis_ray_in *rays_in = sorted ? rays_sorted : a.rays;
-            const uint8_t *live = sorted ? live_sorted : a.alive;
-            if ((rc = sample_distance_impl(m, ns, rays_in, a.seg, nullptr, live, st, hint))) return rc;
-            k_paths_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, ns, bounce, max_path_bounces, albedo, a, sorted ? order : nullptr, rays_in,
-                                                           sorted ? live_sorted : nullptr);
-            if ((rc = launch_check("k_paths_shade"))) return rc;
+            if (sorted && (rc = regroup_batch(f.rays, f.alive, order, rays_sorted, live_sorted))) return rc;
+            const gpis_ray_in *rays_in = sorted ? rays_sorted : f.rays;
+            const uint8_t *live = sorted ? live_sorted : f.alive;
+            if ((rc = sample_distance_impl(m, ns, rays_in, f.seg, nullptr, live, st, hint))) return rc;
+            if ((rc = shade(bounce, ns, sorted ? order : nullptr, rays_in, sorted ? live_sorted : nullptr))) return rc;
+            if (bounce >= n_nee)
+                continue;
             if (sorted) {
                 // the shadow segments share one direction but start where the bounce segments ended: regroup
                 // them by their own lattice cells (the bounce batch's copy of the rays is free again)
-                if ((rc = regroup_batch(a.shadow, a.nee, order2, rays_sorted, live2))) return rc;
-                if ((rc = transmittance_impl(m, ns, rays_sorted, a.vis, live2, st, hint))) return rc;
-                k_paths_nee_add<<<grid_of(ns, 256), 256, 0, st>>>(ns, a, order, order2, live2, a.vis);
+                if ((rc = regroup_batch(f.shadow, f.nee, order2, rays_sorted, live2))) return rc;
+                if ((rc = transmittance_impl(m, ns, rays_sorted, f.vis, live2, st, hint))) return rc;
+                if ((rc = nee_add(ns, order, order2, live2))) return rc;
             } else {
-                if ((rc = transmittance_impl(m, ns, a.shadow, a.vis, a.nee, st, hint))) return rc;
-                k_paths_nee_add<<<grid_of(ns, 256), 256, 0, st>>>(ns, a, sorted ? order : nullptr, nullptr, nullptr, a.vis);
+                if ((rc = transmittance_impl(m, ns, f.shadow, f.vis, f.nee, st, hint))) return rc;
+                if ((rc = nee_add(ns, nullptr, nullptr, nullptr))) return rc;
             }
-            if ((rc = launch_check("k_paths_nee_add"))) return rc;
         }
-        k_paths_accumulate<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, a.emission, radiance_sum);
-        if ((rc = launch_check("k_paths_accumulate"))) return rc;
+        if ((rc = finish(p0, np))) return rc;
     }
     return ws_release(m, 0, st);
+}
+
+extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo, float *radiance_sum, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && radiance_sum && max_path_bounces >= 1);
+    CHECK_ARGS(scene_args_ok(s));
+    hipStream_t st = (hipStream_t)stream;
+    const SceneConst sc = make_scene_const(s);
+    size_t o_rng = 0, o_thr = 0, o_em = 0, o_con = 0;
+    PathArrays a;
+    // the segment of bounce max-1 cannot contribute (no NEE there, TraceBase.cpp:546, and the
+    // light is a Dirac delta), so it is not traced
+    return lambert_paths_frames(
+        m, s, max_path_bounces - 1, max_path_bounces - 1, st,
+        [&](auto &carve, size_t ns_max) { o_rng = carve(ns_max * 8); o_thr = carve(ns_max * 4); o_em = carve(ns_max * 4); o_con = carve(ns_max * 4); },
+        [&](const PathsFrame &f) {
+            a.rays = f.rays; a.seg = f.seg; a.shadow = f.shadow;
+            a.rng = (uint64_t *)(f.ws + o_rng);
+            a.throughput = (float *)(f.ws + o_thr); a.emission = (float *)(f.ws + o_em); a.contrib = (float *)(f.ws + o_con);
+            a.alive = f.alive; a.nee = f.nee; a.vis = f.vis;
+        },
+        [&](size_t p0, size_t ns) {
+            k_paths_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, p0, ns, a);
+            return launch_check("k_paths_begin");
+        },
+        [&](int bounce, size_t ns, const uint32_t *order, const gpis_ray_in *rays_in, const uint8_t *live) {
+            k_paths_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, ns, bounce, max_path_bounces, albedo, a, order, rays_in, live);
+            return launch_check("k_paths_shade");
+        },
+        [&](size_t ns, const uint32_t *order, const uint32_t *order2, const uint8_t *live2) {
+            k_paths_nee_add<<<grid_of(ns, 256), 256, 0, st>>>(ns, a, order, order2, live2, a.vis);
+            return launch_check("k_paths_nee_add");
+        },
+        [&](size_t p0, size_t np) {
+            k_paths_accumulate<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, a.emission, radiance_sum);
+            return launch_check("k_paths_accumulate");
+        });
+}
+
+// gpis_render_scene_s_paths in RGB with the medium's emission (gpis_paths_rgb.hpp): three planes of throughput / emission / contrib
+// and a per-sample segment count.  With mean_emission enabled the segment max_path_bounces - 1 is marched too: its hit emits, and
+// neither next-event estimation nor a bounce follows it.
+extern "C" int gpis_render_scene_s_paths_rgb(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, const float albedo[3], float *radiance_sum3,
+                                             uint32_t *seg_count, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && albedo && radiance_sum3 && max_path_bounces >= 1);
+    CHECK_ARGS(scene_args_ok(s));
+    hipStream_t st = (hipStream_t)stream;
+    const SceneConst sc = make_scene_const(s);
+    const bool emissive = m->host_model.emission.enabled != 0;
+    size_t o_rng = 0, o_thr = 0, o_em = 0, o_con = 0, o_segs = 0;
+    launch::PathsRgbArrays a;
+    return lambert_paths_frames(
+        m, s, emissive ? max_path_bounces : max_path_bounces - 1, max_path_bounces - 1, st,
+        [&](auto &carve, size_t ns_max) {
+            o_rng = carve(ns_max * 8); o_thr = carve(ns_max * 12); o_em = carve(ns_max * 12); o_con = carve(ns_max * 12); o_segs = carve(ns_max * 4);
+            a.plane = ns_max;
+        },
+        [&](const PathsFrame &f) {
+            a.rays = f.rays; a.seg = f.seg; a.shadow = f.shadow;
+            a.rng = (uint64_t *)(f.ws + o_rng);
+            a.throughput = (float *)(f.ws + o_thr); a.emission = (float *)(f.ws + o_em); a.contrib = (float *)(f.ws + o_con);
+            a.segs = (uint32_t *)(f.ws + o_segs);
+            a.alive = f.alive; a.nee = f.nee; a.vis = f.vis;
+        },
+        [&](size_t p0, size_t ns) {
+            launch::paths_rgb_begin(sc, p0, ns, a, st);
+            return launch_check("k_paths_rgb_begin");
+        },
+        [&](int bounce, size_t ns, const uint32_t *order, const gpis_ray_in *rays_in, const uint8_t *live) {
+            launch::paths_rgb_shade(m->d_model, sc, ns, bounce, max_path_bounces, emissive, albedo, a, order, rays_in, live, st);
+            return launch_check("k_paths_rgb_shade");
+        },
+        [&](size_t ns, const uint32_t *order, const uint32_t *order2, const uint8_t *live2) {
+            launch::paths_rgb_nee_add(ns, a, order, order2, live2, st);
+            return launch_check("k_paths_rgb_nee_add");
+        },
+        [&](size_t p0, size_t np) {
+            launch::paths_rgb_accumulate(sc, p0, np, a, radiance_sum3, st);
+            if (int rc = launch_check("k_paths_rgb_accumulate")) return rc;
+            if (!seg_count) return (int)GPIS_OK;
+            launch::paths_rgb_segs(sc, p0, np, a, seg_count, st);
+            return launch_check("k_paths_rgb_segs");
+        });
 }
 
 // The frames of the two conductor NEE / MIS drivers.  max_path_bounces == 0: the single-interaction estimator of

@@ -106,6 +106,25 @@ size_t fs_paths_rec_bytes();
 void fs_paths(unsigned grid, const DevModel *d_model, const SceneConst &sc, size_t first_pixel, uint32_t n_samples, int max_bounces, float albedo,
               uint32_t *next, void *recs, void *workspace, gpis_fs_state *path_slots, gpis_fs_state *shadow_slots, hipStream_t s);
 void fs_paths_sum(const SceneConst &sc, size_t first_pixel, size_t n_pixels, const void *recs, float *radiance_sum, uint32_t *seg_count, hipStream_t s);
+// ---- RGB multi-bounce paths of the sparse-convolution medium (tu_paths_rgb.hip; gpis_paths_rgb.hpp): the kernels between the marches
+struct PathsRgbArrays {                // path state of one chunk, SoA; `plane` floats per channel plane
+    gpis_ray_in *rays;                 // current segment of every path (rewritten in place at each bounce)
+    gpis_seg_out *seg;
+    gpis_ray_in *shadow;
+    uint64_t *rng;                     // PCG32 state of the sample's stream
+    float *throughput, *emission;      // 3 planes each, indexed by path
+    float *contrib;                    // 3 planes, indexed by batch slot
+    uint32_t *segs;                    // segments marched for the sample, path plus shadow
+    uint8_t *alive, *nee, *vis;
+    size_t plane;
+};
+void paths_rgb_begin(const SceneConst &sc, size_t first_pixel, size_t n_samples, const PathsRgbArrays &a, hipStream_t s);
+void paths_rgb_shade(const DevModel *d_model, const SceneConst &sc, size_t n_samples, int bounce, int max_bounces, bool emissive, const float albedo[3],
+                     const PathsRgbArrays &a, const uint32_t *order, const gpis_ray_in *rays_in, const uint8_t *live, hipStream_t s);
+void paths_rgb_nee_add(size_t n_samples, const PathsRgbArrays &a, const uint32_t *order, const uint32_t *shadow_order, const uint8_t *shadow_live,
+                       hipStream_t s);
+void paths_rgb_accumulate(const SceneConst &sc, size_t first_pixel, size_t n_pixels, const PathsRgbArrays &a, float *radiance_sum3, hipStream_t s);
+void paths_rgb_segs(const SceneConst &sc, size_t first_pixel, size_t n_pixels, const PathsRgbArrays &a, uint32_t *seg_count, hipStream_t s);
 inline unsigned grid_of(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 }   // namespace launch
