@@ -502,6 +502,9 @@ typedef enum gpis_option {
                                  //   1 = by a second kernel over the pending records (measured: DESIGN.md 8, the spill experiment)
     GPIS_OPT_SCENE_EXIT_STATE = 9,   // gpis_render_scene_s, diagnostic: 0 (default) = the primary march of the resident guided form does not
                                      //   evaluate lastVal and the gradient of a segment that exits (the driver reads neither); 1 = it does
+    GPIS_OPT_SCENE_COMPACT = 10,     // gpis_render_scene_s on the resident guided march without exit state: 1 (default) = its kernels pass
+                                     //   32-byte ray / hit records (71 B of workspace per sample); 0 = the 128 / 96-byte records of the batch
+                                     //   ABI (236 B per sample).  The same evaluations either way; environment: GPIS_SCENE_COMPACT
     GPIS_OPT_COUNT_
 } gpis_option;
 typedef enum gpis_march_form { GPIS_MARCH_FORM_AUTO = 0, GPIS_MARCH_FORM_RESIDENT = 1, GPIS_MARCH_FORM_WAVE = 2 } gpis_march_form;
@@ -569,8 +572,11 @@ void gpis_default_scene_s(gpis_scene_s *s, uint32_t width, uint32_t height, uint
  * have been created with grid_nonstationary = 1.  Not to be called while work of this handle is in flight. */
 int gpis_set_variance_grid(gpis_medium *m, const gpis_variance_grid *g, const float *voxels);
 
-/* Allocates the workspace gpis_render_scene_s needs for `s` (236 B per sample of the largest chunk the device holds: 31.3 GB for
- * a whole 1920x1080x64 frame) ahead of the first frame.  Optional: the render entry allocates on demand, each of its three arrays
+/* Allocates the workspace gpis_render_scene_s needs for `s` ahead of the first frame: 71 B per sample of the largest chunk the
+ * device holds with the compact records (the resident march, GPIS_OPT_SCENE_COMPACT: 9.5 GB for a whole 1920x1080x64 frame),
+ * 236 B per sample (31.3 GB) otherwise.  The call is meant to run beside gpis_build_guide, so it does not look at whether a guide
+ * is present yet: a medium that can carry a guide gets the guided body's size, and a handle that then renders without a guide
+ * grows the arrays on demand.  Optional: the render entry allocates on demand, each of its three arrays
  * right before the first kernel that needs it.  This entry does not take the handle's lock: call it from a second host thread
  * while gpis_build_guide runs (allocation time is per byte and overlaps the guide build's kernels) — not concurrently with a
  * render call that uses a DIFFERENT scene size on the same handle. */
@@ -582,7 +588,11 @@ int gpis_reserve_scene_workspace(gpis_medium *m, const gpis_scene_s *s);
  * one shadow transmittance per hit.  hit_count (device, may be NULL) accumulates per-pixel hits.
  * The driver's internal segment records of primary rays that EXIT carry no state (last_val = 0, aniso = 0: lastVal and the
  * gradient at farT are not evaluated, GPIS_OPT_SCENE_EXIT_STATE), since the estimator reads only ok / exited of them; the records
- * gpis_sample_distance_batch returns are complete as ever.  Image and hit counts do not depend on the option. */
+ * gpis_sample_distance_batch returns are complete as ever.  Image and hit counts do not depend on the option.
+ * Where that lean primary march runs (a guide field, the resident form, no range refill, no deferred gradient), the driver's kernels
+ * pass 32-byte ray and hit records instead of gpis_ray_in / gpis_seg_out (GPIS_OPT_SCENE_COMPACT): the camera position, the light
+ * direction and the first_scatter / bounce values of a launch are kernel arguments, the fields only per-path media read are dropped.
+ * The marches evaluate exactly what they evaluate on the full records. */
 int gpis_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radiance_sum,
                         uint32_t *hit_count, void *stream);
 

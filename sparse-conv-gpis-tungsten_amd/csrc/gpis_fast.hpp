@@ -26,6 +26,7 @@
 // reference computes and discards the gradient there: SCN.cpp:76, SCN.hpp:62).
 #pragma once
 #include "gpis_device.hpp"
+#include "gpis_scene.hpp"
 
 #pragma clang fp contract(off)
 
@@ -755,9 +756,48 @@ GPIS_DEV V3 coop_evaluate_gradient(const DevModel &M, const FastTable &T, FastLd
 
 enum Phase : int { PH_INIT = 0, PH_MARCH = 1, PH_REFINE = 2, PH_FINAL = 3, PH_GRAD = 4, PH_DONE = 5 };
 
+// ---- record policies of the march kernels: which ray record a lane loads and which segment record it stores.
+// BatchRecords: the records of the public batch ABI (gpis_ray_in, gpis_seg_out) — every *_batch / *_host entry and the full-record
+// body of the frame drivers.  The march loads these in its own text (guided_march), as it always did: the instances of the batch ABI
+// keep their code, register for register.
+struct BatchRecords {
+    using Ray = gpis_ray_in;
+    using Out = gpis_seg_out;
+    static constexpr bool kRayState = true;     // the ray carries the path's medium state (last_val, last_gp_id, last_aniso)
+    static GPIS_DEV void store(Out *out, const gpis_seg_out &o) { *out = o; }
+};
+// SceneRecords: the compact records of the Lambert frame driver (gpis_scene.hpp).  SHADOW = false: a primary ray, v = direction, the
+// camera position is uniform; SHADOW = true: a shadow ray, v = origin, the light direction is uniform.  first_scatter / bounce are
+// what scene_camera_ray / scene_next_ray write for those two.  A stored record keeps what k_scene_shade_c reads.
+template <bool SHADOW>
+struct SceneRecords {
+    using Ray = SceneRay;
+    using Out = SceneHit;
+    static constexpr bool kRayState = false;
+    V3 uniform;
+    GPIS_DEV void load(const Ray *__restrict__ rayp, V3 &pos, V3 &dir, float &nearT, float &farT, float &u_jitter, bool &first_scatter, int &bounce) const
+    {
+        const V3 v = v3(rayp->v[0], rayp->v[1], rayp->v[2]);
+        pos = SHADOW ? v : uniform;
+        dir = SHADOW ? uniform : v;
+        nearT = SHADOW ? 0.f : rayp->near_t;      // a shadow ray starts at its hit point (scene_next_ray)
+        farT = rayp->far_t; u_jitter = rayp->u_jitter;
+        first_scatter = !SHADOW;
+        bounce = SHADOW ? 1 : 0;
+    }
+    static GPIS_DEV void store(Out *out, const gpis_seg_out &o)
+    {
+        // aniso of a record with ok = 1 and exited = 0, the only one whose gradient is read, is to_d() of a float gradient
+        const float4 a = make_float4(o.p[0], o.p[1], o.p[2], (float)o.aniso[0]);
+        const float4 b = make_float4((float)o.aniso[1], (float)o.aniso[2], __uint_as_float((o.ok ? kSceneHitOk : 0u) | (o.exited ? kSceneHitExited : 0u)), 0.f);
+        float4 *q = reinterpret_cast<float4 *>(out);
+        q[0] = a; q[1] = b;
+    }
+};
 // The MediumSample / MediumState writes of GPM.cpp:224-340 for one finished segment.
-GPIS_DEV void finish_sample_distance(const DevModel &M, const gpis_ray_in *__restrict__ rayp, V3 pos, V3 dir, float farT, bool early_ok,
-                                     bool want_grad, bool hit, double t, float last_val, int gp, V3 g, gpis_seg_out *out)
+template <class REC = BatchRecords>
+GPIS_DEV void finish_sample_distance(const DevModel &M, const typename REC::Ray *__restrict__ rayp, V3 pos, V3 dir, float farT, bool early_ok,
+                                     bool want_grad, bool hit, double t, float last_val, int gp, V3 g, typename REC::Out *out)
 {
     const float maxT = farT;
     gpis_seg_out o;
@@ -765,27 +805,35 @@ GPIS_DEV void finish_sample_distance(const DevModel &M, const gpis_ray_in *__res
     o.sample_t = 0.f; o.continued_t = 0.f;
     for (int c = 0; c < 3; ++c) { o.weight[c] = 0.f; o.continued_weight[c] = 0.f; o.p[c] = 0.f; }
     o.exited = 0; o.ok = 0; o.scheme = GPIS_UNI;
-    o.gp_id = rayp->last_gp_id;
-    o.last_val = rayp->last_val;
-    o.aniso[0] = rayp->last_aniso[0]; o.aniso[1] = rayp->last_aniso[1]; o.aniso[2] = rayp->last_aniso[2];
+    if constexpr (REC::kRayState) {
+        o.gp_id = rayp->last_gp_id;
+        o.last_val = rayp->last_val;
+        o.aniso[0] = rayp->last_aniso[0]; o.aniso[1] = rayp->last_aniso[1]; o.aniso[2] = rayp->last_aniso[2];
+    } else {
+        o.gp_id = 0; o.last_val = 0.f;
+        o.aniso[0] = o.aniso[1] = o.aniso[2] = 0.;
+    }
     if (early_ok) {
         o.weight[0] = o.weight[1] = o.weight[2] = 1.f;
         o.exited = 1;
         V3 pp = pos + dir * o.sample_t;
         o.p[0] = pp.x; o.p[1] = pp.y; o.p[2] = pp.z;
         o.ok = 1;
-        *out = o;
+        REC::store(out, o);
         return;
     }
     if (!want_grad) {   // bounce limit
-        *out = o;
+        REC::store(out, o);
         return;
     }
     V3d aniso = to_d(g);
     o.t = t;
     o.exited = hit ? 0 : 1;
     o.last_val = last_val;
-    o.gp_id = hit ? gp : rayp->last_gp_id;   // intersectGP stores GPId only on a hit (SCNM.cpp:162); an exit keeps state.lastGPId
+    if constexpr (REC::kRayState)
+        o.gp_id = hit ? gp : rayp->last_gp_id;   // intersectGP stores GPId only on a hit (SCNM.cpp:162); an exit keeps state.lastGPId
+    else
+        o.gp_id = gp;
     bool ok = true;
     if (hit) {
         double avg = (aniso.x + aniso.y + aniso.z) / 3.0;
@@ -816,7 +864,7 @@ GPIS_DEV void finish_sample_distance(const DevModel &M, const gpis_ray_in *__res
         o.p[0] = pp.x; o.p[1] = pp.y; o.p[2] = pp.z;
         o.ok = 1;
     }
-    *out = o;
+    REC::store(out, o);
 }
 
 // The march of one wave of segments.  WANT_SAMPLE: sampleDistance (GPM.cpp:221-341) — otherwise

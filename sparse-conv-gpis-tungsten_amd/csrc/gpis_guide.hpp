@@ -639,20 +639,30 @@ GPIS_DEV int guide_sign_at(const DevModel &M, const GuideField &F, const GuideRa
 // ends there as it does in the transmittance instance — neither lastVal at farT nor the gradient there is evaluated, and its record
 // is the exit record (ok = 1, exited = 1, t = farT) with last_val = 0 and aniso = 0.  A caller that only asks "hit or exit?" never
 // reads either; the batch ABI returns both and keeps EXIT_STATE = true.
-template <bool WANT_SAMPLE, bool SMALLARG, bool DEFER_GRAD = false, bool EXIT_STATE = true>
+// REC (gpis_fast.hpp): the record policy — which ray record the lane loads at the top and which segment record
+// finish_sample_distance stores at the end.  BatchRecords are the records of the batch ABI, loaded by the text below as ever (as a
+// call of the policy the same load cost k_guided_sample_distance_nograd<false> six spills less: its code is to stay as it was);
+// SceneRecords the 32-byte records of the Lambert frame driver, whose uniform origin / direction comes in `rec`.  Nothing between the
+// load and the store depends on the policy.
+template <bool WANT_SAMPLE, bool SMALLARG, bool DEFER_GRAD = false, bool EXIT_STATE = true, class REC = BatchRecords>
 GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideField &F, FastLds &lds, bool valid,
-                           const gpis_ray_in *__restrict__ rayp, gpis_seg_out *out, bool &visible, uint32_t &n_eval, uint32_t &n_guide)
+                           const typename REC::Ray *__restrict__ rayp, typename REC::Out *out, bool &visible, uint32_t &n_eval, uint32_t &n_guide,
+                           const REC &rec = REC())
 {
     V3 pos = v3(0.f, 0.f, 1.f), dir = v3(0.f, 0.f, 1.f);
     float nearT = 0.f, farT = 1.f, u_jitter = 0.f;
     bool first_scatter = true;
     int bounce = 0;
     if (valid) {
-        pos = v3(rayp->pos[0], rayp->pos[1], rayp->pos[2]);
-        dir = v3(rayp->dir[0], rayp->dir[1], rayp->dir[2]);
-        nearT = rayp->near_t; farT = rayp->far_t; u_jitter = rayp->u_jitter;
-        first_scatter = rayp->first_scatter != 0;
-        bounce = rayp->bounce;
+        if constexpr (REC::kRayState) {
+            pos = v3(rayp->pos[0], rayp->pos[1], rayp->pos[2]);
+            dir = v3(rayp->dir[0], rayp->dir[1], rayp->dir[2]);
+            nearT = rayp->near_t; farT = rayp->far_t; u_jitter = rayp->u_jitter;
+            first_scatter = rayp->first_scatter != 0;
+            bounce = rayp->bounce;
+        } else {
+            rec.load(rayp, pos, dir, nearT, farT, u_jitter, first_scatter, bounce);
+        }
     }
     if (!__builtin_isfinite(farT))
         farT = (float)((double)nearT + 2000);
@@ -879,7 +889,8 @@ GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideFie
     const long long clk_g0 = FCLK();
     const bool want_grad = phase == G_GRAD;
     V3 g = v3(0.f, 0.f, 0.f);
-    if (DEFER_GRAD) {
+    if constexpr (DEFER_GRAD) {
+        static_assert(REC::kRayState, "the deferred-gradient instance exists on the batch records only");
         if (valid && want_grad) {
             out->t = t;
             out->exited = hit ? 0 : 1;
@@ -914,9 +925,9 @@ GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideFie
     if (!valid)
         return;
     if constexpr (EXIT_STATE)
-        finish_sample_distance(M, rayp, pos, dir, farT, early_ok, want_grad, hit, t, last_val, gp, g, out);
+        finish_sample_distance<REC>(M, rayp, pos, dir, farT, early_ok, want_grad, hit, t, last_val, gp, g, out);
     else
-        finish_sample_distance(M, rayp, pos, dir, farT, early_ok, want_grad || phase == G_EXIT, hit, t, last_val, gp, g, out);
+        finish_sample_distance<REC>(M, rayp, pos, dir, farT, early_ok, want_grad || phase == G_EXIT, hit, t, last_val, gp, g, out);
 }
 
 struct GuideCounters { unsigned long long n_guide; };
@@ -1010,6 +1021,56 @@ __global__ void __launch_bounds__(kFastBlock, GPIS_GUIDE_OCC_TR) k_guided_transm
     uint32_t n_eval = 0, n_guide = 0;
     bool vis = false;
     guided_march<false, SMALLARG>(*Mp, T, *Fp, lds, valid, rays + (valid ? i : 0), nullptr, vis, n_eval, n_guide);
+    if (i < n)
+        visible[i] = (valid && vis) ? 1 : 0;
+    fast_flush_counters(cnt, n_eval, valid ? 1u : 0u);
+    unsigned long long gsum = n_guide;
+    for (int off = 32; off > 0; off >>= 1) gsum += __shfl_down(gsum, off, 64);
+    if ((threadIdx.x & 63) == 0 && gsum) atomicAdd(guide_cnt, gsum);
+}
+
+// ---- the two instances of the Lambert frame driver's compact body (gpis_render_scene_s, GPIS_OPT_SCENE_COMPACT): the marches of
+// k_guided_sample_distance_noexit and k_guided_transmittance on 32-byte records (gpis_scene.hpp).  A record's flag bit 0 is the
+// batch mask; the camera position / the light direction is a kernel argument.
+template <bool SMALLARG>
+__global__ void __launch_bounds__(kFastBlock, GPIS_GUIDE_OCC) k_guided_sample_distance_scene(const DevModel *__restrict__ Mp, FastTable T, const GuideField *__restrict__ Fp, size_t n,
+                                                                                           const SceneRay *__restrict__ rays, SceneHit *__restrict__ out,
+                                                                                           float ox, float oy, float oz, Counters *cnt, unsigned long long *guide_cnt)
+{
+    __shared__ FastLds lds;
+    fast_lds_init(lds);
+    size_t i = (size_t)blockIdx.x * kFastBlock + threadIdx.x;
+    // the record is read here, as two 16-byte loads, and the march takes it from registers: 199.9 ms per C1 frame and 113 spills,
+    // against 206.0 ms and 125 with the loads behind `valid` inside the march, where k_guided_transmittance_scene has them
+    SceneRay r{};
+    if (i < n) {
+        const float4 a = reinterpret_cast<const float4 *>(rays + i)[0], b = reinterpret_cast<const float4 *>(rays + i)[1];
+        r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.near_t = a.w;
+        r.far_t = b.x; r.u_jitter = b.y; r.u_aux = b.z; r.flags = __float_as_uint(b.w);
+    }
+    const bool valid = (r.flags & kSceneRayLive) != 0u;
+    uint32_t n_eval = 0, n_guide = 0;
+    bool vis;
+    const SceneRecords<false> rec{v3(ox, oy, oz)};
+    guided_march<true, SMALLARG, false, false, SceneRecords<false>>(*Mp, T, *Fp, lds, valid, &r, out + (valid ? i : 0), vis, n_eval, n_guide, rec);
+    fast_flush_counters(cnt, n_eval, valid ? 1u : 0u);
+    unsigned long long gsum = n_guide;
+    for (int off = 32; off > 0; off >>= 1) gsum += __shfl_down(gsum, off, 64);
+    if ((threadIdx.x & 63) == 0 && gsum) atomicAdd(guide_cnt, gsum);
+}
+template <bool SMALLARG>
+__global__ void __launch_bounds__(kFastBlock, GPIS_GUIDE_OCC_TR) k_guided_transmittance_scene(const DevModel *__restrict__ Mp, FastTable T, const GuideField *__restrict__ Fp, size_t n,
+                                                                                         const SceneRay *__restrict__ rays, float lx, float ly, float lz,
+                                                                                         uint8_t *__restrict__ visible, Counters *cnt, unsigned long long *guide_cnt)
+{
+    __shared__ FastLds lds;
+    fast_lds_init(lds);
+    size_t i = (size_t)blockIdx.x * kFastBlock + threadIdx.x;
+    const bool valid = i < n && (rays[i].flags & kSceneRayLive) != 0u;
+    uint32_t n_eval = 0, n_guide = 0;
+    bool vis = false;
+    const SceneRecords<true> rec{v3(lx, ly, lz)};
+    guided_march<false, SMALLARG, false, true, SceneRecords<true>>(*Mp, T, *Fp, lds, valid, rays + (valid ? i : 0), nullptr, vis, n_eval, n_guide, rec);
     if (i < n)
         visible[i] = (valid && vis) ? 1 : 0;
     fast_flush_counters(cnt, n_eval, valid ? 1u : 0u);

@@ -483,6 +483,23 @@ __global__ void __launch_bounds__(256) k_scene_primary(SceneConst sc, size_t fir
     valid[i] = hit ? 1 : 0;
 }
 
+// the same camera step into the compact record (gpis_scene.hpp): the direction, the chord, both jitters and the "inside the bound" flag
+__global__ void __launch_bounds__(256) k_scene_primary_c(SceneConst sc, size_t first_pixel, size_t n_samples, SceneRay *__restrict__ rays)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_samples) return;
+    uint32_t x, y, spp;
+    Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
+    float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
+    float u0 = normalized_uint(g.next_i()), u1 = normalized_uint(g.next_i());
+    const V3 d = scene_camera_dir(sc, x, y, jx, jy);
+    float t0 = 0.f, t1 = 0.f;
+    const bool hit = sphere_chord(v3(sc.s.cam_pos[0], sc.s.cam_pos[1], sc.s.cam_pos[2]), d, sc.s.bound_radius, t0, t1);
+    float4 *q = reinterpret_cast<float4 *>(rays + i);
+    q[0] = make_float4(d.x, d.y, d.z, t0);
+    q[1] = make_float4(t1, u0, u1, __uint_as_float(hit ? kSceneRayLive : 0u));
+}
+
 // `shadow` may be `prim` itself (the Lambert driver writes each shadow ray over the primary ray it came from: the same thread has
 // read that record by then, and nothing reads the primary rays afterwards) — hence no __restrict__ on the two.
 __global__ void __launch_bounds__(256) k_scene_shade(SceneConst sc, size_t n_samples, const gpis_ray_in *prim,
@@ -498,13 +515,11 @@ __global__ void __launch_bounds__(256) k_scene_shade(SceneConst sc, size_t n_sam
         gpis_seg_out o = seg[i];
         if (o.ok && !o.exited) {
             h = 1;
-            V3 l = v3(sc.light[0], sc.light[1], sc.light[2]);
-            c = dot(hit_normal(o), l);
-            float t0, t1;
-            if (c > 0.f && sphere_chord(v3(o.p[0], o.p[1], o.p[2]), l, sc.s.bound_radius, t0, t1)) {
+            float t1;
+            if (scene_lambert_shade(sc, hit_normal(o), v3(o.p[0], o.p[1], o.p[2]), c, t1)) {
                 gpis_ray_in p = prim[i];
                 gpis_ray_in sh = scene_next_ray(p, o);
-                sh.dir[0] = l.x; sh.dir[1] = l.y; sh.dir[2] = l.z;
+                sh.dir[0] = sc.light[0]; sh.dir[1] = sc.light[1]; sh.dir[2] = sc.light[2];
                 sh.far_t = t1;
                 sh.u_jitter = u_shadow[i];
                 shadow[i] = sh;
@@ -514,6 +529,38 @@ __global__ void __launch_bounds__(256) k_scene_shade(SceneConst sc, size_t n_sam
     }
     cosl[i] = c;
     valid2[i] = v2;
+    hit[i] = h;
+}
+
+// The shade step on the compact records.  Every sample's ray record is rewritten in place — the shadow ray (origin = the hit point,
+// near_t = 0) or an empty record — because its flag is the mask of the shadow march; valid2 repeats the flag as the byte
+// k_scene_accumulate reads four at a time.
+__global__ void __launch_bounds__(256) k_scene_shade_c(SceneConst sc, size_t n_samples, SceneRay *rays, const SceneHit *__restrict__ seg,
+                                                       float *__restrict__ cosl, uint8_t *__restrict__ valid2, uint8_t *__restrict__ hit)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_samples) return;
+    uint8_t h = 0;
+    float c = 0.f;
+    float4 *q = reinterpret_cast<float4 *>(rays + i);
+    const float4 r1 = q[1];                      // far_t, u_jitter, u_aux, flags of the primary ray
+    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (__float_as_uint(r1.w) & kSceneRayLive) {
+        const float4 a = reinterpret_cast<const float4 *>(seg + i)[0], b = reinterpret_cast<const float4 *>(seg + i)[1];
+        SceneHit o;
+        o.p[0] = a.x; o.p[1] = a.y; o.p[2] = a.z; o.g[0] = a.w; o.g[1] = b.x; o.g[2] = b.y; o.flags = __float_as_uint(b.z);
+        if ((o.flags & kSceneHitOk) && !(o.flags & kSceneHitExited)) {
+            h = 1;
+            float t1;
+            if (scene_lambert_shade(sc, hit_normal(o), v3(o.p[0], o.p[1], o.p[2]), c, t1)) {
+                s0 = make_float4(o.p[0], o.p[1], o.p[2], 0.f);
+                s1 = make_float4(t1, r1.z, 0.f, __uint_as_float(kSceneRayLive));
+            }
+        }
+    }
+    q[0] = s0; q[1] = s1;
+    cosl[i] = c;
+    valid2[i] = (__float_as_uint(s1.w) & kSceneRayLive) ? 1 : 0;
     hit[i] = h;
 }
 
@@ -1166,6 +1213,8 @@ extern "C" int gpis_create(const gpis_params *params, int device, gpis_medium **
         if (const char *e = getenv("GPIS_SOLO_MAX")) m->opt[GPIS_OPT_SOLO_MAX] = atoll(e);
         m->opt[GPIS_OPT_SCENE_EXIT_STATE] = 0;
         if (const char *e = getenv("GPIS_SCENE_EXIT_STATE")) m->opt[GPIS_OPT_SCENE_EXIT_STATE] = e[0] != '0';
+        m->opt[GPIS_OPT_SCENE_COMPACT] = 1;
+        if (const char *e = getenv("GPIS_SCENE_COMPACT")) m->opt[GPIS_OPT_SCENE_COMPACT] = e[0] != '0';
         m->opt[GPIS_OPT_CHUNK_LOG2] = 0;
         if (const char *e = getenv("GPIS_CHUNK_LOG2")) { int l = atoi(e); m->opt[GPIS_OPT_CHUNK_LOG2] = l < 16 ? 16 : (l > 28 ? 28 : l); }
     }
@@ -1517,6 +1566,32 @@ static int transmittance_impl(gpis_medium *m, size_t n, const gpis_ray_in *rays,
     return launch_check("k_transmittance");
 }
 
+// The Lambert frame driver's compact body (gpis_scene.hpp: 32-byte records): the marches k_guided_sample_distance_noexit and
+// k_guided_transmittance run, on the same counters and profile slots, reading the camera position / the light direction from the
+// launch.  lambert_compact() is true exactly when sample_distance_impl(exit_state = false) and transmittance_impl would launch those
+// two kernels for a coherent batch; every other selection keeps the full-record body.  `guided` is m->guide.enabled for a render call
+// (under the handle's lock); gpis_reserve_scene_workspace, which runs beside gpis_build_guide without the lock, passes what it
+// expects instead and does not read the field the build is writing.
+static bool lambert_compact(const gpis_medium *m, bool guided)
+{
+    return m->opt[GPIS_OPT_SCENE_COMPACT] && guided && !wave_march_selected(m, MARCH_COHERENT) && m->opt[GPIS_OPT_RANGE_LEN] == 0 &&
+           !m->opt[GPIS_OPT_DEFER_GRAD] && !m->opt[GPIS_OPT_SCENE_EXIT_STATE];
+}
+static int scene_sample_distance_compact(gpis_medium *m, size_t n, const SceneRay *rays, SceneHit *out, const float origin[3], hipStream_t s)
+{
+    if (n == 0) return GPIS_OK;
+    ProfScope prof(m, 0, s);
+    launch::guided_sample_distance_scene(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->d_guide, n, rays, out, origin, m->d_counters, m->d_guide_cnt, s);
+    return launch_check("k_guided_sample_distance_scene");
+}
+static int scene_transmittance_compact(gpis_medium *m, size_t n, const SceneRay *rays, const float light[3], uint8_t *visible, hipStream_t s)
+{
+    if (n == 0) return GPIS_OK;
+    ProfScope prof(m, 1, s);
+    launch::guided_transmittance_scene(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->d_guide, n, rays, light, visible, m->d_counters + 1, m->d_guide_cnt, s);
+    return launch_check("k_guided_transmittance_scene");
+}
+
 extern "C" int gpis_sample_distance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, gpis_cond_coeff *coeff, void *stream)
 {
     CHECK_ARGS(std_handle(m) && (n == 0 || (rays && out)));
@@ -1544,7 +1619,7 @@ extern "C" int gpis_set_option(gpis_medium *m, int option, long long value)
     switch (option) {
     case GPIS_OPT_MARCH_FORM: CHECK_ARGS(value >= GPIS_MARCH_FORM_AUTO && value <= GPIS_MARCH_FORM_WAVE); break;
     case GPIS_OPT_WAVE_TAIL: CHECK_ARGS(value >= 0); break;
-    case GPIS_OPT_PATHS_SORT: case GPIS_OPT_PATHS_PRESORT: case GPIS_OPT_PERSISTENT: case GPIS_OPT_DEFER_GRAD: case GPIS_OPT_SCENE_EXIT_STATE: CHECK_ARGS(value == 0 || value == 1); break;
+    case GPIS_OPT_PATHS_SORT: case GPIS_OPT_PATHS_PRESORT: case GPIS_OPT_PERSISTENT: case GPIS_OPT_DEFER_GRAD: case GPIS_OPT_SCENE_EXIT_STATE: case GPIS_OPT_SCENE_COMPACT: CHECK_ARGS(value == 0 || value == 1); break;
     case GPIS_OPT_CHUNK_LOG2: CHECK_ARGS(value == 0 || (value >= 16 && value <= 28)); break;
     case GPIS_OPT_SOLO_MAX: CHECK_ARGS(value >= -1 && value <= 64); break;
     case GPIS_OPT_RANGE_LEN: CHECK_ARGS(value >= 0 && value <= (1 << 24) && value % 64 == 0); break;
@@ -2158,26 +2233,31 @@ static bool try_stage(gpis_medium *m, int slot, size_t bytes)
     return false;
 }
 
-// Workspace of the Lambert driver, 236 B per sample in three allocations: slot 3 [primary rays, overwritten in place by the shadow
-// rays | shadow jitter | mask], slot 5 [segment results], slot 6 [cos | mask | visible | hit].  The chunk is the largest the
-// device can hold, starting from the whole frame (2^27 samples = 31.3 GB; 48.3 GB with separate shadow rays until round 3).
+// Workspace of the Lambert driver in three allocations: slot 3 [primary rays, overwritten in place by the shadow rays | shadow
+// jitter | mask], slot 5 [segment results], slot 6 [cos | mask | visible | hit].  Full-record body: 236 B per sample (gpis_ray_in
+// 128 + 5, gpis_seg_out 96, 7).  Compact body (lambert_compact): 71 B per sample (SceneRay 32, which carries the jitter and the
+// mask; SceneHit 32; 7).  The chunk is the largest the device can hold, starting from the whole frame (2^27 samples = 9.5 GB
+// compact, 31.3 GB full; 48.3 GB with separate shadow rays until round 3).
 struct LambertWs {
+    bool compact;                                      // which body the sizes are for
     size_t chunk_pixels, ns_max;
     size_t b_prim, b_seg, b_shadow;                    // bytes of slots 3, 5, 6
     size_t o_prim, o_us, o_v1;                         // offsets inside slot 3
     size_t o_cos, o_v2, o_vis, o_hit;                  // offsets inside slot 6
 };
 // First-use policy: memory this process allocates for the first time costs 15-30 ms per GB on these boxes (DESIGN.md §6 "cold
-// frame"), so the whole-frame workspace (31 GB) would triple the latency of a handle's FIRST frame.  That frame therefore runs in
-// 16 Mi-sample chunks (4 GB, -4 % throughput); from the second call on — the handle is evidently reused — the workspace grows to
+// frame"), so the whole-frame workspace (9.5 GB compact, 31 GB full) would add to the latency of a handle's FIRST frame.  That frame
+// therefore runs in 16 Mi-sample chunks (1.2 GB compact, 4 GB full; -4 % throughput); from the second call on — the handle is evidently reused — the workspace grows to
 // the whole frame.  A workspace that is already large enough (gpis_reserve_scene_workspace, an earlier larger call) is used as is,
 // and GPIS_CHUNK_LOG2 / GPIS_OPT_CHUNK_LOG2 override the policy.
-static int lambert_ws_plan(gpis_medium *m, const gpis_scene_s *s, size_t total_pixels, LambertWs &W, bool first_call = false)
+static int lambert_ws_plan(gpis_medium *m, const gpis_scene_s *s, size_t total_pixels, LambertWs &W, bool guided, bool first_call = false)
 {
     int l0 = chunk_log2(m, 27);
+    W.compact = lambert_compact(m, guided);
+    const size_t ray_bytes = W.compact ? sizeof(SceneRay) : sizeof(gpis_ray_in), seg_bytes = W.compact ? sizeof(SceneHit) : sizeof(gpis_seg_out);
     if (first_call && !m->opt[GPIS_OPT_CHUNK_LOG2]) {
         const size_t whole = (total_pixels * s->spp_count < ((size_t)1 << 27) ? total_pixels * s->spp_count : ((size_t)1 << 27));
-        const bool have_whole = stage_size(m, 3) >= whole * (sizeof(gpis_ray_in) + 5) && stage_size(m, 5) >= whole * sizeof(gpis_seg_out) && stage_size(m, 6) >= whole * 7;
+        const bool have_whole = stage_size(m, 3) >= whole * (ray_bytes + (W.compact ? 0 : 5)) && stage_size(m, 5) >= whole * seg_bytes && stage_size(m, 6) >= whole * 7;
         if (!have_whole) l0 = 24;
     }
     for (int l = l0;; --l) {
@@ -2187,9 +2267,11 @@ static int lambert_ws_plan(gpis_medium *m, const gpis_scene_s *s, size_t total_p
         const size_t n = W.ns_max = W.chunk_pixels * s->spp_count;
         size_t off = 0;
         auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-        W.o_prim = carve(n * sizeof(gpis_ray_in)); W.o_us = carve(n * 4); W.o_v1 = carve(n);
+        W.o_prim = carve(n * ray_bytes);
+        W.o_us = W.o_v1 = 0;
+        if (!W.compact) { W.o_us = carve(n * 4); W.o_v1 = carve(n); }
         W.b_prim = off;
-        W.b_seg = n * sizeof(gpis_seg_out);
+        W.b_seg = n * seg_bytes;
         off = 0;
         W.o_cos = carve(n * 4); W.o_v2 = carve(n); W.o_vis = carve(n); W.o_hit = carve(n);
         W.b_shadow = off;
@@ -2234,7 +2316,9 @@ extern "C" int gpis_reserve_scene_workspace(gpis_medium *m, const gpis_scene_s *
     CHECK_ARGS(scene_args_ok(s));
     HIP_TRY(hipSetDevice(m->device));
     LambertWs W;
-    if (int rc = lambert_ws_plan(m, s, scene_rows(*s) * s->width, W)) return rc;
+    // Sized for the guided body wherever the medium can carry a guide: the call is made beside gpis_build_guide, before the guide
+    // is enabled.  A handle that then renders without a guide grows the three arrays on demand.
+    if (int rc = lambert_ws_plan(m, s, scene_rows(*s) * s->width, W, m->fast.enabled != 0)) return rc;
     if (int rc = ensure_stage(m, 3, W.b_prim, true)) return rc;      // in the order the first frame needs them
     if (int rc = ensure_stage(m, 5, W.b_seg, true)) return rc;
     return ensure_stage(m, 6, W.b_shadow, true);
@@ -2250,7 +2334,7 @@ extern "C" int gpis_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float 
     SceneConst sc = make_scene_const(s);
     const size_t total_pixels = scene_rows(*s) * s->width;
     LambertWs W;
-    if (int rc0 = lambert_ws_plan(m, s, total_pixels, W, m->lambert_calls == 0)) return rc0;
+    if (int rc0 = lambert_ws_plan(m, s, total_pixels, W, m->guide.enabled != 0, m->lambert_calls == 0)) return rc0;
     ++m->lambert_calls;
     int rc = GPIS_OK;
     if ((rc = ws_acquire(m, 0, st))) return rc;
@@ -2265,6 +2349,25 @@ extern "C" int gpis_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float 
     for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
         size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
         size_t ns = np * s->spp_count;
+        if (W.compact) {
+            // the same five stages on 32-byte records: a ray record carries its mask and the shadow jitter, and is rewritten in place
+            SceneRay *cray = (SceneRay *)(ws3 + W.o_prim);
+            k_scene_primary_c<<<grid_of(ns, 256), 256, 0, st>>>(sc, p0, ns, cray);
+            if ((rc = launch_check("k_scene_primary_c"))) return rc;
+            if ((rc = ensure_stage(m, 5, W.b_seg, true))) return rc;
+            SceneHit *chit = (SceneHit *)m->stage[5];
+            if ((rc = scene_sample_distance_compact(m, ns, cray, chit, sc.s.cam_pos, st))) return rc;
+            if ((rc = ensure_stage(m, 6, W.b_shadow, true))) return rc;
+            char *ws6 = (char *)m->stage[6];
+            float *cosl = (float *)(ws6 + W.o_cos);
+            uint8_t *v2 = (uint8_t *)(ws6 + W.o_v2), *vis = (uint8_t *)(ws6 + W.o_vis), *hit = (uint8_t *)(ws6 + W.o_hit);
+            k_scene_shade_c<<<grid_of(ns, 256), 256, 0, st>>>(sc, ns, cray, chit, cosl, v2, hit);
+            if ((rc = launch_check("k_scene_shade_c"))) return rc;
+            if ((rc = scene_transmittance_compact(m, ns, cray, sc.light, vis, st))) return rc;
+            k_scene_accumulate<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, cosl, v2, vis, hit, radiance_sum, hit_count);
+            if ((rc = launch_check("k_scene_accumulate"))) return rc;
+            continue;
+        }
         k_scene_primary<<<grid_of(ns, 256), 256, 0, st>>>(sc, p0, ns, prim, us, v1);
         if ((rc = launch_check("k_scene_primary"))) return rc;
         if ((rc = ensure_stage(m, 5, W.b_seg, true))) return rc;

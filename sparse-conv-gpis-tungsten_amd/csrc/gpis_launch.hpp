@@ -17,6 +17,8 @@ struct FastTable;
 struct GuideField;
 struct PersistArgs;
 struct SceneConst;
+struct SceneRay;
+struct SceneHit;
 
 // radix sort of (key, value) pairs (gpis_sort.hip); two-call convention: temp == nullptr only reports the scratch size
 hipError_t sort_pairs_u32(void *temp, size_t &temp_bytes, const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
@@ -63,6 +65,12 @@ void range_grad(bool small_arg, const DevModel *d_model, const FastTable &T, con
                 gpis_cond_coeff *coeff, const uint8_t *mask, Counters *cnt, hipStream_t s);      // completes the records a *_nograd / range march left pending
 void guided_transmittance(bool small_arg, const DevModel *d_model, const FastTable &T, const GuideField *d_guide, size_t n, const gpis_ray_in *rays,
                           uint8_t *visible, const uint8_t *mask, Counters *cnt, unsigned long long *guide_cnt, hipStream_t s);
+// the same two marches as k_guided_sample_distance_noexit / k_guided_transmittance on the compact records of the Lambert frame driver
+// (gpis_scene.hpp): flag bit 0 of a ray is its mask; `origin` (camera) / `light` (direction) is the vector all rays of the launch share
+void guided_sample_distance_scene(bool small_arg, const DevModel *d_model, const FastTable &T, const GuideField *d_guide, size_t n, const SceneRay *rays,
+                                  SceneHit *out, const float origin[3], Counters *cnt, unsigned long long *guide_cnt, hipStream_t s);
+void guided_transmittance_scene(bool small_arg, const DevModel *d_model, const FastTable &T, const GuideField *d_guide, size_t n, const SceneRay *rays,
+                                const float light[3], uint8_t *visible, Counters *cnt, unsigned long long *guide_cnt, hipStream_t s);
 // ---- guided march with in-wave refill from a range of the batch (tu_range.hip; off by default) ------------------
 void range_sample_distance(bool small_arg, const DevModel *d_model, const FastTable &T, const GuideField &F, size_t n, const gpis_ray_in *rays,
                            gpis_seg_out *out, gpis_cond_coeff *coeff, const uint8_t *mask, Counters *cnt, unsigned long long *guide_cnt,

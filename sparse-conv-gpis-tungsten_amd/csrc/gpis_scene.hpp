@@ -7,6 +7,9 @@
 //       k_fs_paths;
 //   hit_normal — the six shading kernels (k_scene_shade, k_paths_shade, k_ws_scene, k_ws_paths, k_fs_scene, k_fs_paths) and
 //       the set-up of the conductor NEE drivers (nee_setup_sample in gpis_hip.hip);
+//   the compact records of the Lambert frame (SceneRay, SceneHit: 32 B each, what gpis_render_scene_s passes between its kernels on
+//       the resident guided march), scene_camera_dir and scene_lambert_shade, which k_scene_primary / k_scene_shade share with
+//       their compact forms k_scene_primary_c / k_scene_shade_c;
 //   scene_next_ray, the ray that continues a path from a hit — the Lambert shadow rays of k_scene_shade, k_ws_scene and
 //       k_fs_scene, the shadow rays of the conductor NEE drivers (nee_shade_sample) and the next path segment of
 //       k_nee_paths_shade.
@@ -77,6 +80,29 @@ inline SceneConst make_scene_const(const gpis_scene_s *s)
     return sc;
 }
 
+// ---- the compact records of the Lambert frame driver (gpis_render_scene_s on the resident guided march, GPIS_OPT_SCENE_COMPACT).
+// Of the 128 B of a gpis_ray_in the guided march reads 11 words, and of those the origin of a primary ray (the camera) and the
+// direction of a shadow ray (the light) are the same for every sample of a launch, as are first_scatter and bounce: they travel as
+// kernel arguments.  One 32-byte record per lane remains, 16-byte aligned so that it moves as two dwordx4.
+struct alignas(16) SceneRay {
+    float v[3];          // primary ray: direction; shadow ray: origin (the hit point)
+    float near_t, far_t;
+    float u_jitter;
+    float u_aux;         // primary ray: the jitter of the sample's shadow ray; shadow ray: unused (0)
+    uint32_t flags;      // bit 0 — primary ray: it crosses the bound; shadow ray: the sample has one
+};
+// What k_scene_shade_c reads of a segment result.  g is the `aniso` of the full record: that is to_d() of the float gradient, so
+// three floats hold it exactly.
+struct alignas(16) SceneHit {
+    float p[3];
+    float g[3];
+    uint32_t flags;      // bit 0: ok, bit 1: exited
+    uint32_t spare;
+};
+static_assert(sizeof(SceneRay) == 32 && alignof(SceneRay) == 16, "SceneRay: one 32-byte record per sample");
+static_assert(sizeof(SceneHit) == 32 && alignof(SceneHit) == 16, "SceneHit: one 32-byte record per sample");
+constexpr uint32_t kSceneRayLive = 1u, kSceneHitOk = 1u, kSceneHitExited = 2u;
+
 // ray / sphere(|x| = R) intersection in double; false on a miss
 __device__ __forceinline__ bool sphere_chord(V3 o, V3 d, float R, float &t0, float &t1)
 {
@@ -108,13 +134,18 @@ GPIS_DEV Pcg32 scene_sample(const SceneConst &sc, size_t first_pixel, Index i, u
     g.set_state((uint64_t)(uint32_t)(xxhash32_4(x, y, spp, s.scene_seed) + 1u));
     return g;
 }
+// direction of the camera ray through pixel (x, y) jittered by (jx, jy)
+GPIS_DEV V3 scene_camera_dir(const SceneConst &sc, uint32_t x, uint32_t y, float jx, float jy)
+{
+    const V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
+    return v3(local.x, local.y, -local.z);
+}
 // The camera ray through pixel (x, y) jittered by (jx, jy), clipped to the bounding sphere: every field of the path's first
 // gpis_ray_in but u_jitter (the caller's own draw).  false: the ray misses the bound (near_t = far_t = 0).
 GPIS_DEV bool scene_camera_ray(const SceneConst &sc, uint32_t x, uint32_t y, uint32_t spp, float jx, float jy, gpis_ray_in &ray)
 {
     const gpis_scene_s &s = sc.s;
-    const V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
-    const V3 d = v3(local.x, local.y, -local.z);
+    const V3 d = scene_camera_dir(sc, x, y, jx, jy);
     const V3 o = v3(s.cam_pos[0], s.cam_pos[1], s.cam_pos[2]);
     memset(&ray, 0, sizeof ray);
     ray.pos[0] = o.x; ray.pos[1] = o.y; ray.pos[2] = o.z;
@@ -129,11 +160,22 @@ GPIS_DEV bool scene_camera_ray(const SceneConst &sc, uint32_t x, uint32_t y, uin
 }
 
 // the sampled gradient at a hit, normalised in double and rounded per component
-GPIS_DEV V3 hit_normal(const gpis_seg_out &o)
+GPIS_DEV V3 hit_normal(double ax, double ay, double az)
 {
-    const double ax = o.aniso[0], ay = o.aniso[1], az = o.aniso[2];
     const double len = sqrt(ax * ax + ay * ay + az * az);
     return v3((float)(ax / len), (float)(ay / len), (float)(az / len));
+}
+GPIS_DEV V3 hit_normal(const gpis_seg_out &o) { return hit_normal(o.aniso[0], o.aniso[1], o.aniso[2]); }
+GPIS_DEV V3 hit_normal(const SceneHit &o) { return hit_normal((double)o.g[0], (double)o.g[1], (double)o.g[2]); }
+
+// The Lambert shade step at a hit at p with normal n: c = cos to the light; true where the sample gets a shadow ray (lit, and the
+// ray from p towards the light crosses the bound), which then ends at far_t.
+GPIS_DEV bool scene_lambert_shade(const SceneConst &sc, V3 n, V3 p, float &c, float &far_t)
+{
+    const V3 l = v3(sc.light[0], sc.light[1], sc.light[2]);
+    c = dot(n, l);
+    float t0;
+    return c > 0.f && sphere_chord(p, l, sc.s.bound_radius, t0, far_t);
 }
 
 // The shadow ray that continues the path of `ray` from the hit `o`: everything but dir, far_t and u_jitter, which the caller

@@ -24,6 +24,12 @@ void guided_sample_distance_noexit(bool small_arg, const DevModel *d_model, cons
     if (small_arg) k_guided_sample_distance_noexit<true><<<grid_of(n, kFastBlock), kFastBlock, 0, s>>>(d_model, T, d_guide, n, rays, out, coeff, mask, cnt, guide_cnt);
     else k_guided_sample_distance_noexit<false><<<grid_of(n, kFastBlock), kFastBlock, 0, s>>>(d_model, T, d_guide, n, rays, out, coeff, mask, cnt, guide_cnt);
 }
+void guided_sample_distance_scene(bool small_arg, const DevModel *d_model, const FastTable &T, const GuideField *d_guide, size_t n, const SceneRay *rays,
+                                  SceneHit *out, const float origin[3], Counters *cnt, unsigned long long *guide_cnt, hipStream_t s)
+{
+    if (small_arg) k_guided_sample_distance_scene<true><<<grid_of(n, kFastBlock), kFastBlock, 0, s>>>(d_model, T, d_guide, n, rays, out, origin[0], origin[1], origin[2], cnt, guide_cnt);
+    else k_guided_sample_distance_scene<false><<<grid_of(n, kFastBlock), kFastBlock, 0, s>>>(d_model, T, d_guide, n, rays, out, origin[0], origin[1], origin[2], cnt, guide_cnt);
+}
 int fast_stats_read(unsigned long long *out32)
 {
 #ifdef GPIS_FAST_STATS
