@@ -691,6 +691,74 @@ int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_pat
 int gpis_render_scene_s_paths_rgb(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, const float albedo[3],
                                   float *radiance_sum3, uint32_t *seg_count, void *stream);
 
+/* ---- variance-driven adaptive sampling (PathTraceIntegrator.cpp:43-163, SampleRecord.hpp:44-65; RendererSettings.hpp:39-51:
+ * "adaptive_sampling" true and "spp_step" 16 are the reference's defaults) ---------------------------------------------------- */
+typedef struct gpis_adaptive_s {
+    uint32_t spp_step;        /* 16  RendererSettings "spp_step" */
+    uint32_t threshold;       /* 16  PathTraceIntegrator::AdaptiveThreshold; >= 2 */
+    uint32_t seed;            /* 0xBA5EBA11: seed of the integrator's own UniformSampler */
+    uint32_t _pad;
+} gpis_adaptive_s;
+
+/* SampleRecord.hpp:13-15, one per 4x4 variance tile, index vx + vy * ceil(width/4). 24 bytes. */
+typedef struct gpis_adaptive_record {
+    uint32_t sample_count, next_sample_count, sample_index;
+    float adaptive_weight, mean, running_variance;
+} gpis_adaptive_record;
+
+typedef struct gpis_adaptive_info { uint32_t passes_rendered, stopped_early; uint64_t samples; } gpis_adaptive_info;
+
+void gpis_default_adaptive_s(gpis_adaptive_s *a);
+
+/* gpis_render_scene_s — the same Lambert estimator, sample for sample — under the sample schedule of the reference's
+ * PathTraceIntegrator.  Sparse-convolution handles; s->spp_count is the AVERAGE number of samples per pixel, S.
+ *
+ * Pass loop (PathTraceIntegrator::startRender / advanceSpp): cur = 0; while cur < S: next = min(cur + spp_step, S), n = next - cur;
+ * one plan step (gpis_adaptive_plan_host below, = generateWork, :109-133); a 0 from it ends the frame; else the pass is rendered
+ * and cur = next.  The records start zeroed (SampleRecord.hpp:17-22).  The integrator's sampler is UniformSampler(hash32(seed))
+ * (:194, UniformSampler.hpp:22, MathUtil.hpp:169) less the ceil(W/16) * ceil(H/16) nextI() draws of diceTiles (:26-41):
+ * gpis_adaptive_rng_init_host.  Nothing else draws from it.
+ *
+ * Samples of a pass (renderTile, :135-163): pixel (x, y) belongs to record (x/4) + (y/4) * ceil(W/4) and takes the samples
+ * k = s->spp_begin + sample_index + i, i < next_sample_count of that record; each is exactly the sample (x, y, k) of
+ * gpis_render_scene_s.  DIFFERENCE from the reference: it hands traceSample `_currentSpp + i` as the spp word (:148), which
+ * repeats realization seeds across passes once a count exceeds spp_step; every draw of this library derives from k, so that
+ * would be the same sample twice.  sample_index + i is the reference's own startPath index (:147).
+ * Clamp (:149-156): a sample value that is NaN, infinite or > 65536 counts as 0, in the image and in the statistics.
+ * Image: per pixel and pass the samples are summed in i order from zero; that sum is ACCUMULATED once into
+ * radiance_sum[y*width+x], the count into sample_count, the hits into hit_count (device pointers, height*width entries; the caller
+ * divides each pixel by its own sample_count).  While no sample is clamped, a pixel therefore equals bit for bit what the
+ * sequence of gpis_render_scene_s calls with its (spp_begin, spp_count) ranges gives.
+ * Statistics: per record SampleRecord::addSample(float) (Welford in float, :44-50, contraction off) over the tile's pixels
+ * row-major, clipped at the image edge, then i — the order of renderTile, since its 16-pixel tiles are multiples of 4.
+ * records (device pointer, ceil(W/4) * ceil(H/4) entries, may be NULL) receives the records after the last rendered pass with the
+ * closing sample_index += next_sample_count applied: sample_index is then the tile's samples per pixel.  info (host pointer, may be
+ * NULL): passes rendered, whether a plan step ended the frame early, samples rendered.  hit_count may be NULL.
+ * Image, counts and records depend neither on how a pass is cut into chunks (GPIS_OPT_CHUNK_LOG2; cuts fall between records,
+ * and a record larger than a chunk is a chunk of its own) nor on any tuning option; the marches are those gpis_render_scene_s
+ * launches (32-byte records where it would pass them).
+ * GPIS_ERR_INVALID_ARG, nothing written: rows other than the whole image or shard_count > 1 (the percentile needs the whole
+ * frame), spp_step == 0, threshold < 2, a NULL a / radiance_sum / sample_count, a weight-space handle, spp_count == 0.
+ * The plan runs on the host: the entry SYNCHRONISES `stream` once per pass (and returns with the stream idle). */
+int gpis_render_scene_s_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a,
+                                 float *radiance_sum, uint32_t *sample_count, uint32_t *hit_count,
+                                 gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
+/* host only, no device needed: one PathTraceIntegrator::generateWork step on `records` (in place, n_records must be
+ * ceil(width/4) * ceil(height/4)); returns 1 (render the pass), 0 (maxError == 0: stop; only sample_index and adaptive_weight
+ * have changed), < 0 error.  *rng_state is the integrator sampler's PCG state.  current_spp / pass_spp are _currentSpp and
+ * _nextSpp - _currentSpp (pass_spp >= 1).  In order: sample_index += next_sample_count; below the threshold next_sample_count =
+ * pass_spp; else errorPercentile95 (:43-58), the clamp to it, dilateAdaptiveWeights (:60-84), distributeAdaptiveSamples
+ * (:86-107: double totalWeight in record order, int adaptiveBudget = (pass_spp-1)*W*H in 32 bits, /16, the float factor, the
+ * running pixelPdf carry with one next1D() per record), next_sample_count = adaptiveSamples + 1.  min / max are MathUtil.hpp's
+ * (a < b ? a : b, a > b ? a : b); int(fractionalSamples) of a NaN is taken as 0 and saturates at +-2^31. */
+int gpis_adaptive_plan_host(const gpis_adaptive_s *a, uint32_t width, uint32_t height, uint32_t current_spp,
+                            uint32_t pass_spp, uint64_t *rng_state, size_t n_records, gpis_adaptive_record *records);
+/* host only: the PCG state gpis_render_scene_s_adaptive starts a width x height frame with (0 for a NULL a). */
+uint64_t gpis_adaptive_rng_init_host(const gpis_adaptive_s *a, uint32_t width, uint32_t height);
+/* host only, test surface: SampleRecord::addSample over values[n] onto *rec, then variance() and errorEstimate() of the result
+ * (out2, may be NULL) — the statistics the device kernel and the plan step compute. */
+void gpis_adaptive_record_add_host(gpis_adaptive_record *rec, size_t n, const float *values, float *out2);
+
 /* ---- weight-space GP medium (WeightSpaceGaussianProcessMedium.cpp, WeightSpaceGaussianProcess.cpp) --------------------
  * The field of one realization is  f(p) = sqrt(cov(p,p)) * (sqrt(2/N) * sum_i w_i cos((d_i . p) * omega_i + phi_i)) + mean(p)
  * with N random Fourier features of the squared-exponential covariance (WSG:120-127, 160-240).  A realization is fixed by the

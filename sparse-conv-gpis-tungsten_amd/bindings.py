@@ -132,6 +132,21 @@ SURFACE_S = np.dtype([
     ("eta", "<f4"), ("k", "<f4"), ("albedo", "<f4"), ("cap_cos", "<f4"), ("cap_radiance", "<f4"), ("_pad", "<f4", 3),
 ], align=True)
 
+# variance-driven adaptive sampling (gpis_render_scene_s_adaptive)
+ADAPTIVE_S = np.dtype([("spp_step", "<u4"), ("threshold", "<u4"), ("seed", "<u4"), ("_pad", "<u4")], align=True)
+ADAPTIVE_RECORD = np.dtype([
+    ("sample_count", "<u4"), ("next_sample_count", "<u4"), ("sample_index", "<u4"),
+    ("adaptive_weight", "<f4"), ("mean", "<f4"), ("running_variance", "<f4"),
+], align=True)
+ADAPTIVE_INFO = np.dtype([("passes_rendered", "<u4"), ("stopped_early", "<u4"), ("samples", "<u8")], align=True)
+
+
+def default_adaptive_s():
+    """gpis_default_adaptive_s (RendererSettings "spp_step" 16, AdaptiveThreshold 16, the integrator's seed) without loading the library."""
+    a = np.zeros((), dtype=ADAPTIVE_S)
+    a["spp_step"], a["threshold"], a["seed"] = 16, 16, 0xBA5EBA11
+    return a
+
 
 def default_scene_s(width, height, spp):
     """gpis_default_scene_s (scene S of SURVEY.md 8d) without loading the library."""
@@ -192,6 +207,7 @@ _EXPECTED_SIZES = {
     "gpis_surface_s": SURFACE_S.itemsize, "gpis_ramp": RAMP.itemsize,
     "gpis_fs_state": FS_STATE.itemsize, "gpis_guide_info": GUIDE_INFO.itemsize,
     "gpis_ws_params": WS_PARAMS.itemsize, "gpis_ws_query": WS_QUERY.itemsize,
+    "gpis_adaptive_s": ADAPTIVE_S.itemsize, "gpis_adaptive_record": ADAPTIVE_RECORD.itemsize, "gpis_adaptive_info": ADAPTIVE_INFO.itemsize,
 }
 assert RAY_IN.itemsize == 128 and SEG_OUT.itemsize == 96 and COND_COEFF.itemsize == 32
 assert QUERY.itemsize == 96 and NEE_QUERY.itemsize == 96
@@ -337,6 +353,7 @@ class GpisLib:
         "gpis_ws_sample_distance_host", "gpis_ws_transmittance_host", "gpis_ws_eval_batch", "gpis_ws_basis_batch",
         "gpis_ws_get_counters", "gpis_ws_reset_counters", "gpis_ws_render_scene_s", "gpis_ws_render_scene_s_paths",
         "gpis_fs_render_scene_s", "gpis_fs_render_scene_s_paths",
+        "gpis_default_adaptive_s", "gpis_render_scene_s_adaptive", "gpis_adaptive_plan_host", "gpis_adaptive_rng_init_host", "gpis_adaptive_record_add_host",
     ]
 
     def __init__(self, path=None):
@@ -415,6 +432,14 @@ class GpisLib:
         L.gpis_render_scene_s_nee.argtypes = [vp, vp, vp, vp, vp]
         L.gpis_render_scene_s_nee_paths.argtypes = [vp, vp, vp, i32, vp, vp, vp]
         L.gpis_render_scene_s_paths_rgb.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+        L.gpis_default_adaptive_s.argtypes = [vp]
+        L.gpis_default_adaptive_s.restype = None
+        L.gpis_render_scene_s_adaptive.argtypes = [vp] * 9
+        L.gpis_adaptive_plan_host.argtypes = [vp, u32, u32, u32, u32, vp, sz, vp]
+        L.gpis_adaptive_rng_init_host.argtypes = [vp, u32, u32]
+        L.gpis_adaptive_rng_init_host.restype = ctypes.c_uint64
+        L.gpis_adaptive_record_add_host.argtypes = [vp, sz, vp, vp]
+        L.gpis_adaptive_record_add_host.restype = None
         L.gpis_ws_default_params.argtypes = [vp]
         L.gpis_ws_default_params.restype = None
         L.gpis_ws_create.argtypes = [vp, vp, i32, ctypes.POINTER(vp)]
@@ -653,6 +678,36 @@ class Medium:
         if not want_segs:
             return rad
         return rad, d_seg.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
+
+    def render_scene_s_adaptive(self, scene, adaptive=None, want_hits=False, want_records=False):
+        """One frame of the Lambert driver under the reference's adaptive sample schedule (gpis_render_scene_s_adaptive) into zeroed
+        device buffers: (radiance_sum, sample_count[, hit_count][, records], info) — the float32 sum-of-radiance image and the uint32
+        samples per pixel to divide it by (height, width), the hits per pixel and the ADAPTIVE_RECORD array (ceil(height/4),
+        ceil(width/4)) when asked, and the ADAPTIVE_INFO record.  scene["spp_count"] is the average number of samples per pixel."""
+        import torch
+        scene = np.array(scene, dtype=SCENE_S).reshape(())
+        adaptive = np.array(default_adaptive_s() if adaptive is None else adaptive, dtype=ADAPTIVE_S).reshape(())
+        hgt, wid = int(scene["height"]), int(scene["width"])
+        vh, vw = (hgt + 3) // 4, (wid + 3) // 4
+        dev = torch.device("cuda", self.device)
+        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
+        d_cnt = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev)
+        d_hit = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_hits else None
+        d_rec = torch.zeros(max(vh * vw, 1) * ADAPTIVE_RECORD.itemsize, dtype=torch.uint8, device=dev) if want_records else None
+        info = np.zeros((), dtype=ADAPTIVE_INFO)
+        torch.cuda.synchronize(dev)
+        self.L.check(self.L.lib.gpis_render_scene_s_adaptive(self.h, _ptr(scene), _ptr(adaptive), ctypes.c_void_p(d_rad.data_ptr()),
+                                                             ctypes.c_void_p(d_cnt.data_ptr()), ctypes.c_void_p(d_hit.data_ptr()) if want_hits else None,
+                                                             ctypes.c_void_p(d_rec.data_ptr()) if want_records else None, _ptr(info), None),
+                     "gpis_render_scene_s_adaptive")
+        torch.cuda.synchronize(dev)
+        out = [d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy(), d_cnt.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()]
+        if want_hits:
+            out.append(d_hit.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy())
+        if want_records:
+            out.append(d_rec.cpu().numpy()[:vh * vw * ADAPTIVE_RECORD.itemsize].view(ADAPTIVE_RECORD).reshape(vh, vw).copy())
+        out.append(info)
+        return tuple(out)
 
     def mean_color_emission(self, points):
         """(color, emission) of the mean at double-precision points (n, 3)"""

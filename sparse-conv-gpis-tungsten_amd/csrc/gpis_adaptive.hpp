@@ -1,0 +1,85 @@
+// gpis_adaptive.hpp — the variable-count sample layout and the tile statistics of the adaptive frame drivers
+// (gpis_render_scene_s_adaptive in gpis_hip.hip; kernels and the host plan step in tu_adaptive.hip; include/gpis.h states the
+// contract and cites the reference).
+//   host + device: SampleRecord::addSample / errorEstimate (adaptive_add_sample, adaptive_error_estimate), the sample clamp of
+//       renderTile (adaptive_clamp), the 4x4 variance tile of a record clipped at the image edge (adaptive_tile);
+//   device: scene_sample_adaptive — the camera step of gpis_scene.hpp's scene_sample for a pass whose records carry different
+//       sample counts.  A driver that seeds its samples through it renders under the adaptive schedule; nothing else of its
+//       kernels changes.
+// Layout of a pass: records in index order; record r owns the samples [offset[r], offset[r+1]) = its pixels row-major x its
+// next_sample_count samples, so a pixel's samples stay contiguous (what the cooperative guided evaluator lives on).
+#pragma once
+#include <cmath>
+#include <cfloat>
+
+#include "gpis.h"
+#include "gpis_scene.hpp"
+
+#pragma clang fp contract(off)
+
+namespace gpis {
+
+constexpr uint32_t kVarianceTile = 4;       // PathTraceIntegrator::VarianceTileSize
+
+// what a pass's kernels read of a record: 16 bytes, uploaded once per pass (entry n_records holds the pass's sample total)
+struct AdaptivePlanRec {
+    uint64_t offset;                        // exclusive prefix sum of pixels * count over the records before
+    uint32_t sample_index, count;           // SampleRecord::sampleIndex, nextSampleCount
+};
+// the records [r0, r0 + nrec) of a pass as one chunk: its samples are [plan[r0].offset, plan[r0 + nrec].offset)
+struct AdaptiveChunk {
+    const AdaptivePlanRec *plan;
+    uint32_t r0, nrec;
+};
+
+struct AdaptiveTile { uint32_t x0, y0, w, h; };
+__host__ __device__ inline AdaptiveTile adaptive_tile(uint32_t width, uint32_t height, uint32_t r)
+{
+    const uint32_t vw = (width + kVarianceTile - 1) / kVarianceTile;
+    AdaptiveTile t;
+    t.x0 = (r % vw) * kVarianceTile; t.y0 = (r / vw) * kVarianceTile;
+    t.w = width - t.x0 < kVarianceTile ? width - t.x0 : kVarianceTile;
+    t.h = height - t.y0 < kVarianceTile ? height - t.y0 : kVarianceTile;
+    return t;
+}
+
+// SampleRecord::addSample(float), SampleRecord.hpp:44-50
+__host__ __device__ inline void adaptive_add_sample(gpis_adaptive_record &r, float x)
+{
+    r.sample_count++;
+    const float delta = x - r.mean;
+    r.mean += delta / (float)r.sample_count;
+    r.running_variance += delta * (x - r.mean);
+}
+// SampleRecord::variance / errorEstimate, :57-65 (max of MathUtil.hpp:26: a > b ? a : b)
+__host__ __device__ inline float adaptive_variance(const gpis_adaptive_record &r) { return r.running_variance / (float)(r.sample_count - 1u); }
+__host__ __device__ inline float adaptive_error_estimate(const gpis_adaptive_record &r)
+{
+    const float m2 = r.mean * r.mean;
+    return adaptive_variance(r) / ((float)r.sample_count * (m2 > 1e-3f ? m2 : 1e-3f));
+}
+// renderTile's clamp, PathTraceIntegrator.cpp:149-156: NaN, +-inf and values above 65536 count as 0
+__host__ __device__ inline float adaptive_clamp(float c) { return (!(fabsf(c) <= FLT_MAX) || c > 65536.f) ? 0.f : c; }
+
+// Sample i of a chunk -> its record, then its pixel, its sample index k and the sample's PCG32 stream, seeded as scene_sample seeds
+// the sample (x, y, k).  The record is the last one of the chunk whose offset is <= the sample's position in the pass.
+GPIS_DEV Pcg32 scene_sample_adaptive(const SceneConst &sc, const AdaptiveChunk &c, size_t i, uint32_t &x, uint32_t &y, uint32_t &spp)
+{
+    const gpis_scene_s &s = sc.s;
+    const uint64_t pos = c.plan[c.r0].offset + i;
+    uint32_t lo = c.r0, hi = c.r0 + c.nrec;           // plan[lo].offset <= pos < plan[hi].offset
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (c.plan[mid].offset <= pos) lo = mid; else hi = mid;
+    }
+    const AdaptivePlanRec rec = c.plan[lo];
+    const uint32_t local = (uint32_t)(pos - rec.offset);      // a record holds fewer than 2^32 samples (the entry checks)
+    const uint32_t p = local / rec.count;
+    const AdaptiveTile t = adaptive_tile(s.width, s.height, lo);
+    x = t.x0 + p % t.w; y = t.y0 + p / t.w;
+    spp = s.spp_begin + rec.sample_index + local % rec.count;
+    Pcg32 g;
+    g.set_state((uint64_t)(uint32_t)(xxhash32_4(x, y, spp, s.scene_seed) + 1u));
+    return g;
+}
+}   // namespace gpis

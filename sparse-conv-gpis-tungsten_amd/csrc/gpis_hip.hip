@@ -26,6 +26,7 @@
 #include "gpis_guide.hpp"     // GuideField, guide_free
 #include "gpis_launch.hpp"    // the march kernels live in the tu_*.hip translation units
 #include "gpis_scene.hpp"     // SceneConst, scene_pixel, sphere_chord: shared with the weight-space frame driver
+#include "gpis_adaptive.hpp"  // AdaptivePlanRec, AdaptiveChunk, adaptive_tile: the adaptive frame driver (kernels: tu_adaptive.hip)
 
 #pragma clang fp contract(off)
 
@@ -1103,14 +1104,14 @@ __global__ void __launch_bounds__(256) k_nee_paths_segs(SceneConst sc, size_t fi
 
 extern "C" const char *gpis_abi_sizes(void)
 {
-    static char buf[512];
+    static char buf[768];
     snprintf(buf, sizeof buf,
              "gpis_params=%zu,gpis_mean=%zu,gpis_ray_in=%zu,gpis_seg_out=%zu,gpis_cond_coeff=%zu,gpis_query=%zu,"
              "gpis_nee_query=%zu,gpis_derived=%zu,gpis_scene_s=%zu,gpis_surface_s=%zu,gpis_ramp=%zu,gpis_fs_state=%zu,gpis_guide_info=%zu,"
-             "gpis_ws_params=%zu,gpis_ws_query=%zu",
+             "gpis_ws_params=%zu,gpis_ws_query=%zu,gpis_adaptive_s=%zu,gpis_adaptive_record=%zu,gpis_adaptive_info=%zu",
              sizeof(gpis_params), sizeof(gpis_mean), sizeof(gpis_ray_in), sizeof(gpis_seg_out), sizeof(gpis_cond_coeff),
              sizeof(gpis_query), sizeof(gpis_nee_query), sizeof(gpis_derived), sizeof(gpis_scene_s), sizeof(gpis_surface_s), sizeof(gpis_ramp), sizeof(gpis_fs_state), sizeof(gpis_guide_info),
-             sizeof(gpis_ws_params), sizeof(gpis_ws_query));
+             sizeof(gpis_ws_params), sizeof(gpis_ws_query), sizeof(gpis_adaptive_s), sizeof(gpis_adaptive_record), sizeof(gpis_adaptive_info));
     return buf;
 }
 
@@ -2245,6 +2246,32 @@ struct LambertWs {
     size_t o_prim, o_us, o_v1;                         // offsets inside slot 3
     size_t o_cos, o_v2, o_vis, o_hit;                  // offsets inside slot 6
 };
+// The layout of a workspace for chunks of up to n samples (W.compact says of which body), and whether the device can hold it.
+static int lambert_ws_carve(gpis_medium *m, LambertWs &W, size_t n, bool &fits)
+{
+    const size_t ray_bytes = W.compact ? sizeof(SceneRay) : sizeof(gpis_ray_in), seg_bytes = W.compact ? sizeof(SceneHit) : sizeof(gpis_seg_out);
+    W.ns_max = n;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    W.o_prim = carve(n * ray_bytes);
+    W.o_us = W.o_v1 = 0;
+    if (!W.compact) { W.o_us = carve(n * 4); W.o_v1 = carve(n); }
+    W.b_prim = off;
+    W.b_seg = n * seg_bytes;
+    off = 0;
+    W.o_cos = carve(n * 4); W.o_v2 = carve(n); W.o_vis = carve(n); W.o_hit = carve(n);
+    W.b_shadow = off;
+    // what is still to be allocated must fit the free memory (with 1 GiB to spare)
+    const size_t have3 = stage_size(m, 3), have5 = stage_size(m, 5), have6 = stage_size(m, 6);
+    const size_t missing = (have3 >= W.b_prim ? 0 : W.b_prim) + (have5 >= W.b_seg ? 0 : W.b_seg) + (have6 >= W.b_shadow ? 0 : W.b_shadow);
+    fits = missing == 0;
+    if (fits) return GPIS_OK;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const size_t reclaim = (have3 >= W.b_prim ? 0 : have3) + (have5 >= W.b_seg ? 0 : have5) + (have6 >= W.b_shadow ? 0 : have6);   // freed on growth
+    fits = missing + ((size_t)1 << 30) <= free_b + reclaim;
+    return GPIS_OK;
+}
 // First-use policy: memory this process allocates for the first time costs 15-30 ms per GB on these boxes (DESIGN.md §6 "cold
 // frame"), so the whole-frame workspace (9.5 GB compact, 31 GB full) would add to the latency of a handle's FIRST frame.  That frame
 // therefore runs in 16 Mi-sample chunks (1.2 GB compact, 4 GB full; -4 % throughput); from the second call on — the handle is evidently reused — the workspace grows to
@@ -2264,25 +2291,9 @@ static int lambert_ws_plan(gpis_medium *m, const gpis_scene_s *s, size_t total_p
         W.chunk_pixels = ((size_t)1 << l) / s->spp_count;
         if (W.chunk_pixels < 1) W.chunk_pixels = 1;
         if (W.chunk_pixels > total_pixels) W.chunk_pixels = total_pixels;
-        const size_t n = W.ns_max = W.chunk_pixels * s->spp_count;
-        size_t off = 0;
-        auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-        W.o_prim = carve(n * ray_bytes);
-        W.o_us = W.o_v1 = 0;
-        if (!W.compact) { W.o_us = carve(n * 4); W.o_v1 = carve(n); }
-        W.b_prim = off;
-        W.b_seg = n * seg_bytes;
-        off = 0;
-        W.o_cos = carve(n * 4); W.o_v2 = carve(n); W.o_vis = carve(n); W.o_hit = carve(n);
-        W.b_shadow = off;
-        // what is still to be allocated must fit the free memory (with 1 GiB to spare), otherwise halve the chunk
-        const size_t have3 = stage_size(m, 3), have5 = stage_size(m, 5), have6 = stage_size(m, 6);
-        const size_t missing = (have3 >= W.b_prim ? 0 : W.b_prim) + (have5 >= W.b_seg ? 0 : W.b_seg) + (have6 >= W.b_shadow ? 0 : W.b_shadow);
-        if (missing == 0) return GPIS_OK;
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        const size_t reclaim = (have3 >= W.b_prim ? 0 : have3) + (have5 >= W.b_seg ? 0 : have5) + (have6 >= W.b_shadow ? 0 : have6);   // freed on growth
-        if (missing + ((size_t)1 << 30) <= free_b + reclaim) return GPIS_OK;
+        bool fits = false;
+        if (int rc = lambert_ws_carve(m, W, W.chunk_pixels * s->spp_count, fits)) return rc;
+        if (fits) return GPIS_OK;
         if (l <= 20) return set_err(GPIS_ERR_DEVICE, "scene driver: no memory for a 1 Mi-sample workspace");
     }
 }
@@ -2386,6 +2397,131 @@ extern "C" int gpis_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float 
         if ((rc = launch_check("k_scene_accumulate"))) return rc;
     }
     return ws_release(m, 0, st);
+}
+
+// gpis_render_scene_s under the reference's adaptive sample schedule (include/gpis.h; gpis_adaptive.hpp, tu_adaptive.hip).  Per pass:
+// the plan step on the host, its (offset, sample_index, count) table to the device, then per chunk of whole records the five stages of
+// gpis_render_scene_s — with the camera step and the pixel sum of the variable-count layout — and the tile statistics; the records
+// come back for the next plan step, which is the pass's one synchronisation.
+namespace {
+struct DeviceArray {                   // hipMalloc for the length of one call
+    void *p = nullptr;
+    ~DeviceArray() { if (p) (void)hipFree(p); }
+};
+}
+extern "C" int gpis_render_scene_s_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a, float *radiance_sum, uint32_t *sample_count,
+                                            uint32_t *hit_count, gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && a && radiance_sum && sample_count);
+    CHECK_ARGS(scene_args_ok(s));
+    CHECK_ARGS(s->y_begin == 0 && s->y_count == s->height && s->shard_count <= 1u);
+    CHECK_ARGS(a->spp_step > 0 && a->threshold >= 2);
+    std::lock_guard<std::mutex> lock(m->mu);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = (hipStream_t)stream;
+    const SceneConst sc = make_scene_const(s);
+    const uint32_t vw = (s->width + kVarianceTile - 1) / kVarianceTile, vh = (s->height + kVarianceTile - 1) / kVarianceTile;
+    const size_t n_rec = (size_t)vw * vh;
+    CHECK_ARGS(n_rec < 0xFFFFFFFFull);
+    std::vector<gpis_adaptive_record> rec(n_rec, gpis_adaptive_record{0, 0, 0, 0.f, 0.f, 0.f}), rec_dev(n_rec);
+    std::vector<AdaptivePlanRec> plan(n_rec + 1);
+    DeviceArray d_rec, d_plan;
+    HIP_TRY(hipMalloc(&d_rec.p, n_rec * sizeof(gpis_adaptive_record)));
+    HIP_TRY(hipMalloc(&d_plan.p, (n_rec + 1) * sizeof(AdaptivePlanRec)));
+    HIP_TRY(hipMemsetAsync(d_rec.p, 0, n_rec * sizeof(gpis_adaptive_record), st));
+    uint64_t rng = gpis_adaptive_rng_init_host(a, s->width, s->height);
+    gpis_adaptive_info done = {0, 0, 0};
+    const size_t chunk_max = (size_t)1 << 28;          // the largest GPIS_OPT_CHUNK_LOG2; one record may not hold more
+    int rc = GPIS_OK;
+    if ((rc = ws_acquire(m, 0, st))) return rc;
+    for (uint32_t cur = 0; cur < s->spp_count;) {
+        const uint32_t next = s->spp_count - cur < a->spp_step ? s->spp_count : cur + a->spp_step;
+        const int go = gpis_adaptive_plan_host(a, s->width, s->height, cur, next - cur, &rng, n_rec, rec.data());
+        if (go < 0) return go;
+        if (go == 0) { done.stopped_early = 1; break; }
+        size_t total = 0, largest = 0;
+        for (size_t r = 0; r < n_rec; ++r) {
+            const AdaptiveTile t = adaptive_tile(s->width, s->height, (uint32_t)r);
+            const size_t n = (size_t)t.w * t.h * rec[r].next_sample_count;
+            if (rec[r].next_sample_count == 0 || n > chunk_max)
+                return set_err(GPIS_ERR_UNSUPPORTED, "gpis_render_scene_s_adaptive: record %zu plans %u samples per pixel in one pass (1 .. 2^28 / 16)", r, rec[r].next_sample_count);
+            plan[r] = AdaptivePlanRec{total, rec[r].sample_index, rec[r].next_sample_count};
+            total += n;
+            if (n > largest) largest = n;
+        }
+        plan[n_rec] = AdaptivePlanRec{total, 0, 0};
+        // the workspace: chunks of 2^l samples (GPIS_OPT_CHUNK_LOG2, else the whole pass up to 2^27), halved until the device holds one;
+        // a record larger than that is a chunk of its own
+        LambertWs W;
+        W.compact = lambert_compact(m, m->guide.enabled != 0);
+        size_t chunk = 0;
+        for (int l = chunk_log2(m, 27);; --l) {
+            chunk = (size_t)1 << l;
+            if (chunk > total) chunk = total;
+            bool fits = false;
+            if ((rc = lambert_ws_carve(m, W, chunk > largest ? chunk : largest, fits))) return rc;
+            if (fits) break;
+            if (l <= 16 || chunk <= largest) return set_err(GPIS_ERR_DEVICE, "gpis_render_scene_s_adaptive: no memory for a workspace of %zu samples", W.ns_max);
+        }
+        HIP_TRY(hipMemcpyAsync(d_plan.p, plan.data(), (n_rec + 1) * sizeof(AdaptivePlanRec), hipMemcpyHostToDevice, st));
+        if ((rc = ensure_stage(m, 3, W.b_prim, true))) return rc;
+        if ((rc = ensure_stage(m, 5, W.b_seg, true))) return rc;
+        if ((rc = ensure_stage(m, 6, W.b_shadow, true))) return rc;
+        char *ws3 = (char *)m->stage[3], *ws6 = (char *)m->stage[6];
+        float *cosl = (float *)(ws6 + W.o_cos);
+        uint8_t *v2 = (uint8_t *)(ws6 + W.o_v2), *vis = (uint8_t *)(ws6 + W.o_vis), *hit = (uint8_t *)(ws6 + W.o_hit);
+        const launch::AdaptiveLambert arrays{cosl, v2, vis, hit};
+        for (size_t r0 = 0; r0 < n_rec;) {
+            size_t r1 = r0 + 1;                             // records [r0, r1): as many as the chunk holds, at least one
+            while (r1 < n_rec && plan[r1 + 1].offset - plan[r0].offset <= chunk) ++r1;
+            const size_t ns = (size_t)(plan[r1].offset - plan[r0].offset);
+            const AdaptiveChunk ch{(const AdaptivePlanRec *)d_plan.p, (uint32_t)r0, (uint32_t)(r1 - r0)};
+            if (W.compact) {
+                SceneRay *cray = (SceneRay *)(ws3 + W.o_prim);
+                SceneHit *chit = (SceneHit *)m->stage[5];
+                launch::adaptive_primary_compact(sc, ch, ns, cray, st);
+                if ((rc = launch_check("k_adaptive_primary_c"))) return rc;
+                if ((rc = scene_sample_distance_compact(m, ns, cray, chit, sc.s.cam_pos, st))) return rc;
+                k_scene_shade_c<<<grid_of(ns, 256), 256, 0, st>>>(sc, ns, cray, chit, cosl, v2, hit);
+                if ((rc = launch_check("k_scene_shade_c"))) return rc;
+                if ((rc = scene_transmittance_compact(m, ns, cray, sc.light, vis, st))) return rc;
+            } else {
+                gpis_ray_in *prim = (gpis_ray_in *)(ws3 + W.o_prim);
+                float *us = (float *)(ws3 + W.o_us);
+                uint8_t *v1 = (uint8_t *)(ws3 + W.o_v1);
+                gpis_seg_out *seg = (gpis_seg_out *)m->stage[5];
+                launch::adaptive_primary(sc, ch, ns, prim, us, v1, st);
+                if ((rc = launch_check("k_adaptive_primary"))) return rc;
+                if ((rc = sample_distance_impl(m, ns, prim, seg, nullptr, v1, st, MARCH_COHERENT, m->opt[GPIS_OPT_SCENE_EXIT_STATE] != 0))) return rc;
+                k_scene_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, ns, prim, seg, us, v1, prim, cosl, v2, hit);
+                if ((rc = launch_check("k_scene_shade"))) return rc;
+                if ((rc = transmittance_impl(m, ns, prim, vis, v2, st))) return rc;
+            }
+            launch::adaptive_accumulate(sc, ch, arrays, radiance_sum, sample_count, hit_count, st);
+            if ((rc = launch_check("k_adaptive_accumulate"))) return rc;
+            launch::adaptive_stats(sc, ch, arrays, (gpis_adaptive_record *)d_rec.p, st);
+            if ((rc = launch_check("k_adaptive_stats"))) return rc;
+            r0 = r1;
+        }
+        HIP_TRY(hipMemcpyAsync(rec_dev.data(), d_rec.p, n_rec * sizeof(gpis_adaptive_record), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t r = 0; r < n_rec; ++r) {                 // the device keeps the statistics, the host the schedule
+            rec[r].sample_count = rec_dev[r].sample_count;
+            rec[r].mean = rec_dev[r].mean;
+            rec[r].running_variance = rec_dev[r].running_variance;
+        }
+        ++done.passes_rendered;
+        done.samples += total;
+        cur = next;
+    }
+    if (!done.stopped_early)
+        for (size_t r = 0; r < n_rec; ++r)
+            rec[r].sample_index += rec[r].next_sample_count;
+    if ((rc = ws_release(m, 0, st))) return rc;
+    if (records) HIP_TRY(hipMemcpyAsync(records, rec.data(), n_rec * sizeof(gpis_adaptive_record), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (info) *info = done;
+    return GPIS_OK;
 }
 
 // The frame loop of the function-space scene-S drivers: per chunk of samples one fused launch over the resident set of the

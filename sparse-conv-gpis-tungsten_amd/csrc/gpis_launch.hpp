@@ -19,6 +19,7 @@ struct PersistArgs;
 struct SceneConst;
 struct SceneRay;
 struct SceneHit;
+struct AdaptiveChunk;
 
 // radix sort of (key, value) pairs (gpis_sort.hip); two-call convention: temp == nullptr only reports the scratch size
 hipError_t sort_pairs_u32(void *temp, size_t &temp_bytes, const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
@@ -133,6 +134,16 @@ void paths_rgb_nee_add(size_t n_samples, const PathsRgbArrays &a, const uint32_t
                        hipStream_t s);
 void paths_rgb_accumulate(const SceneConst &sc, size_t first_pixel, size_t n_pixels, const PathsRgbArrays &a, float *radiance_sum3, hipStream_t s);
 void paths_rgb_segs(const SceneConst &sc, size_t first_pixel, size_t n_pixels, const PathsRgbArrays &a, uint32_t *seg_count, hipStream_t s);
+// ---- adaptive sampling of the Lambert frame (tu_adaptive.hip; gpis_adaptive.hpp): the kernels around the marches of one chunk of records
+struct AdaptiveLambert {               // what the Lambert shade step and the shadow march leave per sample of a chunk
+    const float *cosl;
+    const uint8_t *valid2, *vis, *hit;
+};
+void adaptive_primary(const SceneConst &sc, const AdaptiveChunk &ch, size_t n_samples, gpis_ray_in *rays, float *u_shadow, uint8_t *valid, hipStream_t s);
+void adaptive_primary_compact(const SceneConst &sc, const AdaptiveChunk &ch, size_t n_samples, SceneRay *rays, hipStream_t s);
+void adaptive_accumulate(const SceneConst &sc, const AdaptiveChunk &ch, const AdaptiveLambert &a, float *radiance_sum, uint32_t *sample_count,
+                         uint32_t *hit_count, hipStream_t s);
+void adaptive_stats(const SceneConst &sc, const AdaptiveChunk &ch, const AdaptiveLambert &a, gpis_adaptive_record *records, hipStream_t s);
 inline unsigned grid_of(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 }   // namespace launch
