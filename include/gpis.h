@@ -759,6 +759,45 @@ uint64_t gpis_adaptive_rng_init_host(const gpis_adaptive_s *a, uint32_t width, u
  * (out2, may be NULL) — the statistics the device kernel and the plan step compute. */
 void gpis_adaptive_record_add_host(gpis_adaptive_record *rec, size_t n, const float *values, float *out2);
 
+/* gpis_render_scene_s_paths_rgb — the same RGB path estimator, sample for sample — under the sample schedule of
+ * gpis_render_scene_s_adaptive: what the reference's PathTraceIntegrator runs by default (traceSample into a Vec3f, spent by
+ * generateWork).  Sparse-convolution handles; s->spp_count is the AVERAGE number of samples per pixel, S.
+ * Pass loop, records, RNG: exactly those of gpis_render_scene_s_adaptive above — the plan step gpis_adaptive_plan_host, the start
+ * state gpis_adaptive_rng_init_host, record (x/4) + (y/4) * ceil(W/4); sample i of a record in a pass is
+ * k = s->spp_begin + sample_index + i, with the DIFFERENCE from the reference's `_currentSpp + i` stated there.
+ * A sample: (x, y, k) gives the em[3] and the segments gpis_render_scene_s_paths_rgb computes for the sample (x, y, k) — its
+ * arithmetic, draws and segment words, see that entry; with mean_emission enabled the extra last segment is marched too.
+ * Clamp (PathTraceIntegrator.cpp:149-156 on a Vec3f): if ANY component of em is NaN, +-infinite or > 65536, all three components
+ * count as 0, in the image and in the statistics.  A large negative finite component is kept (the reference keeps it).  The
+ * sample's segments still count in seg_count: they were marched.
+ * Statistics: SampleRecord::addSample(float) on the luminance of the clamped value (SampleRecord.hpp:52-55, Vec.hpp:218-222),
+ * ((c0 * 0.2126f) + (c1 * 0.7152f)) + (c2 * 0.0722f), every product and sum rounded to float (contraction off), in the order of
+ * gpis_render_scene_s_adaptive: the tile's pixels row-major, clipped at the image edge, then i.
+ * Image: per pixel, pass and channel the clamped samples are summed in i order from zero; that sum is ACCUMULATED once into
+ * radiance_sum3[3*(y*width+x)+c] (device pointer, 3*height*width floats), the count into sample_count[y*width+x], the segments
+ * marched (path plus shadow) into seg_count[y*width+x] (device pointers, height*width entries; seg_count may be NULL).
+ * records (device pointer, may be NULL) and info (host pointer, may be NULL) are filled as by gpis_render_scene_s_adaptive,
+ * including the closing sample_index += next_sample_count.
+ * Image, counts, records and info depend neither on how a pass is cut into chunks (GPIS_OPT_CHUNK_LOG2, default 2^25 samples as
+ * gpis_render_scene_s_paths_rgb; cuts fall between records, and a record larger than a chunk is a chunk of its own) nor on
+ * GPIS_OPT_PATHS_SORT / PATHS_PRESORT / MARCH_FORM / PERSISTENT.
+ * GPIS_ERR_INVALID_ARG, nothing written: max_path_bounces < 1, a NULL albedo (host pointer, 3 floats) / radiance_sum3 / a /
+ * sample_count, a weight-space handle, rows other than the whole image, shard_count > 1, spp_step == 0, threshold < 2,
+ * spp_count == 0.  GPIS_ERR_UNSUPPORTED: a plan that gives a record 0 or more than 2^28 samples in a pass.  GPIS_ERR_DEVICE: the
+ * device cannot hold the workspace of the smallest chunk.
+ * Consequences: with threshold >= S the schedule is uniform, and while nothing is clamped the image equals bit for bit the
+ * sequence of gpis_render_scene_s_paths_rgb calls with the passes' (spp_begin, spp_count) ranges accumulated into one buffer;
+ * without emission and with max_path_bounces = 1 every sample is zero: the first pass is rendered, then the plan step ends the
+ * frame (stopped_early = 1, passes_rendered = 1).
+ * The entry SYNCHRONISES `stream` once per pass and returns with the stream idle. */
+extern int gpis_render_scene_s_paths_rgb_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a,
+                                                  int max_path_bounces, const float albedo[3],
+                                                  float *radiance_sum3, uint32_t *sample_count, uint32_t *seg_count,
+                                                  gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
+/* host only, test surface: the Vec3f clamp and the luminance of gpis_render_scene_s_paths_rgb_adaptive on rgb_in[3*n] — the
+ * clamped values into rgb_out[3*n] and their luminances into luminance[n] (each may be NULL), by the functions the kernels call. */
+extern void gpis_adaptive_rgb_value_host(size_t n, const float *rgb_in, float *rgb_out, float *luminance);
+
 /* ---- weight-space GP medium (WeightSpaceGaussianProcessMedium.cpp, WeightSpaceGaussianProcess.cpp) --------------------
  * The field of one realization is  f(p) = sqrt(cov(p,p)) * (sqrt(2/N) * sum_i w_i cos((d_i . p) * omega_i + phi_i)) + mean(p)
  * with N random Fourier features of the squared-exponential covariance (WSG:120-127, 160-240).  A realization is fixed by the

@@ -354,6 +354,7 @@ class GpisLib:
         "gpis_ws_get_counters", "gpis_ws_reset_counters", "gpis_ws_render_scene_s", "gpis_ws_render_scene_s_paths",
         "gpis_fs_render_scene_s", "gpis_fs_render_scene_s_paths",
         "gpis_default_adaptive_s", "gpis_render_scene_s_adaptive", "gpis_adaptive_plan_host", "gpis_adaptive_rng_init_host", "gpis_adaptive_record_add_host",
+        "gpis_render_scene_s_paths_rgb_adaptive", "gpis_adaptive_rgb_value_host",
     ]
 
     def __init__(self, path=None):
@@ -440,6 +441,9 @@ class GpisLib:
         L.gpis_adaptive_rng_init_host.restype = ctypes.c_uint64
         L.gpis_adaptive_record_add_host.argtypes = [vp, sz, vp, vp]
         L.gpis_adaptive_record_add_host.restype = None
+        L.gpis_render_scene_s_paths_rgb_adaptive.argtypes = [vp, vp, vp, i32] + [vp] * 7
+        L.gpis_adaptive_rgb_value_host.argtypes = [sz, vp, vp, vp]
+        L.gpis_adaptive_rgb_value_host.restype = None
         L.gpis_ws_default_params.argtypes = [vp]
         L.gpis_ws_default_params.restype = None
         L.gpis_ws_create.argtypes = [vp, vp, i32, ctypes.POINTER(vp)]
@@ -704,6 +708,39 @@ class Medium:
         out = [d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy(), d_cnt.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()]
         if want_hits:
             out.append(d_hit.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy())
+        if want_records:
+            out.append(d_rec.cpu().numpy()[:vh * vw * ADAPTIVE_RECORD.itemsize].view(ADAPTIVE_RECORD).reshape(vh, vw).copy())
+        out.append(info)
+        return tuple(out)
+
+    def render_scene_s_paths_rgb_adaptive(self, scene, max_bounces, albedo, adaptive=None, want_segs=False, want_records=False):
+        """One frame of the RGB path driver under the reference's adaptive sample schedule (gpis_render_scene_s_paths_rgb_adaptive)
+        into zeroed device buffers: (radiance_sum, sample_count[, seg_count][, records], info) — the float32 sum-of-radiance image
+        (height, width, 3) and the uint32 samples per pixel to divide it by (height, width), the segments marched per pixel and the
+        ADAPTIVE_RECORD array (ceil(height/4), ceil(width/4)) when asked, and the ADAPTIVE_INFO record.  scene["spp_count"] is the
+        average number of samples per pixel.  A scalar `albedo` is broadcast to the three channels."""
+        import torch
+        scene = np.array(scene, dtype=SCENE_S).reshape(())
+        adaptive = np.array(default_adaptive_s() if adaptive is None else adaptive, dtype=ADAPTIVE_S).reshape(())
+        alb = np.ascontiguousarray(np.broadcast_to(np.asarray(albedo, dtype=np.float32), (3,)))
+        hgt, wid = int(scene["height"]), int(scene["width"])
+        vh, vw = (hgt + 3) // 4, (wid + 3) // 4
+        dev = torch.device("cuda", self.device)
+        d_rad = torch.zeros(max(3 * hgt * wid, 1), dtype=torch.float32, device=dev)
+        d_cnt = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev)
+        d_seg = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_segs else None
+        d_rec = torch.zeros(max(vh * vw, 1) * ADAPTIVE_RECORD.itemsize, dtype=torch.uint8, device=dev) if want_records else None
+        info = np.zeros((), dtype=ADAPTIVE_INFO)
+        torch.cuda.synchronize(dev)
+        self.L.check(self.L.lib.gpis_render_scene_s_paths_rgb_adaptive(self.h, _ptr(scene), _ptr(adaptive), int(max_bounces), _ptr(alb),
+                                                                       ctypes.c_void_p(d_rad.data_ptr()), ctypes.c_void_p(d_cnt.data_ptr()),
+                                                                       ctypes.c_void_p(d_seg.data_ptr()) if want_segs else None,
+                                                                       ctypes.c_void_p(d_rec.data_ptr()) if want_records else None, _ptr(info), None),
+                     "gpis_render_scene_s_paths_rgb_adaptive")
+        torch.cuda.synchronize(dev)
+        out = [d_rad.cpu().numpy()[:3 * hgt * wid].reshape(hgt, wid, 3).copy(), d_cnt.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()]
+        if want_segs:
+            out.append(d_seg.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy())
         if want_records:
             out.append(d_rec.cpu().numpy()[:vh * vw * ADAPTIVE_RECORD.itemsize].view(ADAPTIVE_RECORD).reshape(vh, vw).copy())
         out.append(info)

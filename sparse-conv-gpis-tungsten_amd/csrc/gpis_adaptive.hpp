@@ -1,8 +1,9 @@
 // gpis_adaptive.hpp — the variable-count sample layout and the tile statistics of the adaptive frame drivers
-// (gpis_render_scene_s_adaptive in gpis_hip.hip; kernels and the host plan step in tu_adaptive.hip; include/gpis.h states the
-// contract and cites the reference).
+// (gpis_render_scene_s_adaptive and gpis_render_scene_s_paths_rgb_adaptive in gpis_hip.hip; kernels in tu_adaptive.hip and
+// tu_adaptive_paths.hip, the host plan step in tu_adaptive.hip; include/gpis.h states the contract and cites the reference).
 //   host + device: SampleRecord::addSample / errorEstimate (adaptive_add_sample, adaptive_error_estimate), the sample clamp of
-//       renderTile (adaptive_clamp), the 4x4 variance tile of a record clipped at the image edge (adaptive_tile);
+//       renderTile on a float and on a Vec3f (adaptive_clamp, adaptive_rgb_clamped), Vec3f::luminance (adaptive_luminance), the 4x4
+//       variance tile of a record clipped at the image edge (adaptive_tile);
 //   device: scene_sample_adaptive — the camera step of gpis_scene.hpp's scene_sample for a pass whose records carry different
 //       sample counts.  A driver that seeds its samples through it renders under the adaptive schedule; nothing else of its
 //       kernels changes.
@@ -60,6 +61,13 @@ __host__ __device__ inline float adaptive_error_estimate(const gpis_adaptive_rec
 }
 // renderTile's clamp, PathTraceIntegrator.cpp:149-156: NaN, +-inf and values above 65536 count as 0
 __host__ __device__ inline float adaptive_clamp(float c) { return (!(fabsf(c) <= FLT_MAX) || c > 65536.f) ? 0.f : c; }
+// the same clamp on a Vec3f sample: one NaN, infinite or > 65536 component makes all three count as 0
+__host__ __device__ inline bool adaptive_rgb_clamped(float c0, float c1, float c2)
+{
+    return !(fabsf(c0) <= FLT_MAX) || !(fabsf(c1) <= FLT_MAX) || !(fabsf(c2) <= FLT_MAX) || c0 > 65536.f || c1 > 65536.f || c2 > 65536.f;
+}
+// Vec3f::luminance, Vec.hpp:218-222: what SampleRecord::addSample(const Vec3f &) hands addSample(float), SampleRecord.hpp:52-55
+__host__ __device__ inline float adaptive_luminance(float c0, float c1, float c2) { return ((c0 * 0.2126f) + (c1 * 0.7152f)) + (c2 * 0.0722f); }
 
 // Sample i of a chunk -> its record, then its pixel, its sample index k and the sample's PCG32 stream, seeded as scene_sample seeds
 // the sample (x, y, k).  The record is the last one of the chunk whose offset is <= the sample's position in the pass.

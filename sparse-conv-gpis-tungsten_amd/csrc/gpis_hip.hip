@@ -2399,30 +2399,37 @@ extern "C" int gpis_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float 
     return ws_release(m, 0, st);
 }
 
-// gpis_render_scene_s under the reference's adaptive sample schedule (include/gpis.h; gpis_adaptive.hpp, tu_adaptive.hip).  Per pass:
-// the plan step on the host, its (offset, sample_index, count) table to the device, then per chunk of whole records the five stages of
-// gpis_render_scene_s — with the camera step and the pixel sum of the variable-count layout — and the tile statistics; the records
-// come back for the next plan step, which is the pass's one synchronisation.
+// The pass loop of the adaptive frame drivers (include/gpis.h at gpis_render_scene_s_adaptive; gpis_adaptive.hpp, tu_adaptive.hip).  Per
+// pass: the plan step on the host, its (offset, sample_index, count) table to the device, then chunks of whole records through the
+// driver's own stages, which end with its tile statistics into the device records; the records come back for the next plan step,
+// which is the pass's one synchronisation.  The driver passes
+//   size(n, fits): lay out (and, if it wants, allocate) its workspace for chunks of up to n samples; fits = the device holds it;
+//   bind():        called once per pass after the table's upload: allocate what `size` planned and take the pointers;
+//   render(ch, ns, d_records): the stages of the chunk `ch` of ns samples.
+// Chunks hold 2^l samples (GPIS_OPT_CHUNK_LOG2, else default_log2, at most the pass), halved until the device holds the workspace;
+// a record larger than that is a chunk of its own.  The entry has checked the arguments of its own; `entry` names it in messages.
 namespace {
 struct DeviceArray {                   // hipMalloc for the length of one call
     void *p = nullptr;
     ~DeviceArray() { if (p) (void)hipFree(p); }
 };
 }
-extern "C" int gpis_render_scene_s_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a, float *radiance_sum, uint32_t *sample_count,
-                                            uint32_t *hit_count, gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream)
+template <typename Size, typename Bind, typename Render>
+static int adaptive_passes(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a, int default_log2, const char *entry, hipStream_t st,
+                           gpis_adaptive_record *records, gpis_adaptive_info *info, Size size, Bind bind, Render render)
 {
-    CHECK_ARGS(std_handle(m) && s && a && radiance_sum && sample_count);
-    CHECK_ARGS(scene_args_ok(s));
-    CHECK_ARGS(s->y_begin == 0 && s->y_count == s->height && s->shard_count <= 1u);
-    CHECK_ARGS(a->spp_step > 0 && a->threshold >= 2);
-    std::lock_guard<std::mutex> lock(m->mu);
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = (hipStream_t)stream;
-    const SceneConst sc = make_scene_const(s);
     const uint32_t vw = (s->width + kVarianceTile - 1) / kVarianceTile, vh = (s->height + kVarianceTile - 1) / kVarianceTile;
     const size_t n_rec = (size_t)vw * vh;
-    CHECK_ARGS(n_rec < 0xFFFFFFFFull);
+#define ADAPTIVE_ARGS(cond)                                                                                        \
+    do {                                                                                                           \
+        if (!(cond)) return set_err(GPIS_ERR_INVALID_ARG, "%s: invalid argument (%s)", entry, #cond);              \
+    } while (0)
+    ADAPTIVE_ARGS(s->y_begin == 0 && s->y_count == s->height && s->shard_count <= 1u);
+    ADAPTIVE_ARGS(a->spp_step > 0 && a->threshold >= 2);
+    ADAPTIVE_ARGS(n_rec < 0xFFFFFFFFull);
+#undef ADAPTIVE_ARGS
+    std::lock_guard<std::mutex> lock(m->mu);
+    HIP_TRY(hipSetDevice(m->device));
     std::vector<gpis_adaptive_record> rec(n_rec, gpis_adaptive_record{0, 0, 0, 0.f, 0.f, 0.f}), rec_dev(n_rec);
     std::vector<AdaptivePlanRec> plan(n_rec + 1);
     DeviceArray d_rec, d_plan;
@@ -2444,63 +2451,30 @@ extern "C" int gpis_render_scene_s_adaptive(gpis_medium *m, const gpis_scene_s *
             const AdaptiveTile t = adaptive_tile(s->width, s->height, (uint32_t)r);
             const size_t n = (size_t)t.w * t.h * rec[r].next_sample_count;
             if (rec[r].next_sample_count == 0 || n > chunk_max)
-                return set_err(GPIS_ERR_UNSUPPORTED, "gpis_render_scene_s_adaptive: record %zu plans %u samples per pixel in one pass (1 .. 2^28 / 16)", r, rec[r].next_sample_count);
+                return set_err(GPIS_ERR_UNSUPPORTED, "%s: record %zu plans %u samples per pixel in one pass (1 .. 2^28 / 16)", entry, r, rec[r].next_sample_count);
             plan[r] = AdaptivePlanRec{total, rec[r].sample_index, rec[r].next_sample_count};
             total += n;
             if (n > largest) largest = n;
         }
         plan[n_rec] = AdaptivePlanRec{total, 0, 0};
-        // the workspace: chunks of 2^l samples (GPIS_OPT_CHUNK_LOG2, else the whole pass up to 2^27), halved until the device holds one;
-        // a record larger than that is a chunk of its own
-        LambertWs W;
-        W.compact = lambert_compact(m, m->guide.enabled != 0);
         size_t chunk = 0;
-        for (int l = chunk_log2(m, 27);; --l) {
+        for (int l = chunk_log2(m, default_log2);; --l) {
             chunk = (size_t)1 << l;
             if (chunk > total) chunk = total;
+            const size_t ns_max = chunk > largest ? chunk : largest;
             bool fits = false;
-            if ((rc = lambert_ws_carve(m, W, chunk > largest ? chunk : largest, fits))) return rc;
+            if ((rc = size(ns_max, fits))) return rc;
             if (fits) break;
-            if (l <= 16 || chunk <= largest) return set_err(GPIS_ERR_DEVICE, "gpis_render_scene_s_adaptive: no memory for a workspace of %zu samples", W.ns_max);
+            if (l <= 16 || chunk <= largest) return set_err(GPIS_ERR_DEVICE, "%s: no memory for a workspace of %zu samples", entry, ns_max);
         }
         HIP_TRY(hipMemcpyAsync(d_plan.p, plan.data(), (n_rec + 1) * sizeof(AdaptivePlanRec), hipMemcpyHostToDevice, st));
-        if ((rc = ensure_stage(m, 3, W.b_prim, true))) return rc;
-        if ((rc = ensure_stage(m, 5, W.b_seg, true))) return rc;
-        if ((rc = ensure_stage(m, 6, W.b_shadow, true))) return rc;
-        char *ws3 = (char *)m->stage[3], *ws6 = (char *)m->stage[6];
-        float *cosl = (float *)(ws6 + W.o_cos);
-        uint8_t *v2 = (uint8_t *)(ws6 + W.o_v2), *vis = (uint8_t *)(ws6 + W.o_vis), *hit = (uint8_t *)(ws6 + W.o_hit);
-        const launch::AdaptiveLambert arrays{cosl, v2, vis, hit};
+        if ((rc = bind())) return rc;
         for (size_t r0 = 0; r0 < n_rec;) {
             size_t r1 = r0 + 1;                             // records [r0, r1): as many as the chunk holds, at least one
             while (r1 < n_rec && plan[r1 + 1].offset - plan[r0].offset <= chunk) ++r1;
             const size_t ns = (size_t)(plan[r1].offset - plan[r0].offset);
             const AdaptiveChunk ch{(const AdaptivePlanRec *)d_plan.p, (uint32_t)r0, (uint32_t)(r1 - r0)};
-            if (W.compact) {
-                SceneRay *cray = (SceneRay *)(ws3 + W.o_prim);
-                SceneHit *chit = (SceneHit *)m->stage[5];
-                launch::adaptive_primary_compact(sc, ch, ns, cray, st);
-                if ((rc = launch_check("k_adaptive_primary_c"))) return rc;
-                if ((rc = scene_sample_distance_compact(m, ns, cray, chit, sc.s.cam_pos, st))) return rc;
-                k_scene_shade_c<<<grid_of(ns, 256), 256, 0, st>>>(sc, ns, cray, chit, cosl, v2, hit);
-                if ((rc = launch_check("k_scene_shade_c"))) return rc;
-                if ((rc = scene_transmittance_compact(m, ns, cray, sc.light, vis, st))) return rc;
-            } else {
-                gpis_ray_in *prim = (gpis_ray_in *)(ws3 + W.o_prim);
-                float *us = (float *)(ws3 + W.o_us);
-                uint8_t *v1 = (uint8_t *)(ws3 + W.o_v1);
-                gpis_seg_out *seg = (gpis_seg_out *)m->stage[5];
-                launch::adaptive_primary(sc, ch, ns, prim, us, v1, st);
-                if ((rc = launch_check("k_adaptive_primary"))) return rc;
-                if ((rc = sample_distance_impl(m, ns, prim, seg, nullptr, v1, st, MARCH_COHERENT, m->opt[GPIS_OPT_SCENE_EXIT_STATE] != 0))) return rc;
-                k_scene_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, ns, prim, seg, us, v1, prim, cosl, v2, hit);
-                if ((rc = launch_check("k_scene_shade"))) return rc;
-                if ((rc = transmittance_impl(m, ns, prim, vis, v2, st))) return rc;
-            }
-            launch::adaptive_accumulate(sc, ch, arrays, radiance_sum, sample_count, hit_count, st);
-            if ((rc = launch_check("k_adaptive_accumulate"))) return rc;
-            launch::adaptive_stats(sc, ch, arrays, (gpis_adaptive_record *)d_rec.p, st);
-            if ((rc = launch_check("k_adaptive_stats"))) return rc;
+            if ((rc = render(ch, ns, (gpis_adaptive_record *)d_rec.p))) return rc;
             r0 = r1;
         }
         HIP_TRY(hipMemcpyAsync(rec_dev.data(), d_rec.p, n_rec * sizeof(gpis_adaptive_record), hipMemcpyDeviceToHost, st));
@@ -2522,6 +2496,66 @@ extern "C" int gpis_render_scene_s_adaptive(gpis_medium *m, const gpis_scene_s *
     HIP_TRY(hipStreamSynchronize(st));
     if (info) *info = done;
     return GPIS_OK;
+}
+
+// gpis_render_scene_s under the reference's adaptive sample schedule: per chunk of whole records the five stages of gpis_render_scene_s
+// — with the camera step and the pixel sum of the variable-count layout — and the tile statistics.
+extern "C" int gpis_render_scene_s_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a, float *radiance_sum, uint32_t *sample_count,
+                                            uint32_t *hit_count, gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && a && radiance_sum && sample_count);
+    CHECK_ARGS(scene_args_ok(s));
+    hipStream_t st = (hipStream_t)stream;
+    const SceneConst sc = make_scene_const(s);
+    LambertWs W;
+    char *ws3 = nullptr;
+    float *cosl = nullptr;
+    uint8_t *v2 = nullptr, *vis = nullptr, *hit = nullptr;
+    return adaptive_passes(
+        m, s, a, 27, __func__, st, records, info,
+        [&](size_t n, bool &fits) {
+            W.compact = lambert_compact(m, m->guide.enabled != 0);
+            return lambert_ws_carve(m, W, n, fits);
+        },
+        [&]() {
+            if (int rc = ensure_stage(m, 3, W.b_prim, true)) return rc;
+            if (int rc = ensure_stage(m, 5, W.b_seg, true)) return rc;
+            if (int rc = ensure_stage(m, 6, W.b_shadow, true)) return rc;
+            char *ws6 = (char *)m->stage[6];
+            ws3 = (char *)m->stage[3];
+            cosl = (float *)(ws6 + W.o_cos);
+            v2 = (uint8_t *)(ws6 + W.o_v2); vis = (uint8_t *)(ws6 + W.o_vis); hit = (uint8_t *)(ws6 + W.o_hit);
+            return (int)GPIS_OK;
+        },
+        [&](const AdaptiveChunk &ch, size_t ns, gpis_adaptive_record *d_records) {
+            int rc = GPIS_OK;
+            if (W.compact) {
+                SceneRay *cray = (SceneRay *)(ws3 + W.o_prim);
+                SceneHit *chit = (SceneHit *)m->stage[5];
+                launch::adaptive_primary_compact(sc, ch, ns, cray, st);
+                if ((rc = launch_check("k_adaptive_primary_c"))) return rc;
+                if ((rc = scene_sample_distance_compact(m, ns, cray, chit, sc.s.cam_pos, st))) return rc;
+                k_scene_shade_c<<<grid_of(ns, 256), 256, 0, st>>>(sc, ns, cray, chit, cosl, v2, hit);
+                if ((rc = launch_check("k_scene_shade_c"))) return rc;
+                if ((rc = scene_transmittance_compact(m, ns, cray, sc.light, vis, st))) return rc;
+            } else {
+                gpis_ray_in *prim = (gpis_ray_in *)(ws3 + W.o_prim);
+                float *us = (float *)(ws3 + W.o_us);
+                uint8_t *v1 = (uint8_t *)(ws3 + W.o_v1);
+                gpis_seg_out *seg = (gpis_seg_out *)m->stage[5];
+                launch::adaptive_primary(sc, ch, ns, prim, us, v1, st);
+                if ((rc = launch_check("k_adaptive_primary"))) return rc;
+                if ((rc = sample_distance_impl(m, ns, prim, seg, nullptr, v1, st, MARCH_COHERENT, m->opt[GPIS_OPT_SCENE_EXIT_STATE] != 0))) return rc;
+                k_scene_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, ns, prim, seg, us, v1, prim, cosl, v2, hit);
+                if ((rc = launch_check("k_scene_shade"))) return rc;
+                if ((rc = transmittance_impl(m, ns, prim, vis, v2, st))) return rc;
+            }
+            const launch::AdaptiveLambert arrays{cosl, v2, vis, hit};
+            launch::adaptive_accumulate(sc, ch, arrays, radiance_sum, sample_count, hit_count, st);
+            if ((rc = launch_check("k_adaptive_accumulate"))) return rc;
+            launch::adaptive_stats(sc, ch, arrays, d_records, st);
+            return launch_check("k_adaptive_stats");
+        });
 }
 
 // The frame loop of the function-space scene-S drivers: per chunk of samples one fused launch over the resident set of the
@@ -2597,13 +2631,112 @@ extern "C" int gpis_fs_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *
 // The loop owns the arrays the marches read and write (PathsFrame); the driver carves its own path state into the same workspace
 // (`state`, called before the allocation with the carving function and the chunk's samples) and takes its pointers from it
 // (`bind`).  Segments 0 .. n_marched - 1 are marched; next-event estimation follows the first n_nee of them.  Every callback
-// launches and returns its launch_check.
+// launches and returns its launch_check.  The workspace layout (lambert_paths_carve, lambert_paths_bind) and the body of one chunk
+// (lambert_paths_chunk) are functions of their own: the pass loop of gpis_render_scene_s_paths_rgb_adaptive runs the same code.
 struct PathsFrame {
     char *ws;                          // stage[3]: the driver's arrays lie at the offsets its `state` carved
     gpis_ray_in *rays, *shadow;        // current segment of every path; the shadow segments of the bounce (by batch slot)
     gpis_seg_out *seg;
     uint8_t *alive, *nee, *vis;
 };
+// The layout of stage[3] for chunks of up to ns_max samples: the frame's arrays, the driver's own (carved by `state` between them)
+// and, when the secondary segments are regrouped, the sort's.
+struct PathsWs {
+    size_t bytes;
+    size_t o_rays, o_seg, o_sh, o_alive, o_nee, o_vis;
+    bool regroup, presort;
+    size_t sort_temp_bytes;
+    size_t o_keys, o_vals, o_keys2, o_order, o_rsorted, o_live, o_temp, o_order2, o_live2;
+};
+template <typename State>
+static int lambert_paths_carve(gpis_medium *m, int n_marched, size_t ns_max, hipStream_t st, State state, PathsWs &W)
+{
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    W.o_rays = carve(ns_max * sizeof(gpis_ray_in)); W.o_seg = carve(ns_max * sizeof(gpis_seg_out)); W.o_sh = carve(ns_max * sizeof(gpis_ray_in));
+    state(carve, ns_max);
+    W.o_alive = carve(ns_max); W.o_nee = carve(ns_max); W.o_vis = carve(ns_max);
+    // regrouping of secondary segments (GPIS_PATHS_SORT=0 keeps the sample order: results are identical)
+    W.regroup = m->opt[GPIS_OPT_PATHS_SORT] != 0 && n_marched > 1;
+    W.presort = m->opt[GPIS_OPT_PATHS_PRESORT] != 0;
+    W.sort_temp_bytes = 0;
+    W.o_keys = W.o_vals = W.o_keys2 = W.o_order = W.o_rsorted = W.o_live = W.o_temp = W.o_order2 = W.o_live2 = 0;
+    if (W.regroup) {
+        if (sort_pairs_u32(nullptr, W.sort_temp_bytes, nullptr, nullptr, nullptr, nullptr, ns_max, st) != hipSuccess)
+            return set_err(GPIS_ERR_DEVICE, "radix sort scratch query failed");
+        W.o_keys = carve(ns_max * 4); W.o_vals = carve(ns_max * 4); W.o_keys2 = carve(ns_max * 4); W.o_order = carve(ns_max * 4);
+        W.o_rsorted = carve(ns_max * sizeof(gpis_ray_in)); W.o_live = carve(ns_max); W.o_temp = carve(W.sort_temp_bytes);
+        W.o_order2 = carve(ns_max * 4); W.o_live2 = carve(ns_max);
+    }
+    W.bytes = off;
+    return GPIS_OK;
+}
+// the frame's arrays in stage[3], which holds W.bytes
+static PathsFrame lambert_paths_bind(gpis_medium *m, const PathsWs &W)
+{
+    char *ws = (char *)m->stage[3];
+    PathsFrame f;
+    f.ws = ws;
+    f.rays = (gpis_ray_in *)(ws + W.o_rays); f.seg = (gpis_seg_out *)(ws + W.o_seg); f.shadow = (gpis_ray_in *)(ws + W.o_sh);
+    f.alive = (uint8_t *)(ws + W.o_alive); f.nee = (uint8_t *)(ws + W.o_nee); f.vis = (uint8_t *)(ws + W.o_vis);
+    return f;
+}
+// One chunk of ns samples: `begin` (the driver's camera step), the bounce loop, `finish` (its sums).
+template <typename Begin, typename Shade, typename NeeAdd, typename Finish>
+static int lambert_paths_chunk(gpis_medium *m, const PathsWs &W, const PathsFrame &f, size_t ns, int n_marched, int n_nee, hipStream_t st, Begin begin,
+                               Shade shade, NeeAdd nee_add, Finish finish)
+{
+    char *ws = f.ws;
+    uint32_t *keys = (uint32_t *)(ws + W.o_keys), *vals = (uint32_t *)(ws + W.o_vals), *keys2 = (uint32_t *)(ws + W.o_keys2), *order = (uint32_t *)(ws + W.o_order);
+    gpis_ray_in *rays_sorted = (gpis_ray_in *)(ws + W.o_rsorted);
+    uint8_t *live_sorted = (uint8_t *)(ws + W.o_live), *live2 = (uint8_t *)(ws + W.o_live2);
+    uint32_t *order2 = (uint32_t *)(ws + W.o_order2);
+    const DevModel &H = m->host_model;
+    const float cell_size = H.iso3d ? (H.radius_iso > 0.f ? H.radius_iso : H.kernel_scale) : (H.radius_world > 0.f ? H.radius_world : 0.1f);
+    const bool regroup = W.regroup, presort = W.presort;
+    const size_t sort_temp_bytes = W.sort_temp_bytes, o_temp = W.o_temp;
+    int rc = GPIS_OK;
+    if ((rc = begin())) return rc;
+    for (int bounce = 0; bounce < n_marched; ++bounce) {
+        // primary segments are coherent as generated (consecutive spp of a pixel); later ones are regrouped
+        // Secondary segments are regrouped here by start cell (compaction + locality of the guide steps;
+        // GPIS_PATHS_PRESORT=0 skips it when the wavefront march runs, which regroups the exact work
+        // itself).  Measured at 4 bounces, C1 1080p x16: sample order + resident march 22.1 M paths/s,
+        // regrouped + resident 40.4, wavefront march alone 56.7, regrouped + wavefront 61.3.
+        const bool wave = bounce > 0 && m->guide.enabled && wave_march_selected(m, MARCH_SCATTERED);
+        const bool sorted = regroup && bounce > 0 && (!wave || presort);
+        const int hint = bounce > 0 ? MARCH_SCATTERED : MARCH_COHERENT;
+        // src rays + mask -> order, regrouped copy, live flags of the regrouped slots
+        auto regroup_batch = [&](const gpis_ray_in *src, const uint8_t *mask, uint32_t *ord, gpis_ray_in *dst, uint8_t *live_out) -> int {
+            k_paths_keys<<<grid_of(ns, 256), 256, 0, st>>>(m->d_model, cell_size, ns, src, mask, keys, vals);
+            int r = launch_check("k_paths_keys");
+            if (r) return r;
+            size_t tb = sort_temp_bytes;
+            if (sort_pairs_u32(ws + o_temp, tb, keys, keys2, vals, ord, ns, st) != hipSuccess)
+                return set_err(GPIS_ERR_DEVICE, "radix sort failed");
+            k_paths_gather<<<grid_of(ns, 256), 256, 0, st>>>(ns, keys2, ord, src, dst, live_out);
+            return launch_check("k_paths_gather");
+        };
+        if (sorted && (rc = regroup_batch(f.rays, f.alive, order, rays_sorted, live_sorted))) return rc;
+        const gpis_ray_in *rays_in = sorted ? rays_sorted : f.rays;
+        const uint8_t *live = sorted ? live_sorted : f.alive;
+        if ((rc = sample_distance_impl(m, ns, rays_in, f.seg, nullptr, live, st, hint))) return rc;
+        if ((rc = shade(bounce, ns, sorted ? order : nullptr, rays_in, sorted ? live_sorted : nullptr))) return rc;
+        if (bounce >= n_nee)
+            continue;
+        if (sorted) {
+            // the shadow segments share one direction but start where the bounce segments ended: regroup
+            // them by their own lattice cells (the bounce batch's copy of the rays is free again)
+            if ((rc = regroup_batch(f.shadow, f.nee, order2, rays_sorted, live2))) return rc;
+            if ((rc = transmittance_impl(m, ns, rays_sorted, f.vis, live2, st, hint))) return rc;
+            if ((rc = nee_add(ns, order, order2, live2))) return rc;
+        } else {
+            if ((rc = transmittance_impl(m, ns, f.shadow, f.vis, f.nee, st, hint))) return rc;
+            if ((rc = nee_add(ns, nullptr, nullptr, nullptr))) return rc;
+        }
+    }
+    return finish();
+}
 template <typename State, typename Bind, typename Begin, typename Shade, typename NeeAdd, typename Finish>
 static int lambert_paths_frames(gpis_medium *m, const gpis_scene_s *s, int n_marched, int n_nee, hipStream_t st, State state, Bind bind, Begin begin,
                                 Shade shade, NeeAdd nee_add, Finish finish)
@@ -2614,82 +2747,18 @@ static int lambert_paths_frames(gpis_medium *m, const gpis_scene_s *s, int n_mar
     size_t chunk_pixels = ((size_t)1 << chunk_log2(m, 25)) / s->spp_count;
     if (chunk_pixels < 1) chunk_pixels = 1;
     if (chunk_pixels > total_pixels) chunk_pixels = total_pixels;
-    const size_t ns_max = chunk_pixels * s->spp_count;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    size_t o_rays = carve(ns_max * sizeof(gpis_ray_in)), o_seg = carve(ns_max * sizeof(gpis_seg_out)), o_sh = carve(ns_max * sizeof(gpis_ray_in));
-    state(carve, ns_max);
-    size_t o_alive = carve(ns_max), o_nee = carve(ns_max), o_vis = carve(ns_max);
-    // regrouping of secondary segments (GPIS_PATHS_SORT=0 keeps the sample order: results are identical)
-    const bool regroup = m->opt[GPIS_OPT_PATHS_SORT] != 0 && n_marched > 1;
-    const bool presort = m->opt[GPIS_OPT_PATHS_PRESORT] != 0;
-    size_t sort_temp_bytes = 0;
-    size_t o_keys = 0, o_vals = 0, o_keys2 = 0, o_order = 0, o_rsorted = 0, o_live = 0, o_temp = 0, o_order2 = 0, o_live2 = 0;
-    if (regroup) {
-        if (sort_pairs_u32(nullptr, sort_temp_bytes, nullptr, nullptr, nullptr, nullptr, ns_max, st) != hipSuccess)
-            return set_err(GPIS_ERR_DEVICE, "radix sort scratch query failed");
-        o_keys = carve(ns_max * 4); o_vals = carve(ns_max * 4); o_keys2 = carve(ns_max * 4); o_order = carve(ns_max * 4);
-        o_rsorted = carve(ns_max * sizeof(gpis_ray_in)); o_live = carve(ns_max); o_temp = carve(sort_temp_bytes);
-        o_order2 = carve(ns_max * 4); o_live2 = carve(ns_max);
-    }
-    int rc = ensure_stage(m, 3, off);
+    PathsWs W;
+    int rc = lambert_paths_carve(m, n_marched, chunk_pixels * s->spp_count, st, state, W);
     if (rc) return rc;
+    if ((rc = ensure_stage(m, 3, W.bytes))) return rc;
     if ((rc = ws_acquire(m, 0, st))) return rc;
-    char *ws = (char *)m->stage[3];
-    uint32_t *keys = (uint32_t *)(ws + o_keys), *vals = (uint32_t *)(ws + o_vals), *keys2 = (uint32_t *)(ws + o_keys2), *order = (uint32_t *)(ws + o_order);
-    gpis_ray_in *rays_sorted = (gpis_ray_in *)(ws + o_rsorted);
-    uint8_t *live_sorted = (uint8_t *)(ws + o_live), *live2 = (uint8_t *)(ws + o_live2);
-    uint32_t *order2 = (uint32_t *)(ws + o_order2);
-    const DevModel &H = m->host_model;
-    const float cell_size = H.iso3d ? (H.radius_iso > 0.f ? H.radius_iso : H.kernel_scale) : (H.radius_world > 0.f ? H.radius_world : 0.1f);
-    PathsFrame f;
-    f.ws = ws;
-    f.rays = (gpis_ray_in *)(ws + o_rays); f.seg = (gpis_seg_out *)(ws + o_seg); f.shadow = (gpis_ray_in *)(ws + o_sh);
-    f.alive = (uint8_t *)(ws + o_alive); f.nee = (uint8_t *)(ws + o_nee); f.vis = (uint8_t *)(ws + o_vis);
+    const PathsFrame f = lambert_paths_bind(m, W);
     bind(f);
     for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
         size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
         size_t ns = np * s->spp_count;
-        if ((rc = begin(p0, ns))) return rc;
-        for (int bounce = 0; bounce < n_marched; ++bounce) {
-            // primary segments are coherent as generated (consecutive spp of a pixel); later ones are regrouped
-            // Secondary segments are regrouped here by start cell (compaction + locality of the guide steps;
-            // GPIS_PATHS_PRESORT=0 skips it when the wavefront march runs, which regroups the exact work
-            // itself).  Measured at 4 bounces, C1 1080p x16: sample order + resident march 22.1 M paths/s,
-            // regrouped + resident 40.4, wavefront march alone 56.7, regrouped + wavefront 61.3.
-            const bool wave = bounce > 0 && m->guide.enabled && wave_march_selected(m, MARCH_SCATTERED);
-            const bool sorted = regroup && bounce > 0 && (!wave || presort);
-            const int hint = bounce > 0 ? MARCH_SCATTERED : MARCH_COHERENT;
-            // src rays + mask -> order, regrouped copy, live flags of the regrouped slots
-            auto regroup_batch = [&](const gpis_ray_in *src, const uint8_t *mask, uint32_t *ord, gpis_ray_in *dst, uint8_t *live_out) -> int {
-                k_paths_keys<<<grid_of(ns, 256), 256, 0, st>>>(m->d_model, cell_size, ns, src, mask, keys, vals);
-                int r = launch_check("k_paths_keys");
-                if (r) return r;
-                size_t tb = sort_temp_bytes;
-                if (sort_pairs_u32(ws + o_temp, tb, keys, keys2, vals, ord, ns, st) != hipSuccess)
-                    return set_err(GPIS_ERR_DEVICE, "radix sort failed");
-                k_paths_gather<<<grid_of(ns, 256), 256, 0, st>>>(ns, keys2, ord, src, dst, live_out);
-                return launch_check("k_paths_gather");
-            };
-            if (sorted && (rc = regroup_batch(f.rays, f.alive, order, rays_sorted, live_sorted))) return rc;
-            const gpis_ray_in *rays_in = sorted ? rays_sorted : f.rays;
-            const uint8_t *live = sorted ? live_sorted : f.alive;
-            if ((rc = sample_distance_impl(m, ns, rays_in, f.seg, nullptr, live, st, hint))) return rc;
-            if ((rc = shade(bounce, ns, sorted ? order : nullptr, rays_in, sorted ? live_sorted : nullptr))) return rc;
-            if (bounce >= n_nee)
-                continue;
-            if (sorted) {
-                // the shadow segments share one direction but start where the bounce segments ended: regroup
-                // them by their own lattice cells (the bounce batch's copy of the rays is free again)
-                if ((rc = regroup_batch(f.shadow, f.nee, order2, rays_sorted, live2))) return rc;
-                if ((rc = transmittance_impl(m, ns, rays_sorted, f.vis, live2, st, hint))) return rc;
-                if ((rc = nee_add(ns, order, order2, live2))) return rc;
-            } else {
-                if ((rc = transmittance_impl(m, ns, f.shadow, f.vis, f.nee, st, hint))) return rc;
-                if ((rc = nee_add(ns, nullptr, nullptr, nullptr))) return rc;
-            }
-        }
-        if ((rc = finish(p0, np))) return rc;
+        if ((rc = lambert_paths_chunk(m, W, f, ns, n_marched, n_nee, st, [&] { return begin(p0, ns); }, shade, nee_add, [&] { return finish(p0, np); })))
+            return rc;
     }
     return ws_release(m, 0, st);
 }
@@ -2734,6 +2803,26 @@ extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, 
 // gpis_render_scene_s_paths in RGB with the medium's emission (gpis_paths_rgb.hpp): three planes of throughput / emission / contrib
 // and a per-sample segment count.  With mean_emission enabled the segment max_path_bounces - 1 is marched too: its hit emits, and
 // neither next-event estimation nor a bounce follows it.
+namespace {
+struct PathsRgbState {                 // the path state of the RGB drivers inside the frame's workspace
+    size_t o_rng = 0, o_thr = 0, o_em = 0, o_con = 0, o_segs = 0;
+    launch::PathsRgbArrays a;
+    template <typename Carve>
+    void carve(Carve &carve, size_t ns_max)
+    {
+        o_rng = carve(ns_max * 8); o_thr = carve(ns_max * 12); o_em = carve(ns_max * 12); o_con = carve(ns_max * 12); o_segs = carve(ns_max * 4);
+        a.plane = ns_max;
+    }
+    void bind(const PathsFrame &f)
+    {
+        a.rays = f.rays; a.seg = f.seg; a.shadow = f.shadow;
+        a.rng = (uint64_t *)(f.ws + o_rng);
+        a.throughput = (float *)(f.ws + o_thr); a.emission = (float *)(f.ws + o_em); a.contrib = (float *)(f.ws + o_con);
+        a.segs = (uint32_t *)(f.ws + o_segs);
+        a.alive = f.alive; a.nee = f.nee; a.vis = f.vis;
+    }
+};
+}
 extern "C" int gpis_render_scene_s_paths_rgb(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, const float albedo[3], float *radiance_sum3,
                                              uint32_t *seg_count, void *stream)
 {
@@ -2742,21 +2831,12 @@ extern "C" int gpis_render_scene_s_paths_rgb(gpis_medium *m, const gpis_scene_s 
     hipStream_t st = (hipStream_t)stream;
     const SceneConst sc = make_scene_const(s);
     const bool emissive = m->host_model.emission.enabled != 0;
-    size_t o_rng = 0, o_thr = 0, o_em = 0, o_con = 0, o_segs = 0;
-    launch::PathsRgbArrays a;
+    PathsRgbState state;
+    launch::PathsRgbArrays &a = state.a;
     return lambert_paths_frames(
         m, s, emissive ? max_path_bounces : max_path_bounces - 1, max_path_bounces - 1, st,
-        [&](auto &carve, size_t ns_max) {
-            o_rng = carve(ns_max * 8); o_thr = carve(ns_max * 12); o_em = carve(ns_max * 12); o_con = carve(ns_max * 12); o_segs = carve(ns_max * 4);
-            a.plane = ns_max;
-        },
-        [&](const PathsFrame &f) {
-            a.rays = f.rays; a.seg = f.seg; a.shadow = f.shadow;
-            a.rng = (uint64_t *)(f.ws + o_rng);
-            a.throughput = (float *)(f.ws + o_thr); a.emission = (float *)(f.ws + o_em); a.contrib = (float *)(f.ws + o_con);
-            a.segs = (uint32_t *)(f.ws + o_segs);
-            a.alive = f.alive; a.nee = f.nee; a.vis = f.vis;
-        },
+        [&](auto &carve, size_t ns_max) { state.carve(carve, ns_max); },
+        [&](const PathsFrame &f) { state.bind(f); },
         [&](size_t p0, size_t ns) {
             launch::paths_rgb_begin(sc, p0, ns, a, st);
             return launch_check("k_paths_rgb_begin");
@@ -2775,6 +2855,71 @@ extern "C" int gpis_render_scene_s_paths_rgb(gpis_medium *m, const gpis_scene_s 
             if (!seg_count) return (int)GPIS_OK;
             launch::paths_rgb_segs(sc, p0, np, a, seg_count, st);
             return launch_check("k_paths_rgb_segs");
+        });
+}
+
+// gpis_render_scene_s_paths_rgb under the adaptive sample schedule (tu_adaptive_paths.hip): the pass loop of
+// gpis_render_scene_s_adaptive around the chunk body of the Lambert path drivers.  A chunk of records is seeded through
+// scene_sample_adaptive, runs the bounce loop of gpis_render_scene_s_paths_rgb, and ends with the clamped luminance and the clamp
+// flag of every sample (4 + 1 bytes per sample behind the path state), the tile statistics on the luminances and the pixel sums.
+extern "C" int gpis_render_scene_s_paths_rgb_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a, int max_path_bounces,
+                                                      const float albedo[3], float *radiance_sum3, uint32_t *sample_count, uint32_t *seg_count,
+                                                      gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && a && albedo && radiance_sum3 && sample_count && max_path_bounces >= 1);
+    CHECK_ARGS(scene_args_ok(s));
+    hipStream_t st = (hipStream_t)stream;
+    const SceneConst sc = make_scene_const(s);
+    const bool emissive = m->host_model.emission.enabled != 0;
+    const int n_marched = emissive ? max_path_bounces : max_path_bounces - 1, n_nee = max_path_bounces - 1;
+    PathsRgbState state;
+    const launch::PathsRgbArrays &arr = state.a;
+    size_t o_lum = 0, o_clamped = 0;
+    PathsWs W;
+    PathsFrame f;
+    float *lum = nullptr;
+    uint8_t *clamped = nullptr;
+    return adaptive_passes(
+        m, s, a, 25, __func__, st, records, info,
+        [&](size_t n, bool &fits) {
+            const int rc = lambert_paths_carve(m, n_marched, n, st,
+                                               [&](auto &carve, size_t ns_max) {
+                                                   state.carve(carve, ns_max);
+                                                   o_lum = carve(ns_max * 4); o_clamped = carve(ns_max);
+                                               }, W);
+            if (rc) return rc;
+            fits = try_stage(m, 3, W.bytes);
+            return (int)GPIS_OK;
+        },
+        [&]() {
+            f = lambert_paths_bind(m, W);
+            state.bind(f);
+            lum = (float *)(f.ws + o_lum); clamped = (uint8_t *)(f.ws + o_clamped);
+            return (int)GPIS_OK;
+        },
+        [&](const AdaptiveChunk &ch, size_t ns, gpis_adaptive_record *d_records) {
+            return lambert_paths_chunk(
+                m, W, f, ns, n_marched, n_nee, st,
+                [&] {
+                    launch::adaptive_paths_rgb_begin(sc, ch, ns, arr, st);
+                    return launch_check("k_rgb_adaptive_begin");
+                },
+                [&](int bounce, size_t n, const uint32_t *order, const gpis_ray_in *rays_in, const uint8_t *live) {
+                    launch::paths_rgb_shade(m->d_model, sc, n, bounce, max_path_bounces, emissive, albedo, arr, order, rays_in, live, st);
+                    return launch_check("k_paths_rgb_shade");
+                },
+                [&](size_t n, const uint32_t *order, const uint32_t *order2, const uint8_t *live2) {
+                    launch::paths_rgb_nee_add(n, arr, order, order2, live2, st);
+                    return launch_check("k_paths_rgb_nee_add");
+                },
+                [&] {
+                    launch::adaptive_paths_rgb_value(ns, arr, lum, clamped, st);
+                    if (int rc = launch_check("k_rgb_adaptive_value")) return rc;
+                    launch::adaptive_paths_rgb_accumulate(sc, ch, arr, clamped, radiance_sum3, sample_count, seg_count, st);
+                    if (int rc = launch_check("k_rgb_adaptive_accumulate")) return rc;
+                    launch::adaptive_paths_rgb_stats(ch, lum, d_records, st);
+                    return launch_check("k_rgb_adaptive_stats");
+                });
         });
 }
 

@@ -144,6 +144,13 @@ void adaptive_primary_compact(const SceneConst &sc, const AdaptiveChunk &ch, siz
 void adaptive_accumulate(const SceneConst &sc, const AdaptiveChunk &ch, const AdaptiveLambert &a, float *radiance_sum, uint32_t *sample_count,
                          uint32_t *hit_count, hipStream_t s);
 void adaptive_stats(const SceneConst &sc, const AdaptiveChunk &ch, const AdaptiveLambert &a, gpis_adaptive_record *records, hipStream_t s);
+// ---- adaptive sampling of the RGB path driver (tu_adaptive_paths.hip): the camera step of a chunk of records, and after its bounce
+// loop the clamped luminance and the clamp flag of every sample, the tile statistics on the luminances and the per-pixel sums
+void adaptive_paths_rgb_begin(const SceneConst &sc, const AdaptiveChunk &ch, size_t n_samples, const PathsRgbArrays &a, hipStream_t s);
+void adaptive_paths_rgb_value(size_t n_samples, const PathsRgbArrays &a, float *luminance, uint8_t *clamped, hipStream_t s);
+void adaptive_paths_rgb_stats(const AdaptiveChunk &ch, const float *luminance, gpis_adaptive_record *records, hipStream_t s);
+void adaptive_paths_rgb_accumulate(const SceneConst &sc, const AdaptiveChunk &ch, const PathsRgbArrays &a, const uint8_t *clamped, float *radiance_sum3,
+                                   uint32_t *sample_count, uint32_t *seg_count, hipStream_t s);
 inline unsigned grid_of(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 }   // namespace launch

@@ -23,12 +23,10 @@ namespace gpis {
 
 using launch::PathsRgbArrays;
 
-GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_rgb_begin(SceneConst sc, size_t first_pixel, size_t n_samples, PathsRgbArrays a)
+// The camera step of sample (x, y, spp), whose stream `g` the caller's sample step has seeded (scene_sample here, scene_sample_adaptive
+// in tu_adaptive_paths.hip): the path state of slot i.
+GPIS_DEV void paths_rgb_begin_sample(const SceneConst &sc, const PathsRgbArrays &a, size_t i, Pcg32 &g, uint32_t x, uint32_t y, uint32_t spp)
 {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_samples) return;
-    uint32_t x, y, spp;
-    Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
     float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
     float u0 = normalized_uint(g.next_i());
     gpis_ray_in r;
@@ -42,6 +40,15 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_rgb_begin(SceneCon
     }
     a.segs[i] = 0;
     a.alive[i] = hit ? 1 : 0;
+}
+
+GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_rgb_begin(SceneConst sc, size_t first_pixel, size_t n_samples, PathsRgbArrays a)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_samples) return;
+    uint32_t x, y, spp;
+    Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
+    paths_rgb_begin_sample(sc, a, i, g, x, y, spp);
 }
 
 // After sampleDistance of segment `bounce`: the hit's emission, the throughput, and for bounce < max_bounces - 1 the next-event
