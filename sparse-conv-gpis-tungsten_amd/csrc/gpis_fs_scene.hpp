@@ -1,6 +1,6 @@
 // gpis_fs_scene.hpp — scene S rendered through the function-space GP medium: one fused kernel, one wave per sample.
 //
-// The estimator is gpis_render_scene_s's (gpis_hip.hip: k_scene_primary, k_scene_shade, k_scene_accumulate) and the frame has
+// The estimator is gpis_render_scene_s's (tu_scene.hip: k_scene_primary, k_scene_shade, k_scene_accumulate) and the frame has
 // the shape of the weight-space one (gpis_ws_scene.hpp): camera ray, bounding-sphere chord, a primary sampleDistance, Lambert
 // shading against the directional light, one shadow transmittance per lit hit, one 8-byte record per sample and a per-pixel sum
 // of the records in sample order, so the image depends neither on the order in which workgroups finish nor on how a frame is cut

@@ -1,7 +1,9 @@
-// gpis_launch.hpp — host-side launch interface between the C-ABI translation unit (gpis_hip.hip) and the kernel
-// translation units (tu_*.hip).  The library is built from several .hip files so that the big march kernels compile
-// in parallel (one TU took 7 minutes); each kernel is defined in exactly one TU and reached through a plain function
-// declared here (device pointers, PODs, a stream — no templates cross a TU boundary).
+// gpis_launch.hpp — host-side launch interface between the host translation units (gpis_hip.hip: C ABI, batch entries;
+// tu_scene.hip: the staged scene-S frame drivers) and the march-kernel translation units (tu_*.hip).  The library is built from
+// several .hip files so that the big march kernels — and the fused frame kernels of the function-space medium — compile in
+// parallel (one TU took 7 minutes); each kernel is defined in exactly one TU and reached through a plain function declared here
+// (device pointers, PODs, a stream — no templates cross a TU boundary).  The small kernels a staged frame driver runs between the
+// marches are not march kernels and have no entry here: tu_scene.hip defines or instantiates them and launches them directly.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,7 +21,6 @@ struct PersistArgs;
 struct SceneConst;
 struct SceneRay;
 struct SceneHit;
-struct AdaptiveChunk;
 
 // radix sort of (key, value) pairs (gpis_sort.hip); two-call convention: temp == nullptr only reports the scratch size
 hipError_t sort_pairs_u32(void *temp, size_t &temp_bytes, const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
@@ -115,42 +116,6 @@ size_t fs_paths_rec_bytes();
 void fs_paths(unsigned grid, const DevModel *d_model, const SceneConst &sc, size_t first_pixel, uint32_t n_samples, int max_bounces, float albedo,
               uint32_t *next, void *recs, void *workspace, gpis_fs_state *path_slots, gpis_fs_state *shadow_slots, hipStream_t s);
 void fs_paths_sum(const SceneConst &sc, size_t first_pixel, size_t n_pixels, const void *recs, float *radiance_sum, uint32_t *seg_count, hipStream_t s);
-// ---- RGB multi-bounce paths of the sparse-convolution medium (tu_paths_rgb.hip; gpis_paths_rgb.hpp): the kernels between the marches
-struct PathsRgbArrays {                // path state of one chunk, SoA; `plane` floats per channel plane
-    gpis_ray_in *rays;                 // current segment of every path (rewritten in place at each bounce)
-    gpis_seg_out *seg;
-    gpis_ray_in *shadow;
-    uint64_t *rng;                     // PCG32 state of the sample's stream
-    float *throughput, *emission;      // 3 planes each, indexed by path
-    float *contrib;                    // 3 planes, indexed by batch slot
-    uint32_t *segs;                    // segments marched for the sample, path plus shadow
-    uint8_t *alive, *nee, *vis;
-    size_t plane;
-};
-void paths_rgb_begin(const SceneConst &sc, size_t first_pixel, size_t n_samples, const PathsRgbArrays &a, hipStream_t s);
-void paths_rgb_shade(const DevModel *d_model, const SceneConst &sc, size_t n_samples, int bounce, int max_bounces, bool emissive, const float albedo[3],
-                     const PathsRgbArrays &a, const uint32_t *order, const gpis_ray_in *rays_in, const uint8_t *live, hipStream_t s);
-void paths_rgb_nee_add(size_t n_samples, const PathsRgbArrays &a, const uint32_t *order, const uint32_t *shadow_order, const uint8_t *shadow_live,
-                       hipStream_t s);
-void paths_rgb_accumulate(const SceneConst &sc, size_t first_pixel, size_t n_pixels, const PathsRgbArrays &a, float *radiance_sum3, hipStream_t s);
-void paths_rgb_segs(const SceneConst &sc, size_t first_pixel, size_t n_pixels, const PathsRgbArrays &a, uint32_t *seg_count, hipStream_t s);
-// ---- adaptive sampling of the Lambert frame (tu_adaptive.hip; gpis_adaptive.hpp): the kernels around the marches of one chunk of records
-struct AdaptiveLambert {               // what the Lambert shade step and the shadow march leave per sample of a chunk
-    const float *cosl;
-    const uint8_t *valid2, *vis, *hit;
-};
-void adaptive_primary(const SceneConst &sc, const AdaptiveChunk &ch, size_t n_samples, gpis_ray_in *rays, float *u_shadow, uint8_t *valid, hipStream_t s);
-void adaptive_primary_compact(const SceneConst &sc, const AdaptiveChunk &ch, size_t n_samples, SceneRay *rays, hipStream_t s);
-void adaptive_accumulate(const SceneConst &sc, const AdaptiveChunk &ch, const AdaptiveLambert &a, float *radiance_sum, uint32_t *sample_count,
-                         uint32_t *hit_count, hipStream_t s);
-void adaptive_stats(const SceneConst &sc, const AdaptiveChunk &ch, const AdaptiveLambert &a, gpis_adaptive_record *records, hipStream_t s);
-// ---- adaptive sampling of the RGB path driver (tu_adaptive_paths.hip): the camera step of a chunk of records, and after its bounce
-// loop the clamped luminance and the clamp flag of every sample, the tile statistics on the luminances and the per-pixel sums
-void adaptive_paths_rgb_begin(const SceneConst &sc, const AdaptiveChunk &ch, size_t n_samples, const PathsRgbArrays &a, hipStream_t s);
-void adaptive_paths_rgb_value(size_t n_samples, const PathsRgbArrays &a, float *luminance, uint8_t *clamped, hipStream_t s);
-void adaptive_paths_rgb_stats(const AdaptiveChunk &ch, const float *luminance, gpis_adaptive_record *records, hipStream_t s);
-void adaptive_paths_rgb_accumulate(const SceneConst &sc, const AdaptiveChunk &ch, const PathsRgbArrays &a, const uint8_t *clamped, float *radiance_sum3,
-                                   uint32_t *sample_count, uint32_t *seg_count, hipStream_t s);
 inline unsigned grid_of(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 }   // namespace launch

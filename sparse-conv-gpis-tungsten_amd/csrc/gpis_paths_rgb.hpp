@@ -1,10 +1,10 @@
 // gpis_paths_rgb.hpp — the per-bounce kernels of gpis_render_scene_s_paths_rgb: the Lambert multi-bounce estimator of
-// gpis_render_scene_s_paths (gpis_hip.hip: k_paths_begin, k_paths_shade, k_paths_nee_add, k_paths_accumulate) carried in RGB, with
+// gpis_render_scene_s_paths (tu_scene.hip, which instantiates these kernels too: k_paths_begin, k_paths_shade, k_paths_nee_add, k_paths_accumulate) carried in RGB, with
 // the medium's emission (MediumSample.emission, GPM.cpp:317; PathTracer.cpp:72-73: emission += throughput * sample.emission, then
 // throughput *= sample.weight).
 //
 // The march kernels, the regrouping (k_paths_keys, k_paths_gather) and the host loop are the mono driver's; only the small
-// kernels between the medium's launches are new.  One thread per sample (per pixel in the two sums), 256 threads per workgroup,
+// kernels between the medium's launches are new.  One thread per sample (per pixel in the sum), 256 threads per workgroup,
 // no LDS.  Path state is SoA: throughput, emission and contrib are THREE PLANES each of `plane` floats (channel c of sample i at
 // [c * plane + i]), so that a wave's 64 lanes read and write 256 contiguous bytes per channel exactly as the mono driver's single
 // plane does; interleaved float3 would make every access a 12-byte stride.
@@ -14,19 +14,33 @@
 // behind field_vec (sandstone / rust emission) is reached only by the lanes that hit: dead slots, !ok and exited segments return
 // before it.
 #pragma once
-#include "gpis_launch.hpp"
 #include "gpis_scene.hpp"
 
 #pragma clang fp contract(off)
 
 namespace gpis {
 
-using launch::PathsRgbArrays;
+struct PathsRgbArrays {                // path state of one chunk, SoA; `plane` floats per channel plane
+    gpis_ray_in *rays;                 // current segment of every path (rewritten in place at each bounce)
+    gpis_seg_out *seg;
+    gpis_ray_in *shadow;
+    uint64_t *rng;                     // PCG32 state of the sample's stream
+    float *throughput, *emission;      // 3 planes each, indexed by path
+    float *contrib;                    // 3 planes, indexed by batch slot
+    uint32_t *segs;                    // segments marched for the sample, path plus shadow (per pixel: k_scene_sum_u32)
+    uint8_t *alive, *nee, *vis;
+    size_t plane;
+};
 
-// The camera step of sample (x, y, spp), whose stream `g` the caller's sample step has seeded (scene_sample here, scene_sample_adaptive
-// in tu_adaptive_paths.hip): the path state of slot i.
-GPIS_DEV void paths_rgb_begin_sample(const SceneConst &sc, const PathsRgbArrays &a, size_t i, Pcg32 &g, uint32_t x, uint32_t y, uint32_t spp)
+// The camera step: the path state of slot i.  `where` is the sample layout scene_sample takes: size_t, the first pixel of a chunk
+// with spp_count samples per pixel, or AdaptiveChunk (gpis_adaptive.hpp).
+template <typename Where>
+__global__ void __launch_bounds__(256) k_paths_rgb_begin(SceneConst sc, Where where, size_t n_samples, PathsRgbArrays a)
 {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_samples) return;
+    uint32_t x, y, spp;
+    Pcg32 g = scene_sample(sc, where, i, x, y, spp);
     float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
     float u0 = normalized_uint(g.next_i());
     gpis_ray_in r;
@@ -40,15 +54,6 @@ GPIS_DEV void paths_rgb_begin_sample(const SceneConst &sc, const PathsRgbArrays 
     }
     a.segs[i] = 0;
     a.alive[i] = hit ? 1 : 0;
-}
-
-GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_rgb_begin(SceneConst sc, size_t first_pixel, size_t n_samples, PathsRgbArrays a)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_samples) return;
-    uint32_t x, y, spp;
-    Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
-    paths_rgb_begin_sample(sc, a, i, g, x, y, spp);
 }
 
 // After sampleDistance of segment `bounce`: the hit's emission, the throughput, and for bounce < max_bounces - 1 the next-event
@@ -189,19 +194,6 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_rgb_accumulate(Sce
     const size_t pix = scene_pixel(sc.s, first_pixel + j);
     for (int c = 0; c < 3; ++c)
         radiance_sum3[3 * pix + c] += acc[c];
-}
-
-// one lane per pixel: the segments marched for its samples, path plus shadow
-GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_rgb_segs(SceneConst sc, size_t first_pixel, size_t n_pixels, const uint32_t *__restrict__ segs,
-                                                                       uint32_t *__restrict__ seg_count)
-{
-    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_pixels) return;
-    const uint32_t spp = sc.s.spp_count;
-    uint32_t acc = 0;
-    for (uint32_t k = 0; k < spp; ++k)
-        acc += segs[j * spp + k];
-    seg_count[scene_pixel(sc.s, first_pixel + j)] += acc;
 }
 
 }   // namespace gpis

@@ -1,12 +1,14 @@
 // gpis_scene.hpp — what the scene-S drivers of every medium share.  One definition, so that the drivers cannot drift apart in a
 // single bit.
 //   host: the host-precomputed camera constants (SceneConst, make_scene_const), the pixel order of a call (scene_pixel,
-//       scene_rows) and the argument check (scene_args_ok) — gpis_hip.hip, tu_ws_scene.hip, tu_ws_paths.hip;
-//   camera step: scene_sample (pixel, spp index, seeded stream) — k_scene_primary, k_paths_begin, k_ws_scene, k_ws_paths,
-//       k_fs_scene, k_fs_paths — and scene_camera_ray (direction, bounding-sphere chord, the first gpis_ray_in) — the same but
-//       k_fs_paths;
-//   hit_normal — the six shading kernels (k_scene_shade, k_paths_shade, k_ws_scene, k_ws_paths, k_fs_scene, k_fs_paths) and
-//       the set-up of the conductor NEE drivers (nee_setup_sample in gpis_hip.hip);
+//       scene_rows) and the argument check (scene_args_ok) — tu_scene.hip, tu_ws_scene.hip, tu_ws_paths.hip;
+//   camera step: scene_sample (pixel, spp index, seeded stream) — k_scene_primary, k_scene_primary_c, k_paths_begin,
+//       k_paths_rgb_begin, k_ws_scene, k_ws_paths, k_fs_scene, k_fs_paths — and scene_camera_ray (direction, bounding-sphere chord,
+//       the first gpis_ray_in) — the same but k_scene_primary_c and k_fs_paths.  The sample layout is scene_sample's second
+//       argument: here the first pixel of a chunk with spp_count samples per pixel; gpis_adaptive.hpp overloads it for the records
+//       of an adaptive pass, and the three staged camera kernels of tu_scene.hip are templates on that argument's type;
+//   hit_normal — the seven shading kernels (k_scene_shade, k_paths_shade, k_paths_rgb_shade, k_ws_scene, k_ws_paths, k_fs_scene,
+//       k_fs_paths) and the set-up of the conductor NEE drivers (nee_setup_sample in tu_scene.hip);
 //   the compact records of the Lambert frame (SceneRay, SceneHit: 32 B each, what gpis_render_scene_s passes between its kernels on
 //       the resident guided march), scene_camera_dir and scene_lambert_shade, which k_scene_primary / k_scene_shade share with
 //       their compact forms k_scene_primary_c / k_scene_shade_c;
@@ -15,7 +17,7 @@
 //       k_nee_paths_shade.
 // The device helpers draw nothing, hold no barrier and branch only on their arguments: called with wave-uniform arguments they
 // return wave-uniform results (gpis_fs_scene.hpp and gpis_fs_paths.hpp rest on this).
-// Not here: the shade step of the three path kernels (k_paths_shade, k_ws_paths, k_fs_paths: Duff frame, wi / wo, next-event
+// Not here: the shade step of the path kernels (k_paths_shade, k_paths_rgb_shade, k_ws_paths, k_fs_paths: Duff frame, wi / wo, next-event
 // estimation, disk rejection, the `next` template) and the camera ray of k_fs_paths, which those kernels state in full.  As
 // functions around the inlined marches they changed the code of the whole kernel and made k_ws_paths and k_fs_paths slower.
 #pragma once

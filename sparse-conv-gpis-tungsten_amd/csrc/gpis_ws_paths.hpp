@@ -1,6 +1,6 @@
 // gpis_ws_paths.hpp — multi-bounce paths on scene S through the weight-space GP medium: one fused kernel, one wave per sample.
 //
-// The estimator is gpis_render_scene_s_paths's (gpis_hip.hip: k_paths_begin, k_paths_shade, k_paths_nee_add, k_paths_accumulate),
+// The estimator is gpis_render_scene_s_paths's (tu_scene.hip: k_paths_begin, k_paths_shade, k_paths_nee_add, k_paths_accumulate),
 // operation for operation: the camera ray and its three draws, the bounding-sphere chord, then per bounce a sampleDistance with
 // segment word = bounce, next-event estimation of the directional light through a state copy with segment + 1 (one shadow
 // transmittance), and a cosine bounce drawn by unit-disk rejection.  The draw order of the

@@ -1,6 +1,6 @@
 // gpis_ws_scene.hpp — scene S rendered through the weight-space GP medium: one fused kernel, one wave per sample.
 //
-// The estimator is gpis_render_scene_s's (gpis_hip.hip: k_scene_primary, k_scene_shade, k_scene_accumulate), bit for bit: the
+// The estimator is gpis_render_scene_s's (tu_scene.hip: k_scene_primary, k_scene_shade, k_scene_accumulate), bit for bit: the
 // camera ray and its four draws, the bounding-sphere chord, a primary sampleDistance, Lambert shading against the directional
 // light and one shadow transmittance per lit hit.  What differs is where the intermediate records live.  The staged drivers keep
 // a gpis_ray_in and a gpis_seg_out per sample in HBM between five launches; here a wave carries its sample from the camera to one

@@ -1,119 +1,18 @@
-// tu_adaptive.hip — adaptive sampling for the scene-S Lambert frame (gpis_render_scene_s_adaptive in gpis_hip.hip; gpis_adaptive.hpp,
-// gpis_launch.hpp): the camera step, the per-pixel sum and the tile statistics of a pass whose records carry different sample
-// counts, and the host plan step (PathTraceIntegrator::generateWork) between the passes.
+// tu_adaptive.hip — the host side of the adaptive sample schedule (gpis_adaptive.hpp; the frame drivers that run under it are in
+// tu_scene.hip): the plan step between the passes (PathTraceIntegrator::generateWork) and the host restatements of the record
+// update and of the RGB sample value that the tests read.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "gpis_adaptive.hpp"
-#include "gpis_launch.hpp"
 
 #pragma clang fp contract(off)
 
 namespace gpis {
 
 int host_set_err(int code, const char *msg);      // gpis_hip.hip: the library's thread-local error text
-
-// ---- kernels.  The two camera steps write what k_scene_primary / k_scene_primary_c write for the sample (x, y, k).
-__global__ void __launch_bounds__(256) k_adaptive_primary(SceneConst sc, AdaptiveChunk ch, size_t n_samples, gpis_ray_in *__restrict__ rays,
-                                                          float *__restrict__ u_shadow, uint8_t *__restrict__ valid)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_samples) return;
-    uint32_t x, y, spp;
-    Pcg32 g = scene_sample_adaptive(sc, ch, i, x, y, spp);
-    float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
-    float u0 = normalized_uint(g.next_i()), u1 = normalized_uint(g.next_i());
-    gpis_ray_in r;
-    bool hit = scene_camera_ray(sc, x, y, spp, jx, jy, r);
-    r.u_jitter = u0;
-    rays[i] = r;
-    u_shadow[i] = u1;
-    valid[i] = hit ? 1 : 0;
-}
-__global__ void __launch_bounds__(256) k_adaptive_primary_c(SceneConst sc, AdaptiveChunk ch, size_t n_samples, SceneRay *__restrict__ rays)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_samples) return;
-    uint32_t x, y, spp;
-    Pcg32 g = scene_sample_adaptive(sc, ch, i, x, y, spp);
-    float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
-    float u0 = normalized_uint(g.next_i()), u1 = normalized_uint(g.next_i());
-    const V3 d = scene_camera_dir(sc, x, y, jx, jy);
-    float t0 = 0.f, t1 = 0.f;
-    const bool hit = sphere_chord(v3(sc.s.cam_pos[0], sc.s.cam_pos[1], sc.s.cam_pos[2]), d, sc.s.bound_radius, t0, t1);
-    float4 *q = reinterpret_cast<float4 *>(rays + i);
-    q[0] = make_float4(d.x, d.y, d.z, t0);
-    q[1] = make_float4(t1, u0, u1, __uint_as_float(hit ? kSceneRayLive : 0u));
-}
-
-// the value of sample i as k_scene_accumulate adds it, after renderTile's clamp
-GPIS_DEV float adaptive_sample_value(const launch::AdaptiveLambert &a, size_t i, float light_radiance)
-{
-    return a.valid2[i] ? adaptive_clamp(a.cosl[i] * (a.vis[i] ? 1.f : 0.f) * light_radiance) : 0.f;
-}
-
-// one lane per pixel slot (16 per record, those past a clipped tile idle): sequential sum over the pixel's samples, in sample order
-__global__ void __launch_bounds__(256) k_adaptive_accumulate(SceneConst sc, AdaptiveChunk ch, launch::AdaptiveLambert a, float *__restrict__ radiance_sum,
-                                                             uint32_t *__restrict__ sample_count, uint32_t *__restrict__ hit_count)
-{
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= (size_t)ch.nrec * (kVarianceTile * kVarianceTile)) return;
-    const uint32_t r = ch.r0 + (uint32_t)(j / (kVarianceTile * kVarianceTile)), p = (uint32_t)(j % (kVarianceTile * kVarianceTile));
-    const AdaptiveTile t = adaptive_tile(sc.s.width, sc.s.height, r);
-    if (p >= t.w * t.h) return;
-    const AdaptivePlanRec rec = ch.plan[r];
-    const size_t first = (size_t)(rec.offset - ch.plan[ch.r0].offset) + (size_t)p * rec.count;
-    float acc = 0.f;
-    uint32_t hits = 0;
-    for (uint32_t k = 0; k < rec.count; ++k) {
-        hits += a.hit[first + k];
-        acc += adaptive_sample_value(a, first + k, sc.s.light_radiance);
-    }
-    const size_t pix = (size_t)(t.y0 + p / t.w) * sc.s.width + (t.x0 + p % t.w);
-    radiance_sum[pix] += acc;
-    sample_count[pix] += rec.count;
-    if (hit_count) hit_count[pix] += hits;
-}
-
-// one lane per record: SampleRecord::addSample over the tile's pixels row-major, then the sample index — the record's samples in
-// the order the layout stores them
-__global__ void __launch_bounds__(256) k_adaptive_stats(SceneConst sc, AdaptiveChunk ch, launch::AdaptiveLambert a, gpis_adaptive_record *__restrict__ records)
-{
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= ch.nrec) return;
-    const uint32_t r = ch.r0 + (uint32_t)j;
-    const size_t first = (size_t)(ch.plan[r].offset - ch.plan[ch.r0].offset), n = (size_t)(ch.plan[r + 1].offset - ch.plan[r].offset);
-    gpis_adaptive_record rec = records[r];
-    for (size_t q = 0; q < n; ++q)
-        adaptive_add_sample(rec, adaptive_sample_value(a, first + q, sc.s.light_radiance));
-    records[r].sample_count = rec.sample_count;
-    records[r].mean = rec.mean;
-    records[r].running_variance = rec.running_variance;
-}
-
-namespace launch {
-
-void adaptive_primary(const SceneConst &sc, const AdaptiveChunk &ch, size_t n_samples, gpis_ray_in *rays, float *u_shadow, uint8_t *valid, hipStream_t s)
-{
-    k_adaptive_primary<<<grid_of(n_samples, 256), 256, 0, s>>>(sc, ch, n_samples, rays, u_shadow, valid);
-}
-void adaptive_primary_compact(const SceneConst &sc, const AdaptiveChunk &ch, size_t n_samples, SceneRay *rays, hipStream_t s)
-{
-    k_adaptive_primary_c<<<grid_of(n_samples, 256), 256, 0, s>>>(sc, ch, n_samples, rays);
-}
-void adaptive_accumulate(const SceneConst &sc, const AdaptiveChunk &ch, const AdaptiveLambert &a, float *radiance_sum, uint32_t *sample_count,
-                         uint32_t *hit_count, hipStream_t s)
-{
-    k_adaptive_accumulate<<<grid_of((size_t)ch.nrec * (kVarianceTile * kVarianceTile), 256), 256, 0, s>>>(sc, ch, a, radiance_sum, sample_count, hit_count);
-}
-void adaptive_stats(const SceneConst &sc, const AdaptiveChunk &ch, const AdaptiveLambert &a, gpis_adaptive_record *records, hipStream_t s)
-{
-    k_adaptive_stats<<<grid_of(ch.nrec, 256), 256, 0, s>>>(sc, ch, a, records);
-}
-
-}   // namespace launch
 
 // ---- the host plan step.  The integrator's sampler: UniformSampler.hpp:41-53 with sequence 0.
 namespace {
@@ -264,4 +163,16 @@ extern "C" void gpis_adaptive_record_add_host(gpis_adaptive_record *rec, size_t 
     for (size_t i = 0; i < n; ++i)
         adaptive_add_sample(*rec, values[i]);
     if (out2) { out2[0] = adaptive_variance(*rec); out2[1] = adaptive_error_estimate(*rec); }
+}
+
+extern "C" void gpis_adaptive_rgb_value_host(size_t n, const float *rgb_in, float *rgb_out, float *luminance)
+{
+    if (!rgb_in) return;
+    for (size_t i = 0; i < n; ++i) {
+        const float *c = rgb_in + 3 * i;
+        const bool z = adaptive_rgb_clamped(c[0], c[1], c[2]);
+        const float v[3] = {z ? 0.f : c[0], z ? 0.f : c[1], z ? 0.f : c[2]};
+        if (luminance) luminance[i] = adaptive_luminance(v[0], v[1], v[2]);
+        if (rgb_out) { rgb_out[3 * i] = v[0]; rgb_out[3 * i + 1] = v[1]; rgb_out[3 * i + 2] = v[2]; }
+    }
 }

@@ -1,4 +1,4 @@
-// tu_fs_paths.hip — the multi-bounce path frame of the function-space medium (gpis_fs_render_scene_s_paths in gpis_hip.hip;
+// tu_fs_paths.hip — the multi-bounce path frame of the function-space medium (gpis_fs_render_scene_s_paths in tu_scene.hip;
 // gpis_fs_paths.hpp, gpis_launch.hpp): the fused kernel of one chunk of samples and the per-pixel sum of its records.
 #include "gpis_fs_paths.hpp"
 #include "gpis_launch.hpp"

@@ -1,4 +1,4 @@
-// tu_fs_scene.hip — the scene-S frame of the function-space medium (gpis_fs_render_scene_s in gpis_hip.hip; gpis_fs_scene.hpp,
+// tu_fs_scene.hip — the scene-S frame of the function-space medium (gpis_fs_render_scene_s in tu_scene.hip; gpis_fs_scene.hpp,
 // gpis_launch.hpp): the fused kernel of one chunk of samples and the per-pixel sum of its records.
 #include "gpis_fs_scene.hpp"
 #include "gpis_launch.hpp"

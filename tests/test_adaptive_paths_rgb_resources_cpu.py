@@ -11,7 +11,8 @@ import test_kernel_resources as res
 from test_nee_paths_resources_cpu import MARCH_KERNELS_BEFORE
 from test_paths_rgb_resources_cpu import PATHS_KERNELS_BEFORE, _tuple
 
-NEW_KERNELS = ("k_rgb_adaptive_begin", "k_rgb_adaptive_value", "k_rgb_adaptive_stats", "k_rgb_adaptive_accumulate")
+# the camera step is the instance of k_paths_rgb_begin on the variable-count layout (AdaptiveChunk); the uniform driver's is ...Im (size_t)
+NEW_KERNELS = ("k_paths_rgb_beginINS_13AdaptiveChunkE", "k_rgb_adaptive_value", "k_rgb_adaptive_stats", "k_rgb_adaptive_accumulate")
 # (vgpr_count, private_segment_fixed_size, group_segment_fixed_size, vgpr_spill_count) in the library of the commit before
 RGB_BEGIN_BEFORE = (32, 0, 0, 0)
 
@@ -26,7 +27,7 @@ def test_adaptive_paths_rgb_kernels_and_the_kernels_before(pkg):
         print(name, v)
         assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0 and v["group_segment_fixed_size"] == 0, (name, v)
         assert v["vgpr_count"] <= 64, (name, v)
-    begin = [v for n, v in k.items() if "k_paths_rgb_begin" in n]
+    begin = [v for n, v in k.items() if "k_paths_rgb_beginIm" in n]
     assert len(begin) == 1 and _tuple(begin[0]) == RGB_BEGIN_BEFORE, begin
     for prefix, want in list(MARCH_KERNELS_BEFORE.items()) + list(PATHS_KERNELS_BEFORE.items()):
         hits = [v for n, v in k.items() if n.startswith(prefix)]

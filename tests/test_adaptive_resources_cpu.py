@@ -10,7 +10,8 @@ import test_kernel_resources as res
 from test_nee_paths_resources_cpu import MARCH_KERNELS_BEFORE
 from test_paths_rgb_resources_cpu import PATHS_KERNELS_BEFORE, _tuple
 
-NEW_KERNELS = ("k_adaptive_primaryE", "k_adaptive_primary_c", "k_adaptive_accumulate", "k_adaptive_stats")
+# the two camera steps are the instances of k_scene_primary / k_scene_primary_c on the variable-count layout (AdaptiveChunk)
+NEW_KERNELS = ("k_scene_primaryIN4gpis13AdaptiveChunkE", "k_scene_primary_cIN4gpis13AdaptiveChunkE", "k_adaptive_accumulate", "k_adaptive_stats")
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(res.LLVM, "clang-offload-bundler")), reason="LLVM tools of the ROCm image")

@@ -154,6 +154,23 @@ def test_chunks_shards_and_frames(env):
     assert _same(_render(pkg, med, scene, shards), first)
 
 
+def test_full_record_body_in_two_chunks(env):
+    """64 x 64 at 32 spp = 131 072 samples: two chunks at GPIS_OPT_CHUNK_LOG2 = 16, the smallest.  The chunked frame of the full-record
+    body is the frame rendered as one chunk, bit for bit (the compact body in two chunks: test_chunks_shards_and_frames)."""
+    pkg, ob = env
+    med = pkg.Medium(pkg.params_for_config("C1"))
+    med.build_guide(16, 8)
+    scene = _scene(ob, 64, 64, 32)
+    compact = _render(pkg, med, scene)
+    med.set_option("scene_compact", 0)
+    whole = _render(pkg, med, scene)
+    assert whole[0].max() > 0 and whole[1].sum() > 0 and _same(whole, compact)
+    med.set_option("chunk_log2", 16)
+    assert _same(_render(pkg, med, scene), whole)
+    med.set_option("scene_compact", 1)
+    assert _same(_render(pkg, med, scene), whole)
+
+
 def test_fall_backs_on_the_same_handle(env):
     """the full-record body after the compact one has used the workspace, and the compact one again after it: with the exit state
     switched on, and without a guide"""

@@ -60,7 +60,7 @@ MARCH_KERNELS_BEFORE = {
 @pytest.mark.skipif(not os.path.exists(os.path.join(res.LLVM, "clang-offload-bundler")), reason="LLVM tools of the ROCm image")
 def test_nee_paths_kernels_and_the_march_kernels(pkg):
     k = res._kernels(pkg.library_path())
-    for name in ("k_nee_paths_setup", "k_nee_paths_shade", "k_nee_paths_gather", "k_nee_paths_segs"):
+    for name in ("k_nee_paths_setup", "k_nee_paths_shade", "k_nee_paths_gather", "k_scene_sum_u32"):
         hits = [v for n, v in k.items() if name in n]
         assert len(hits) == 1, (name, sorted(k))
         v = hits[0]

@@ -21,7 +21,8 @@ PATHS_KERNELS_BEFORE = {
     "_Z15k_paths_nee_add": (6, 0, 0, 0),
     "_Z18k_paths_accumulate": (14, 0, 0, 0),
 }
-NEW_KERNELS = ("k_paths_rgb_begin", "k_paths_rgb_shade", "k_paths_rgb_nee_add", "k_paths_rgb_accumulate", "k_paths_rgb_segs")
+# k_paths_rgb_beginIm: the instance on the uniform sample layout (size_t first pixel); k_scene_sum_u32: the per-pixel segment count
+NEW_KERNELS = ("k_paths_rgb_beginIm", "k_paths_rgb_shade", "k_paths_rgb_nee_add", "k_paths_rgb_accumulate", "k_scene_sum_u32")
 
 
 def _tuple(v):
