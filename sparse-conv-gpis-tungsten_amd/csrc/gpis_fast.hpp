@@ -27,27 +27,12 @@
 #pragma once
 #include "gpis_device.hpp"
 #include "gpis_scene.hpp"
+#include "gpis_tables.hpp"     // FastTable, fast_supported
 
 #pragma clang fp contract(off)
 
 namespace gpis {
 
-// Cell table in HBM (served from L2 / Infinity Cache): the impulses of every cell (i, j, k) with
-// -H <= i, j, k < H, as float4 (x, y, z, w=+-1) in generation order, `stride` slots per cell.  A wave
-// reads a cell with ONE coalesced 512-B / 1-KiB load; cells outside the table are generated on the
-// fly, so the table is a cache and never a correctness bound.
-struct FastTable {
-    float4 *cells;   // nullptr = every cell is generated per wave
-    int half;        // H
-    int stride;      // 32 or 64 slots per cell
-    int enabled;
-};
-
-inline bool fast_supported(const DevModel &M)
-{
-    return M.single_realization && !M.sampling_1d && !M.nonstationary && !M.use_aniso_mtx && !M.absorption_only && !M.color.enabled && M.kernel_type == GPIS_KERNEL_SQUARED_EXPONENTIAL &&
-           M.n_impulses >= 1 && M.n_impulses <= 64;
-}
 GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fast_build_table(uint32_t seed, int half, int stride, float4 *__restrict__ cells)
 {
     const int lane = (int)(threadIdx.x & 63);
@@ -58,41 +43,6 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fast_build_table(uint32_t
     gen_impulse((uint32_t)ci, (uint32_t)cj, (uint32_t)ck, seed, kJump4.A[lane], kJump4.C[lane], px, py, pz, pw);
     if (lane < stride)
         cells[cell * (size_t)stride + lane] = make_float4(px, py, pz, pw);
-}
-inline int fast_table_build(const DevModel &M, const DevModel *, FastTable *t)
-{
-    t->cells = nullptr;
-    t->half = 0;
-    t->stride = 0;
-    t->enabled = fast_supported(M) && !getenv("GPIS_DISABLE_FAST");
-    if (!t->enabled || getenv("GPIS_DISABLE_TABLE"))
-        return GPIS_OK;
-    int half = 16;   // covers |p| < 16 cells: scene S spans 14.2 cells (1.5 world units / cell size 0.106)
-    if (const char *e = getenv("GPIS_TABLE_HALF_EXTENT")) half = atoi(e);
-    if (half < 2) return GPIS_OK;
-    if (half > 40) half = 40;
-    const int stride = M.n_impulses <= 32 ? 32 : 64;
-    const size_t ncell = (size_t)(2 * half) * (2 * half) * (2 * half);
-    if (hipMalloc(&t->cells, ncell * stride * sizeof(float4)) != hipSuccess) {
-        t->cells = nullptr;   // no table: fall back to per-wave generation
-        (void)hipGetLastError();
-        return GPIS_OK;
-    }
-    k_fast_build_table<0><<<(unsigned)ncell, 64>>>(M.seed, half, stride, t->cells);
-    if (hipDeviceSynchronize() != hipSuccess) {
-        (void)hipFree(t->cells);
-        t->cells = nullptr;
-        return GPIS_ERR_DEVICE;
-    }
-    t->half = half;
-    t->stride = stride;
-    return GPIS_OK;
-}
-inline void fast_table_free(FastTable *t)
-{
-    if (t->cells) (void)hipFree(t->cells);
-    t->cells = nullptr;
-    t->enabled = 0;
 }
 
 // ---- wave reductions (wave64) ----------------------------------------------------------------
@@ -1047,21 +997,6 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(kFastBlock, GPIS_FAST_OCC) k_fa
     if (i < n)
         visible[i] = (valid && vis) ? 1 : 0;
     fast_flush_counters(cnt, n_eval, valid ? 1u : 0u);
-}
-
-inline int fast_sample_distance(const DevModel *d_model, const FastTable *T, size_t n, const gpis_ray_in *rays, gpis_seg_out *out,
-                                gpis_cond_coeff *coeff, const uint8_t *mask, Counters *cnt, hipStream_t s)
-{
-    unsigned grid = (unsigned)((n + kFastBlock - 1) / kFastBlock);
-    k_fast_sample_distance<0><<<grid, kFastBlock, 0, s>>>(d_model, *T, n, rays, out, coeff, mask, cnt);
-    return GPIS_OK;
-}
-inline int fast_transmittance(const DevModel *d_model, const FastTable *T, size_t n, const gpis_ray_in *rays, uint8_t *visible,
-                              const uint8_t *mask, Counters *cnt, hipStream_t s)
-{
-    unsigned grid = (unsigned)((n + kFastBlock - 1) / kFastBlock);
-    k_fast_transmittance<0><<<grid, kFastBlock, 0, s>>>(d_model, *T, n, rays, visible, mask, cnt);
-    return GPIS_OK;
 }
 
 }   // namespace gpis

@@ -34,33 +34,11 @@
 // are skipped without any error term.
 #pragma once
 #include "gpis_fast.hpp"
+#include "gpis_tables.hpp"     // GuideField, the brick constants
 
 #pragma clang fp contract(off)
 
 namespace gpis {
-
-// Storage: the samples live in BRICKS of 16^3 grid points (+ one layer shared with the +neighbours: 17^3 floats, so the eight taps of
-// a lookup never leave their brick), and only the bricks a march can need at level 1 are tabulated: a brick is needed when, over the
-// world points that can map into it, |mean| can come below sigma * amax / norm, amax = an a-priori bound on |N| over the brick
-// from a field 4x coarser (1/64 of the work).  Everywhere else level 0 (guide_sign_at) decides every step by the mean alone, and
-// the block records say so: Err = +inf there, so level 1 can certify nothing and the exact evaluation takes over — the need
-// analysis decides speed, never results.  Scene S: 8 % of the bricks (2.8 of 34 GB at 16:64).
-constexpr int kBrick = 16;                         // grid points per brick edge = 4 blocks
-constexpr uint32_t kBrickRow = 17, kBrickFloats = 17u * 17u * 17u;
-constexpr uint32_t kNoBrick = 0xFFFFFFFFu;
-struct GuideField {
-    float *G;            // pool of tabulated bricks: slot * 17^3 + (lx * 17 + ly) * 17 + lz
-    uint64_t *blk;       // (side/4)^3 block records, dense, 8 bytes = one load per march step: slot << 32 | fp16 Err << 16 | fp16 amax (both
-                         // rounded UP; Err = the bound of the block, +inf where the brick is not tabulated; amax = a bound on |N| anywhere in
-                         // the block's cells; slot = the block's brick in the pool, 0 where not tabulated: Err = +inf makes its taps irrelevant)
-    int half;            // extent in cells: u in [-half, half)
-    int ppc;             // grid points per cell (h = 1/ppc)
-    int side;            // 2*half*ppc
-    float alpha[3];      // A_a * R^2
-    float R;             // kernelRadius of the grid space
-    int enabled;
-    uint32_t n_alloc, n_usable;   // bricks in the pool / bricks level 1 may use
-};
 
 // bounds are stored as fp16 rounded towards +inf (values >= 0 or +inf)
 GPIS_DEV uint32_t guide_f2h_up(float x)
@@ -1194,75 +1172,6 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(kFastBlock) k_guide_raycheck(co
         atomicAdd(&stats[0], certified);
         atomicAdd(&stats[1], bad);
     }
-}
-
-inline void guide_free(GuideField *F)
-{
-    if (F->G) (void)hipFree(F->G);
-    if (F->blk) (void)hipFree(F->blk);
-    F->G = nullptr; F->blk = nullptr; F->enabled = 0; F->n_alloc = 0; F->n_usable = 0;
-}
-
-// Builds the guide field for the grid space of medium M (world space or isotropic-ray space).  `sparse`: tabulate only the bricks
-// level 1 of the certificate can be asked about (a 4x coarser field, built first, bounds |N| per brick); otherwise every brick.
-inline int guide_build(const DevModel &M, const DevModel *d_model, const FastTable &T, int half, int ppc, GuideField *F, bool sparse = true)
-{
-    guide_free(F);
-    if (!fast_supported(M) || half < 2 || half > 64 || (ppc != 8 && ppc != 16 && ppc != 32 && ppc != 64))
-        return GPIS_ERR_UNSUPPORTED;
-    F->half = half; F->ppc = ppc; F->side = 2 * half * ppc;
-    if (!M.iso3d) {
-        F->R = M.radius_world;
-        for (int a = 0; a < 3; ++a) F->alpha[a] = (M.invcov_world[4 * a] * 0.5f) * F->R * F->R;
-    } else {
-        F->R = M.radius_iso;
-        for (int a = 0; a < 3; ++a) F->alpha[a] = 0.5f * F->R * F->R;
-    }
-    const size_t nblk = ((size_t)F->side / 4) * (F->side / 4) * (F->side / 4);
-    const uint32_t nbricks = (uint32_t)(nblk / 64);
-    const unsigned bgrid = (nbricks + 255u) / 256u;
-    uint8_t *need = nullptr;
-    uint32_t *slot_of = nullptr, *list = nullptr, *counters = nullptr;
-    GuideField C{};
-    auto fail = [&](int code) {
-        (void)hipGetLastError();
-        if (need) (void)hipFree(need);
-        if (slot_of) (void)hipFree(slot_of);
-        if (list) (void)hipFree(list);
-        if (counters) (void)hipFree(counters);
-        guide_free(&C);
-        guide_free(F);
-        return code;
-    };
-    if (hipMalloc(&F->blk, nblk * sizeof(uint64_t)) != hipSuccess) { F->blk = nullptr; return fail(GPIS_ERR_DEVICE); }
-    if (hipMalloc(&need, nbricks) != hipSuccess || hipMalloc(&slot_of, (size_t)nbricks * 4) != hipSuccess || hipMalloc(&list, (size_t)nbricks * 4) != hipSuccess ||
-        hipMalloc(&counters, 8) != hipSuccess || hipMemset(counters, 0, 8) != hipSuccess)
-        return fail(GPIS_ERR_DEVICE);
-    // 1. which bricks does level 1 need?  (a-priori bound on |N| per brick from the field at ppc / 4: its 4-point block = this brick)
-    if (sparse && ppc >= 32) {
-        const int st = guide_build(M, d_model, T, half, ppc / 4, &C, false);
-        if (st != GPIS_OK) return fail(st);
-    }
-    k_guide_need<0><<<bgrid, 256>>>(d_model, *F, C.blk, need);
-    k_guide_slots<0><<<bgrid, 256>>>(*F, need, slot_of, list, counters);
-    uint32_t cnt[2] = {0, 0};
-    if (hipMemcpy(cnt, counters, 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(GPIS_ERR_DEVICE);
-    guide_free(&C);
-    F->n_alloc = cnt[0]; F->n_usable = cnt[1];
-    // 2. the samples of the allocated bricks (at least one brick exists: the lookup table points unused bricks at slot 0)
-    const size_t pool = (size_t)(cnt[0] ? cnt[0] : 1u) * kBrickFloats;
-    if (hipMalloc(&F->G, pool * sizeof(float)) != hipSuccess) { F->G = nullptr; return fail(GPIS_ERR_DEVICE); }
-    if (!cnt[0] && hipMemset(F->G, 0, pool * sizeof(float)) != hipSuccess) return fail(GPIS_ERR_DEVICE);
-    const size_t n_items = (size_t)cnt[0] * 64, per_launch = (size_t)1 << 22;   // slabs of 4 Mi blocks
-    for (size_t i0 = 0; i0 < n_items; i0 += per_launch)
-        k_guide_build<0><<<(unsigned)(n_items - i0 < per_launch ? n_items - i0 : per_launch), 64>>>(d_model, T, *F, i0, list, slot_of, need);
-    // 3. the blocks' bounds on |N| (reads the samples incl. the shared layers) and their bricks' slots
-    for (size_t i0 = 0; i0 < n_items; i0 += (size_t)1 << 30)
-        k_guide_amax<0><<<(unsigned)(((n_items - i0 < ((size_t)1 << 30) ? n_items - i0 : ((size_t)1 << 30)) + 255) / 256), 256>>>(*F, i0, n_items, list, need);
-    if (hipDeviceSynchronize() != hipSuccess) return fail(GPIS_ERR_DEVICE);
-    (void)hipFree(need); (void)hipFree(slot_of); (void)hipFree(list); (void)hipFree(counters);
-    F->enabled = 1;
-    return GPIS_OK;
 }
 
 }   // namespace gpis

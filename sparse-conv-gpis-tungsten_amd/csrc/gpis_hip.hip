@@ -21,8 +21,8 @@
 #include <vector>
 
 #include "gpis.h"
-#include "gpis_host.hpp"      // gpis_medium, HIP_TRY, CHECK_ARGS, ProfScope; gpis_fast.hpp (FastTable, fast_supported) and gpis_guide.hpp
-                              // (GuideField, guide_free), of which no kernel is instantiated here
+#include "gpis_host.hpp"      // gpis_medium, HIP_TRY, CHECK_ARGS, ProfScope; gpis_tables.hpp (FastTable, fast_supported, fast_table_free,
+                              // GuideField, kBrickFloats, guide_free) — none of the fast or guided device code is seen here
 #include "gpis_launch.hpp"    // the march kernels live in the tu_*.hip translation units
 
 #pragma clang fp contract(off)

@@ -12,9 +12,8 @@
 
 #include "gpis.h"
 #include "gpis_device.hpp"
-#include "gpis_fast.hpp"      // FastTable (no kernel of it is instantiated through this header)
-#include "gpis_guide.hpp"     // GuideField
 #include "gpis_scene.hpp"     // SceneRay, SceneHit
+#include "gpis_tables.hpp"    // FastTable, GuideField: the records only, none of the fast or guided device code
 
 // ======================================================================================
 // handle
@@ -26,8 +25,8 @@ struct gpis_medium {
     int device;
     gpis::DevModel *d_model;
     gpis::Counters *d_counters;
-    gpis::FastTable fast;    // single-realization wave-cooperative path (gpis_fast.hpp); enabled == 0 when unused
-    gpis::GuideField guide;  // certified guide field (gpis_guide.hpp); enabled == 0 until gpis_build_guide
+    gpis::FastTable fast;    // single-realization wave-cooperative path (gpis_tables.hpp, gpis_fast.hpp); enabled == 0 when unused
+    gpis::GuideField guide;  // certified guide field (gpis_tables.hpp, gpis_guide.hpp); enabled == 0 until gpis_build_guide
     unsigned long long *d_guide_cnt;
     uint64_t selfcheck_tabulated = 0;   // points of the last gpis_guide_selfcheck that fell into tabulated bricks
     gpis::GuideField *d_guide;   // device copy of `guide` (the resident guided kernels read it through scalar loads instead of 14 kernel-argument SGPRs)

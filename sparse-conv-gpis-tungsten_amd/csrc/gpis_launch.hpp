@@ -4,6 +4,9 @@
 // parallel (one TU took 7 minutes); each kernel is defined in exactly one TU and reached through a plain function declared here
 // (device pointers, PODs, a stream — no templates cross a TU boundary).  The small kernels a staged frame driver runs between the
 // marches are not march kernels and have no entry here: tu_scene.hip defines or instantiates them and launches them directly.
+// What keeps "exactly one TU" true: a kernel is instantiated where a `k<0><<<...>>>` is compiled, so a header that more than one
+// unit includes launches nothing — every launcher is a function of the owning tu_*.hip (tests/test_kernel_resources.py checks the
+// built library for a second definition of any kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,13 +14,9 @@
 #include <cstdint>
 
 #include "gpis.h"
+#include "gpis_tables.hpp"    // FastTable, GuideField; through gpis_device.hpp: DevModel, Counters, PersistArgs
 
 namespace gpis {
-struct DevModel;
-struct Counters;
-struct FastTable;
-struct GuideField;
-struct PersistArgs;
 struct SceneConst;
 struct SceneRay;
 struct SceneHit;

@@ -12,10 +12,11 @@ import pytest
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-def _kernels(lib):
-    """kernel name -> resources, over every code object of the library (one offload bundle per translation unit)"""
+def _kernel_entries(lib):
+    """(index of the code object, kernel name, resources) for every kernel entry of the library; one code object (offload bundle)
+    per translation unit, in link order"""
     tmp = tempfile.mkdtemp()
-    notes = ""
+    out = []
     try:
         fat = os.path.join(tmp, "fat.bin")
         subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
@@ -27,16 +28,41 @@ def _kernels(lib):
             open(part, "wb").write(blob[a:starts[i + 1] if i + 1 < len(starts) else len(blob)])
             subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o",
                                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + part, "--output=" + co])
-            notes += subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True, stderr=subprocess.DEVNULL)
+            notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True, stderr=subprocess.DEVNULL)
+            for blk in notes.split("  - .agpr_count")[1:]:
+                name = re.search(r"\.name:\s+(\S+)", blk)
+                if name:
+                    out.append((i, name.group(1), {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
+                                                   for k in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "group_segment_fixed_size")}))
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
-    out = {}
-    for blk in notes.split("  - .agpr_count")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk)
-        if name:
-            out[name.group(1)] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
-                                  for k in ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "group_segment_fixed_size")}
     return out
+
+
+def _duplicates(entries):
+    """kernel name -> indices of its code objects, for the names that occur in more than one"""
+    where = {}
+    for i, name, _ in entries:
+        where.setdefault(name, []).append(i)
+    return {n: idx for n, idx in where.items() if len(idx) > 1}
+
+
+def _kernels(lib):
+    """kernel name -> resources, over every code object of the library.  A name that two code objects define fails here: all copies
+    register under one host stub, and a budget checked on one copy says nothing about the one a launch runs."""
+    entries = _kernel_entries(lib)
+    dup = _duplicates(entries)
+    assert not dup, "kernels defined in more than one code object: " + "; ".join("%s in %s" % (n, idx) for n, idx in sorted(dup.items()))
+    return {name: res for _, name, res in entries}
+
+
+@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "clang-offload-bundler")), reason="LLVM tools of the ROCm image")
+def test_every_kernel_has_one_definition(pkg):
+    """csrc/gpis_launch.hpp: each kernel is defined in exactly one translation unit.  A host function in a shared header that
+    launches with <<<>>> breaks this without any other symptom: every unit that includes the header compiles its own copy."""
+    entries = _kernel_entries(pkg.library_path())
+    assert entries
+    assert _duplicates(entries) == {}
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "clang-offload-bundler")), reason="LLVM tools of the ROCm image")
