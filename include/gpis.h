@@ -76,8 +76,18 @@ typedef enum gpis_scheme_1d { GPIS_UNI = 0, GPIS_NEE = 1, GPIS_MIS = 2 } gpis_sc
 typedef enum gpis_mean_type {
     GPIS_MEAN_HOMOGENEOUS = 0,   /* offset                       GPF.hpp:867-901  */
     GPIS_MEAN_SPHERICAL = 1,     /* |p-c| - r                    GPF.hpp:903-945  */
-    GPIS_MEAN_LINEAR = 2         /* max((p-ref).dir*scale, min)  GPF.hpp:947-1005 */
+    GPIS_MEAN_LINEAR = 2,        /* max((p-ref).dir*scale, min)  GPF.hpp:947-1005 */
+    GPIS_MEAN_PROCEDURAL = 3     /* max(min, sdf(T^-1 p)*scale + offset)  GPF.hpp:1049-1087, GPF.cpp:250-296 */
 } gpis_mean_type;
+
+/* SdfFunctions::Function (math/SdfFunctions.hpp:12-18, same numeric order): the shape of a procedural mean, "func". */
+typedef enum gpis_sdf_function {
+    GPIS_SDF_KNOB = 0,
+    GPIS_SDF_KNOB_INNER = 1,
+    GPIS_SDF_KNOB_OUTER = 2,
+    GPIS_SDF_TWO_SPHERES = 3,
+    GPIS_SDF_PLANE = 4
+} gpis_sdf_function;
 
 /* NoiseType of ProceduralNoise / ProceduralNoiseVec (GPF.hpp:613-650, 702-739): the four ramps (GPF.cpp:57-69, 91-103) and
  * the two fbm noises over 3D simplex noise (GPF.cpp:70-83, 104-117; math/SdfFunctions.cpp:199-296). */
@@ -116,13 +126,18 @@ typedef enum gpis_kernel_type {
 typedef struct gpis_mean {
     int32_t type;          /* gpis_mean_type */
     float radius;          /* spherical */
-    float offset;          /* homogeneous */
-    float scale;           /* linear */
-    float min;             /* linear (default -FLT_MAX) */
-    int32_t _pad;
+    float offset;          /* homogeneous; procedural "offset" */
+    float scale;           /* linear; procedural "scale" */
+    float min;             /* linear, procedural (default -FLT_MAX) */
+    int32_t func;          /* procedural: gpis_sdf_function; not read for the other types */
     double center[3];      /* spherical centre / linear reference_point */
     double dir[3];         /* linear direction (normalised by gpis_create as LinearMean::fromJson does) */
 } gpis_mean;
+/* A procedural mean is ProceduralMean over one of the reference's SDF shapes: mean(a) = max(min, sdf(T^-1 . float(a)) * scale + offset)
+ * in float, widened; dmean_da is the reference's one-sided difference with eps = 0.001f (GPF.cpp:279-296).  T is the mean's
+ * "transform" (identity until gpis_set_mean_transform).  Such a medium runs on the lane-per-ray all-features path instance (GPIS_OPT_PERSISTENT
+ * has no effect on it): no fast table, no guide field, no wavefront form; the function-space and weight-space media refuse it.  Scalar-field objects ("f") are outside
+ * the built scope. */
 
 /*
  * All JSON keys of the hot path (SURVEY.md §5 "Config / flags"):
@@ -401,6 +416,18 @@ int gpis_nee_grad_batch(gpis_medium *m, size_t n, const gpis_nee_query *q, float
  * stores in MediumSample.emission.  color3 / emission3: n xyz triples of float; either may be NULL. */
 int gpis_mean_color_emission_batch(gpis_medium *m, size_t n, const double *p3, float *color3, float *emission3, void *stream);
 int gpis_mean_color_emission_host(gpis_medium *m, size_t n, const double *p3, float *color3, float *emission3);
+/* (with a procedural primary mean, colour is evaluated at Vec3d(T^-1 . Vec3f(p)), GPF.hpp:1065-1073; emission at p itself) */
+
+/* GaussianProcess::mean_weight_space (GaussianProcess.cpp:379-393) at n double-precision points, any mean type: the value, the id
+ * of the slot the CSG minimum chose (0 = mean, 1 = mean_additional) and dmean_da of that slot.  Any output may be null. */
+int gpis_mean_batch(gpis_medium *m, size_t n, const double *p3, double *value, int32_t *id, double *grad3, void *stream);
+int gpis_mean_host(gpis_medium *m, size_t n, const double *p3, double *value, int32_t *id, double *grad3);
+
+/* The "transform" of a procedural mean (ProceduralMean::_configTransform, GPF.cpp:252-253): a row-major Mat4f.  which = 0: mean,
+ * 1: mean_additional.  The library inverts it as Mat4f::invert does (Mat4f.hpp:75-101; a zero determinant gives the identity) and
+ * applies the inverse as transformPoint.  Waits for the device, takes the handle's lock.  GPIS_ERR_INVALID_ARG for a slot that is
+ * not procedural. */
+int gpis_set_mean_transform(gpis_medium *m, int which, const float transform[16]);
 
 /* Medium::sampleDistance / transmittance of the function-space medium (GaussianProcessMedium.cpp:221-393 over
  * FunctionSpaceGaussianProcessMedium::intersectGP / sampleGradient).  rays[i].u_jitter is not used (every variate comes from

@@ -9,12 +9,14 @@
 //   struct A {
 //       using Node = ...;                                             // cheap to copy
 //       static bool child(const Node &o, const char *key, Node &out); // object member, if present
+//       static bool has(const Node &o, const char *key);              // whether the object has that member
 //       template <class T> static void num(const Node &o, const char *key, T &dst);   // number (or bool -> 0 / 1); dst untouched when absent
 //       static void flag(const Node &o, const char *key, int32_t &dst);               // bool (or number) -> 0 / 1
 //       static void str(const Node &o, const char *key, std::string &dst);
 //       static void vec3f(const Node &o, const char *key, float *dst);                // scalar or 3-array, as JsonPtr reads a Vec3f
 //       static void vec3d(const Node &o, const char *key, double *dst);
 //       static void mat3f(const Node &o, const char *key, float *dst9);               // row-major 3x3
+//       static int mat4f(const Node &o, const char *key, float *dst16);               // row-major 4x4 given as 16 numbers: 1 read, 0 absent, -1 another form
 //       [[noreturn]] static void fail(const std::string &what);
 //   };
 //
@@ -64,8 +66,24 @@ template <class A> void readRamp(const typename A::Node &v, gpis_ramp &r)
     A::num(v, "min", r.min); A::num(v, "max", r.max); A::num(v, "start", r.start); A::num(v, "end", r.end);
     A::num(v, "min2", r.min2); A::num(v, "max2", r.max2); A::num(v, "start2", r.start2); A::num(v, "end2", r.end2);
 }
-// MeanFunction subclasses, GPFunctions.hpp:867-1005
-template <class A> void readMean(const typename A::Node &m, gpis_mean &dst)
+// SdfFunctions::stringToFunction, math/SdfFunctions.cpp:22-35
+template <class A> int sdfFunction(const std::string &name)
+{
+    if (name == "knob") return GPIS_SDF_KNOB;
+    if (name == "knob_inner") return GPIS_SDF_KNOB_INNER;
+    if (name == "knob_outer") return GPIS_SDF_KNOB_OUTER;
+    if (name == "two_spheres") return GPIS_SDF_TWO_SPHERES;
+    if (name == "plane") return GPIS_SDF_PLANE;
+    A::fail("Invalid sdf function: '" + name + "'");
+}
+// The "transform" of the two means, where one was given: it is no field of gpis_params; the adapter hands it to
+// gpis_set_mean_transform after gpis_create.
+struct MeanTransforms {
+    int32_t set[2] = {0, 0};          // [0] mean, [1] mean_additional
+    float m[2][16] = {};              // row-major Mat4f
+};
+// MeanFunction subclasses, GPFunctions.hpp:867-1087
+template <class A> void readMean(const typename A::Node &m, gpis_mean &dst, MeanTransforms *tf = nullptr, int which = 0)
 {
     std::string type = "spherical";
     A::str(m, "type", type);
@@ -82,6 +100,30 @@ template <class A> void readMean(const typename A::Node &m, gpis_mean &dst)
         A::vec3d(m, "direction", dst.dir);
         A::num(m, "scale", dst.scale);
         A::num(m, "min", dst.min);
+    } else if (type == "procedural") {               // ProceduralMean::fromJson, GPFunctions.cpp:250-266
+        dst.type = GPIS_MEAN_PROCEDURAL;
+        dst.offset = 0.f; dst.scale = 1.f;           // GPFunctions.hpp:1078-1080 (min keeps the -FLT_MAX of gpis_default_params)
+        typename A::Node f = m;
+        std::string func = "knob";
+        A::str(m, "func", func);
+        if (!A::has(m, "func")) {                    // "func" wins over "f", as in the reference; without either: knob
+            if (A::child(m, "f", f))
+                A::fail("procedural mean: \"f\" scalar-field objects (sdf, noise, code) are outside the built scope; name the shape with \"func\"");
+        }
+        dst.func = sdfFunction<A>(func);
+        A::num(m, "min", dst.min);
+        A::num(m, "scale", dst.scale);
+        A::num(m, "offset", dst.offset);
+        float t[16];
+        const int got = A::mat4f(m, "transform", t);
+        if (got < 0)
+            A::fail("procedural mean: only the 16-number array form of \"transform\" is read (the position / rotation / scale object form is outside the built scope)");
+        if (got > 0) {
+            if (!tf)
+                A::fail("procedural mean: this medium takes no \"transform\"");
+            tf->set[which] = 1;
+            for (int i = 0; i < 16; ++i) tf->m[which][i] = t[i];
+        }
     } else {
         A::fail("Unsupported mean function type: '" + type + "'");
     }
@@ -164,17 +206,17 @@ template <class A> void readCovariance(const typename A::Node &c, gpis_params &p
     }
 }
 // GaussianProcess::fromJson (GaussianProcess.cpp:172-190) for an inline object
-template <class A> void readGaussianProcess(const typename A::Node &gp, gpis_params &p)
+template <class A> void readGaussianProcess(const typename A::Node &gp, gpis_params &p, MeanTransforms *tf = nullptr)
 {
     typename A::Node m = gp, f = gp;
     if (A::child(gp, "mean", m)) {
-        readMean<A>(m, p.mean);
+        readMean<A>(m, p.mean, tf, 0);
         if (A::child(m, "color", f)) readRamp<A>(f, p.mean_color);          // MeanFunction::fromJson, GPFunctions.hpp:808-818
         if (A::child(m, "emission", f)) readRamp<A>(f, p.mean_emission);
     }
     if (A::child(gp, "mean_additional", m)) {        // GPSampleNodeCSG's second mean (GaussianProcess.cpp:25-39)
         p.has_mean_additional = 1;
-        readMean<A>(m, p.mean_additional);
+        readMean<A>(m, p.mean_additional, tf, 1);
     }
     if (A::child(gp, "covariance", m))
         readCovariance<A>(m, p);
@@ -182,7 +224,7 @@ template <class A> void readGaussianProcess(const typename A::Node &gp, gpis_par
 // The medium object itself: GaussianProcessMedium::fromJson (GaussianProcessMedium.cpp:97-126) and
 // SparseConvolutionNoiseMedium::fromJson (SparseConvolutionNoiseMedium.cpp:57-73).  "max_bounces" (Medium.cpp:29-38) is read by
 // the caller: Tungsten's base class owns it on the integration side.
-template <class A> void readMedium(const typename A::Node &v, gpis_params &p)
+template <class A> void readMedium(const typename A::Node &v, gpis_params &p, MeanTransforms *tf = nullptr)
 {
     A::vec3f(v, "sigma_a", p.sigma_a);
     A::vec3f(v, "sigma_s", p.sigma_s);
@@ -192,7 +234,7 @@ template <class A> void readMedium(const typename A::Node &v, gpis_params &p)
     p.correlation_context = correlationContext<A>(ctxt);
     typename A::Node gp = v;
     if (A::child(v, "gaussian_process", gp))
-        readGaussianProcess<A>(gp, p);
+        readGaussianProcess<A>(gp, p, tf);
     A::num(v, "step_size", p.step_size);
     A::num(v, "min_step", p.min_step);
     A::num(v, "seed", p.seed);

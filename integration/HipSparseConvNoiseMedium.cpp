@@ -44,7 +44,8 @@ void HipSparseConvNoiseMedium::fromJson(JsonPtr value, const Scene &scene)
     if (auto gp = value["gaussian_process"])
         if (!gp.isObject())
             FAIL("hip_sparse_conv_noise: \"gaussian_process\" must be an inline object");
-    gpis_json::readMedium<TungstenJson>(value, _params);
+    _meanTransforms = gpis_json::MeanTransforms();
+    gpis_json::readMedium<TungstenJson>(value, _params, &_meanTransforms);
     _phaseFunctions.clear();
     _phaseFunctions.push_back(_phaseFunction);     // "We always have the default one"
     int device = _device;
@@ -87,6 +88,9 @@ void HipSparseConvNoiseMedium::prepareForRender()
         _handle = nullptr;
         FAIL("hip_sparse_conv_noise: gpis_create failed: %s", gpis_last_error());
     }
+    for (int w = 0; w < 2; ++w)        // the "transform" of a procedural mean
+        if (_meanTransforms.set[w] && gpis_set_mean_transform(_handle, w, _meanTransforms.m[w]) != GPIS_OK)
+            FAIL("hip_sparse_conv_noise: gpis_set_mean_transform failed: %s", gpis_last_error());
 }
 
 void HipSparseConvNoiseMedium::teardownAfterRender()

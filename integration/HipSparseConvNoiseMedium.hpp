@@ -16,6 +16,7 @@
 #include "sampling/PathSampleGenerator.hpp"
 
 #include <gpis.h>
+#include <gpis_json.hpp>
 
 #include <memory>
 #include <string>
@@ -42,6 +43,7 @@ struct GPContextHip : public GPContext
 class HipSparseConvNoiseMedium : public Medium
 {
     gpis_params _params;
+    gpis_json::MeanTransforms _meanTransforms;   // "transform" of a procedural mean: set on the handle after gpis_create
     gpis_medium *_handle;
     int _device;
     Vec3f _sigmaA, _sigmaS, _sigmaT;

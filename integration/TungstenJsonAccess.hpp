@@ -20,6 +20,7 @@ struct TungstenJson {
         if (auto c = o[key]) { out = c; return true; }
         return false;
     }
+    static bool has(const Node &o, const char *key) { return bool(o[key]); }
     template <typename T> static void num(const Node &o, const char *key, T &dst) { o.getField(key, dst); }
     static void flag(const Node &o, const char *key, int32_t &dst)
     {
@@ -49,6 +50,14 @@ struct TungstenJson {
                 for (int col = 0; col < 3; ++col)
                     dst9[3*r + col] = a(r, col);
         }
+    }
+    static int mat4f(const Node &o, const char *key, float *dst16)
+    {
+        auto mtx = o[key];
+        if (!mtx) return 0;
+        if (!mtx.isArray() || mtx.size() != 16) return -1;
+        for (unsigned i = 0; i < 16; ++i) mtx[i].get(dst16[i]);
+        return 1;
     }
     [[noreturn]] static void fail(const std::string &what) { FAIL("hip gpis medium: %s", what); }
 };

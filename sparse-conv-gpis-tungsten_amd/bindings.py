@@ -19,11 +19,19 @@ class SCHEME:
 
 
 class MEAN_TYPE:
-    HOMOGENEOUS, SPHERICAL, LINEAR = 0, 1, 2
+    HOMOGENEOUS, SPHERICAL, LINEAR, PROCEDURAL = 0, 1, 2, 3
 
 
+class SDF_FUNCTION:
+    """gpis_sdf_function: the shape of a procedural mean (SdfFunctions::Function)"""
+    KNOB, KNOB_INNER, KNOB_OUTER, TWO_SPHERES, PLANE = 0, 1, 2, 3, 4
+    NAMES = {"knob": 0, "knob_inner": 1, "knob_outer": 2, "two_spheres": 3, "plane": 4}
+
+
+# gpis_mean.func (the former padding word) keeps the field NAME "_pad" with the numpy TITLE "func": rec["func"] reads and writes it,
+# and the records stored in tests/golden/*.npz under the old name keep loading and comparing field by field
 MEAN = np.dtype([
-    ("type", "<i4"), ("radius", "<f4"), ("offset", "<f4"), ("scale", "<f4"), ("min", "<f4"), ("_pad", "<i4"),
+    ("type", "<i4"), ("radius", "<f4"), ("offset", "<f4"), ("scale", "<f4"), ("min", "<f4"), (("func", "_pad"), "<i4"),
     ("center", "<f8", 3), ("dir", "<f8", 3),
 ], align=True)
 
@@ -341,6 +349,7 @@ class GpisLib:
         "gpis_sample_distance_batch", "gpis_transmittance_batch", "gpis_eval_value_batch",
         "gpis_eval_gradient_batch", "gpis_conditioning_batch", "gpis_nee_pdf_batch", "gpis_nee_grad_batch",
         "gpis_xxhash32_batch", "gpis_pcg32_stream_batch", "gpis_mean_color_emission_batch", "gpis_mean_color_emission_host",
+        "gpis_mean_batch", "gpis_mean_host", "gpis_set_mean_transform",
         "gpis_fs_sample_distance_batch", "gpis_fs_transmittance_batch", "gpis_fs_linalg_batch", "gpis_libm_batch", "gpis_sort_pairs_u32",
         "gpis_fs_sample_distance_host", "gpis_fs_transmittance_host",
         "gpis_sample_distance_host", "gpis_transmittance_host", "gpis_eval_value_host", "gpis_eval_gradient_host",
@@ -395,6 +404,9 @@ class GpisLib:
         L.gpis_fs_sample_distance_host.argtypes = [vp, sz, vp, vp, vp]
         L.gpis_fs_transmittance_host.argtypes = [vp, sz, vp, vp, vp]
         L.gpis_mean_color_emission_host.argtypes = [vp, sz, vp, vp, vp]
+        L.gpis_mean_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+        L.gpis_mean_host.argtypes = [vp, sz, vp, vp, vp, vp]
+        L.gpis_set_mean_transform.argtypes = [vp, i32, vp]
         L.gpis_xxhash32_batch.argtypes = [vp, sz, i32, vp, vp, vp]
         L.gpis_pcg32_stream_batch.argtypes = [vp, sz, vp, u32, vp, vp]
         L.gpis_sample_distance_host.argtypes = [vp, sz, vp, vp, vp]
@@ -753,6 +765,21 @@ class Medium:
         emi = np.zeros((p.shape[0], 3), dtype=np.float32)
         self.L.check(self.L.lib.gpis_mean_color_emission_host(self.h, p.shape[0], _ptr(p), _ptr(col), _ptr(emi)), "gpis_mean_color_emission_host")
         return col, emi
+
+    def mean(self, points):
+        """(value, id, grad) of GaussianProcess::mean_weight_space at double-precision points (n, 3): the mean, the slot the CSG
+        minimum chose and dmean_da of that slot"""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        val = np.zeros(p.shape[0], dtype=np.float64)
+        gid = np.zeros(p.shape[0], dtype=np.int32)
+        grad = np.zeros((p.shape[0], 3), dtype=np.float64)
+        self.L.check(self.L.lib.gpis_mean_host(self.h, p.shape[0], _ptr(p), _ptr(val), _ptr(gid), _ptr(grad)), "gpis_mean_host")
+        return val, gid, grad
+
+    def set_mean_transform(self, which, transform):
+        """the "transform" of a procedural mean (a 4x4 matrix, row-major); which = 0: mean, 1: mean_additional"""
+        t = np.ascontiguousarray(transform, dtype=np.float32).reshape(16)
+        self.L.check(self.L.lib.gpis_set_mean_transform(self.h, int(which), _ptr(t)), "gpis_set_mean_transform")
 
     def eval_value(self, q):
         q = np.ascontiguousarray(q, dtype=QUERY)

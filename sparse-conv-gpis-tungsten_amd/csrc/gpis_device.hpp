@@ -111,6 +111,10 @@ struct DevModel {
     // means
     gpis_mean mean[2];
     double lin_dir[2][3];
+    // procedural SDF means (gpis_sdf.hpp); behind everything else, so no other field moves
+    int32_t sdf_mean;             // a slot in use is GPIS_MEAN_PROCEDURAL: only the all-features path instance evaluates those
+    float sdf_rot[3][9];          // Mat4f::rotAxis((1,0,0), -90 / 90 / -45), rows 0..2 (Mat4f.cpp:132-148, host libm)
+    float sdf_inv[2][12];         // rows 0..2 of the slot's _invConfigTransform (gpis_set_mean_transform; identity by default)
 };
 
 struct Counters {
@@ -815,6 +819,8 @@ GPIS_DEV double lerp_d(double a, double b, double ratio) { return a * (1.0 - rat
 
 }   // namespace gpis
 
+#include "gpis_sdf.hpp"
+
 // ---------------------------------------------------------------------------------------------
 // The path section (covariance layer … sampleDistance) is compiled once per SPECIALISATION: the
 // all-features instance needs 256 VGPRs and spills 2 000+ SGPRs (1 wave/SIMD), so the march kernels
@@ -827,6 +833,7 @@ GPIS_DEV double lerp_d(double a, double b, double ratio) { return a * (1.0 - rat
 #define GPIS_PATH_NS generic
 #define GPIS_PATH_OUTLINE_NOISE3D 1
 #define GPIS_FLAG_fbm_noise(M) ((M).fbm_noise != 0)
+#define GPIS_FLAG_sdf_mean(M) ((M).sdf_mean != 0)
 #define GPIS_FLAG_other_kernels(M) ((M).kernel_type != GPIS_KERNEL_SQUARED_EXPONENTIAL)
 #define GPIS_FLAG_aniso_field(M) ((M).aniso.enabled)
 #define GPIS_FLAG_sampling_1d(M) ((M).sampling_1d)
@@ -840,6 +847,7 @@ GPIS_DEV double lerp_d(double a, double b, double ratio) { return a * (1.0 - rat
 // 1D sampling along the ray (config C2)
 #define GPIS_PATH_NS spec_1d
 #define GPIS_FLAG_fbm_noise(M) 0
+#define GPIS_FLAG_sdf_mean(M) 0
 #define GPIS_FLAG_other_kernels(M) 0
 #define GPIS_FLAG_aniso_field(M) 0
 #define GPIS_FLAG_sampling_1d(M) 1
@@ -852,6 +860,7 @@ GPIS_DEV double lerp_d(double a, double b, double ratio) { return a * (1.0 - rat
 // 3D sampling, stationary kernel (config C0 and its per-path variants, C1 without the fast path)
 #define GPIS_PATH_NS spec_3d
 #define GPIS_FLAG_fbm_noise(M) 0
+#define GPIS_FLAG_sdf_mean(M) 0
 #define GPIS_FLAG_other_kernels(M) 0
 #define GPIS_FLAG_aniso_field(M) 0
 #define GPIS_FLAG_sampling_1d(M) 0
@@ -864,6 +873,7 @@ GPIS_DEV double lerp_d(double a, double b, double ratio) { return a * (1.0 - rat
 // 3D sampling, non-stationary length scale on the multi-resolution grid (config C3)
 #define GPIS_PATH_NS spec_3d_multires
 #define GPIS_FLAG_fbm_noise(M) 0
+#define GPIS_FLAG_sdf_mean(M) 0
 #define GPIS_FLAG_other_kernels(M) 0
 #define GPIS_FLAG_aniso_field(M) 0
 #define GPIS_FLAG_sampling_1d(M) 0

@@ -320,6 +320,21 @@ static int build_model(const gpis_params &P, DevModel &M, gpis_derived &D)
         double inv = len > 0 ? 1.0 / len : 0.0;
         for (int k = 0; k < 3; ++k) M.lin_dir[w][k] = mu.dir[k] * inv;
     }
+    {   // procedural SDF means (gpis_sdf.hpp): the three Mat4f::rotAxis((1,0,0), angle) of SdfFunctions.cpp, Mat4f.cpp:132-148 with the host libm
+        M.sdf_mean = M.mean[0].type == GPIS_MEAN_PROCEDURAL || (M.has_mean_additional && M.mean[1].type == GPIS_MEAN_PROCEDURAL);
+        const float angles[3] = {-90.f, 90.f, -45.f};
+        for (int r = 0; r < 3; ++r) {
+            const float angle = angles[r] * (3.1415926536f / 180.0f);      // Angle::degToRad
+            const float s = std::sin(angle), c = std::cos(angle), c1 = 1.0f - c;
+            const float x = 1.f, y = 0.f, z = 0.f;
+            const float R[9] = {c + x * x * c1, x * y * c1 - z * s, x * z * c1 + y * s,
+                                y * x * c1 + z * s, c + y * y * c1, y * z * c1 - x * s,
+                                z * x * c1 - y * s, z * y * c1 + x * s, c + z * z * c1};
+            memcpy(M.sdf_rot[r], R, sizeof R);
+        }
+        for (int w = 0; w < 2; ++w)
+            for (int i = 0; i < 12; ++i) M.sdf_inv[w][i] = (i % 5 == 0) ? 1.f : 0.f;       // Mat4f(): the identity
+    }
 
     memcpy(D.world_to_local, w2l, sizeof w2l);
     memcpy(D.local_to_world, l2w, sizeof l2w);
@@ -361,13 +376,27 @@ __global__ void __launch_bounds__(256) k_mean_color_emission(const DevModel *__r
     const V3d p{p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]};
     if (color3) {
         double c[3] = {1., 1., 1.};
-        if (M.color.enabled) field_vec(M.color, p, true, c);
+        if (M.color.enabled) field_vec(M.color, sdf::color_point(M, p), true, c);      // ProceduralMean::color: at T^-1 . Vec3f(p)
         for (int k = 0; k < 3; ++k) color3[3 * i + k] = (float)c[k];
     }
     if (emission3) {
         double e[3] = {0., 0., 0.};
         if (M.emission.enabled) field_vec(M.emission, p, true, e);
         for (int k = 0; k < 3; ++k) emission3[3 * i + k] = (float)e[k];
+    }
+}
+// GaussianProcess::mean_weight_space at double-precision points: value, chosen slot, dmean_da of that slot (any mean type)
+__global__ void __launch_bounds__(256) k_mean(const DevModel *__restrict__ Mp, size_t n, const double *__restrict__ p3, double *__restrict__ value,
+                                              int32_t *__restrict__ id, double *__restrict__ grad3)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const sdf::MeanId r = sdf::mean_weight_space(Mp, p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]);
+    if (value) value[i] = r.mean;
+    if (id) id[i] = r.id;
+    if (grad3) {
+        const V3d g = sdf::mean_grad(Mp, r.id, p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]);
+        grad3[3 * i] = g.x; grad3[3 * i + 1] = g.y; grad3[3 * i + 2] = g.z;
     }
 }
 __global__ void k_xxhash32(size_t n, int arity, const uint32_t *__restrict__ w, uint32_t *__restrict__ out)
@@ -438,8 +467,14 @@ extern "C" int gpis_create(const gpis_params *params, int device, gpis_medium **
     if (params->correlation_context < 0 || params->correlation_context > 3) return set_err(GPIS_ERR_INVALID_ARG, "Invalid correlation context: '%d'", params->correlation_context);
     if (params->scheme_1d < 0 || params->scheme_1d > 2) return set_err(GPIS_ERR_INVALID_ARG, "Invalid sparse conv sampling scheme: '%d'", params->scheme_1d);
     if (!(params->impulse_density >= 0.f) || params->impulse_density > 4096.f) return set_err(GPIS_ERR_INVALID_ARG, "impulse_density out of range");
-    if (params->mean.type < 0 || params->mean.type > 2 || (params->has_mean_additional && (params->mean_additional.type < 0 || params->mean_additional.type > 2)))
+    if (params->mean.type < 0 || params->mean.type > GPIS_MEAN_PROCEDURAL ||
+        (params->has_mean_additional && (params->mean_additional.type < 0 || params->mean_additional.type > GPIS_MEAN_PROCEDURAL)))
         return set_err(GPIS_ERR_INVALID_ARG, "invalid mean type");
+    for (int w = 0; w < (params->has_mean_additional ? 2 : 1); ++w) {
+        const gpis_mean &mu = w ? params->mean_additional : params->mean;
+        if (mu.type == GPIS_MEAN_PROCEDURAL && (mu.func < GPIS_SDF_KNOB || mu.func > GPIS_SDF_PLANE))
+            return set_err(GPIS_ERR_INVALID_ARG, "Invalid sdf function: '%d' (procedural mean, slot %d)", mu.func, w);
+    }
     if (params->nonstationary && (params->ls_ramp_type < 0 || params->ls_ramp_type > GPIS_NOISE_RUST)) return set_err(GPIS_ERR_INVALID_ARG, "invalid ls noise type");
     {
         const gpis_ramp *ramps[3] = {&params->var, &params->mean_color, &params->mean_emission};
@@ -702,7 +737,8 @@ static int wave_march(gpis_medium *m, size_t n, const gpis_ray_in *rays, const u
 
 // ---- persistent march launch (per-path media) ---------------------------------------------------------------
 // the lattice sums of gpis_persist.inc have a diagonal kernel matrix: every medium except world-space 3D with a full anisoMtx
-static bool persist_supported(const DevModel &H) { return !H.aniso.enabled && !H.fbm_noise && (H.sampling_1d || H.iso3d || !H.use_aniso_mtx); }
+// (a procedural mean is evaluated by the lane-per-ray all-features instance only: gpis_persist.inc states the analytic means inline)
+static bool persist_supported(const DevModel &H) { return !H.aniso.enabled && !H.fbm_noise && !H.sdf_mean && (H.sampling_1d || H.iso3d || !H.use_aniso_mtx); }
 // sideways (lane = impulse) evaluation pays while at most this many lanes of a wave have a job: lockstep costs
 // 27 n g instructions per round whatever the number of jobs, one sideways job ~20.6 cells x (c0 + c1 n)
 // (g = 61 generator, c0 = 135, c1 = 0.31: counted on the gfx950 ISA of these loops)
@@ -742,11 +778,11 @@ static int launch_persist(gpis_medium *m, PersistArgs a, hipStream_t s)
     return launch_check("k_persist_march");
 }
 // neePDF / neeGrad: the 1D-sampling instance for the media the NEE estimators are built for, else the all-features one
-int gpis::nee_instance(const DevModel &H) { return (H.sampling_1d && !H.fbm_noise) ? launch::INST_1D : launch::INST_GENERIC; }
+int gpis::nee_instance(const DevModel &H) { return (H.sampling_1d && !H.fbm_noise && !H.sdf_mean) ? launch::INST_1D : launch::INST_GENERIC; }
 // the lane-per-ray instance whose compile-time flags equal the medium's
 static int lane_instance(const DevModel &H)
 {
-    if (H.fbm_noise) return launch::INST_GENERIC;           // sandstone / rust fields: all-features instance only
+    if (H.fbm_noise || H.sdf_mean) return launch::INST_GENERIC;           // sandstone / rust fields, procedural means: all-features instance only
     if (H.sampling_1d) return launch::INST_1D;
     if (!H.nonstationary && !H.multi_res && !H.multi_resolution_grid && H.kernel_type == GPIS_KERNEL_SQUARED_EXPONENTIAL) return launch::INST_3D;
     if (H.nonstationary && H.multi_res && H.multi_resolution_grid && !H.aniso.enabled) return launch::INST_3D_MULTIRES;
@@ -946,10 +982,20 @@ extern "C" int gpis_mean_color_emission_batch(gpis_medium *m, size_t n, const do
     k_mean_color_emission<<<grid_of(n, 256), 256, 0, (hipStream_t)stream>>>(m->d_model, n, p3, color3, emission3);
     return launch_check("k_mean_color_emission");
 }
+extern "C" int gpis_mean_batch(gpis_medium *m, size_t n, const double *p3, double *value, int32_t *id, double *grad3, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && (n == 0 || p3));
+    if (n == 0 || (!value && !id && !grad3)) return GPIS_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    k_mean<<<grid_of(n, 256), 256, 0, (hipStream_t)stream>>>(m->d_model, n, p3, value, id, grad3);
+    return launch_check("k_mean");
+}
 // function-space comparison path: gpis_fs.hpp
 int gpis::fs_check(gpis_medium *m)
 {
     const DevModel &H = m->host_model;
+    if (H.sdf_mean)
+        return set_err(GPIS_ERR_UNSUPPORTED, "function-space path: a procedural (SDF) mean is outside its built scope");
     if (H.fs_n < 2 || H.fs_n > GPIS_FS_MAX_POINTS || !(H.fs_step >= 0) || H.kernel_type != GPIS_KERNEL_SQUARED_EXPONENTIAL || H.nonstationary ||
         H.use_aniso_mtx || H.has_mean_additional || (H.color.enabled && H.color.type >= GPIS_NOISE_SANDSTONE))
         return set_err(GPIS_ERR_INVALID_ARG, "function-space path: squared-exponential covariance, analytic mean (ramp colour), 2..64 sample points");
@@ -1091,6 +1137,26 @@ extern "C" int gpis_mean_color_emission_host(gpis_medium *m, size_t n, const dou
     HIP_TRY(hipDeviceSynchronize());
     if (color3) HIP_TRY(hipMemcpy(color3, m->stage[1], 3 * n * sizeof(float), hipMemcpyDeviceToHost));
     if (emission3) HIP_TRY(hipMemcpy(emission3, m->stage[2], 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    return GPIS_OK;
+}
+extern "C" int gpis_mean_host(gpis_medium *m, size_t n, const double *p3, double *value, int32_t *id, double *grad3)
+{
+    CHECK_ARGS(std_handle(m) && (n == 0 || p3));
+    if (n == 0 || (!value && !id && !grad3)) return GPIS_OK;
+    std::lock_guard<std::mutex> lock(m->mu);
+    HIP_TRY(hipSetDevice(m->device));
+    int st;
+    // stage[1]: n values, then 3 n gradient components; stage[2]: n ids
+    if ((st = ensure_stage(m, 0, 3 * n * sizeof(double))) || (st = ensure_stage(m, 1, 4 * n * sizeof(double))) || (st = ensure_stage(m, 2, n * sizeof(int32_t))))
+        return st;
+    double *d_val = (double *)m->stage[1], *d_grad = d_val + n;
+    HIP_TRY(hipMemcpy(m->stage[0], p3, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+    st = gpis_mean_batch(m, n, (const double *)m->stage[0], value ? d_val : nullptr, id ? (int32_t *)m->stage[2] : nullptr, grad3 ? d_grad : nullptr, nullptr);
+    if (st) return st;
+    HIP_TRY(hipDeviceSynchronize());
+    if (value) HIP_TRY(hipMemcpy(value, d_val, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (id) HIP_TRY(hipMemcpy(id, m->stage[2], n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (grad3) HIP_TRY(hipMemcpy(grad3, d_grad, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
     return GPIS_OK;
 }
 extern "C" int gpis_xxhash32_batch(gpis_medium *m, size_t n, int arity, const uint32_t *words, uint32_t *out, void *stream)
@@ -1329,6 +1395,8 @@ extern "C" int gpis_build_guide(gpis_medium *m, int half_extent_cells, int point
     std::lock_guard<std::mutex> lock(m->mu);
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
+    if (m->host_model.sdf_mean)
+        return set_err(GPIS_ERR_UNSUPPORTED, "gpis_build_guide: a procedural (SDF) mean has no guide field (no per-brick bound of such a mean is built)");
     if (!m->fast.enabled)
         return set_err(GPIS_ERR_UNSUPPORTED, "gpis_build_guide: the medium is not covered by the wave-cooperative path (single_realization, 3D, stationary SE, diagonal anisotropy)");
     int st = launch::guide_build(m->host_model, m->d_model, m->fast, half_extent_cells, points_per_cell, &m->guide, getenv("GPIS_GUIDE_DENSE") == nullptr);
@@ -1477,6 +1545,56 @@ extern "C" int gpis_set_variance_grid(gpis_medium *m, const gpis_variance_grid *
     G.interpolate = g->interpolate;
     for (int c = 0; c < 3; ++c) { G.dims[c] = g->dims[c]; G.origin[c] = g->origin[c]; G.lo[c] = g->bounds_min[c] + 2; G.hi[c] = g->bounds_max[c] - 3; }
     for (int i = 0; i < 12; ++i) G.T[i] = g->inv_natural_transform[i];
+    HIP_TRY(hipMemcpy(m->d_model, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
+    return GPIS_OK;
+}
+
+// Mat4f::invert (Mat4f.hpp:75-101): the adjugate over the determinant, in float.  inv[4 i + j] is the cofactor of (row j, column i):
+// with r0 < r1 < r2 the rows other than j and c0 < c1 < c2 the columns other than i, six triple products (a*b)*c summed left to
+// right in the order and with the signs below (all flipped when i + j is odd) — the order the reference's expanded lines have.
+// det = a[0] inv[0] + a[1] inv[4] + a[2] inv[8] + a[3] inv[12]; det == 0 gives the identity.
+static void mat4_invert_ref(const float *a, float *out)
+{
+    static const int pick[6][3] = {{0, 1, 2}, {0, 1, 2}, {1, 0, 2}, {1, 0, 2}, {2, 0, 1}, {2, 0, 1}};     // rows of the three factors
+    static const int cols[6][3] = {{0, 1, 2}, {0, 2, 1}, {0, 1, 2}, {0, 2, 1}, {0, 1, 2}, {0, 2, 1}};     // their columns
+    static const int minus[6] = {0, 1, 1, 0, 0, 1};
+    float inv[16];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            int r[3], c[3];
+            for (int k = 0, nr = 0, nc = 0; k < 4; ++k) {
+                if (k != j) r[nr++] = k;
+                if (k != i) c[nc++] = k;
+            }
+            const int flip = (i + j) & 1;
+            float acc = 0.0f;
+            for (int t = 0; t < 6; ++t) {
+                const float term = a[4 * r[pick[t][0]] + c[cols[t][0]]] * a[4 * r[pick[t][1]] + c[cols[t][1]]] * a[4 * r[pick[t][2]] + c[cols[t][2]]];
+                const int neg = minus[t] ^ flip;
+                if (t == 0) acc = neg ? -term : term;
+                else acc = neg ? acc - term : acc + term;
+            }
+            inv[4 * i + j] = acc;
+        }
+    const float det = a[0] * inv[0] + a[1] * inv[4] + a[2] * inv[8] + a[3] * inv[12];
+    if (det == 0.0f) {
+        for (int i = 0; i < 16; ++i) out[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+        return;
+    }
+    const float invDet = 1.0f / det;
+    for (int i = 0; i < 16; ++i) out[i] = inv[i] * invDet;
+}
+extern "C" int gpis_set_mean_transform(gpis_medium *m, int which, const float transform[16])
+{
+    CHECK_ARGS(std_handle(m) && transform && (which == 0 || which == 1));
+    if (m->host_model.mean[which].type != GPIS_MEAN_PROCEDURAL || (which == 1 && !m->host_model.has_mean_additional))
+        return set_err(GPIS_ERR_INVALID_ARG, "gpis_set_mean_transform: slot %d holds no procedural mean", which);
+    std::lock_guard<std::mutex> lock(m->mu);
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipDeviceSynchronize());
+    float inv[16];
+    mat4_invert_ref(transform, inv);
+    memcpy(m->host_model.sdf_inv[which], inv, 12 * sizeof(float));
     HIP_TRY(hipMemcpy(m->d_model, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
     return GPIS_OK;
 }

@@ -6,6 +6,38 @@
 namespace gpis {
 namespace GPIS_PATH_NS {
 
+// ---- means: the analytic ones of gpis_device.hpp or, in the all-features instance, a procedural SDF mean (gpis_sdf.hpp) ----
+GPIS_DEV void path_mean_weight_space(const DevModel &M, V3d p, double &mean, int &id)
+{
+    if (GPIS_FLAG_sdf_mean(M)) {
+        const sdf::MeanId r = sdf::mean_weight_space(&M, p.x, p.y, p.z);
+        mean = r.mean;
+        id = r.id;
+        return;
+    }
+    mean_weight_space(M, p, mean, id);
+}
+GPIS_DEV V3d path_mean_grad(const DevModel &M, int id, V3d p)
+{
+    if (GPIS_FLAG_sdf_mean(M))
+        return sdf::mean_grad(&M, id, p.x, p.y, p.z);
+    return mean_grad(M, id, p);
+}
+// conditioning_finish3d / 1d are shared with the persistent march (gpis_persist.inc), which does not serve procedural means: its
+// calls take the default SDF_MEAN = false and compile to the analytic means alone, as before
+template <bool SDF_MEAN> GPIS_DEV void cond_mean_weight_space(const DevModel &M, V3d p, double &mean, int &id)
+{
+    if (SDF_MEAN) path_mean_weight_space(M, p, mean, id);
+    else mean_weight_space(M, p, mean, id);
+}
+template <bool SDF_MEAN> GPIS_DEV V3d cond_mean_grad(const DevModel &M, int id, V3d p)
+{
+    if (SDF_MEAN) return path_mean_grad(M, id, p);
+    return mean_grad(M, id, p);
+}
+// the point of MeanFunction::color on a hit (GPM.cpp:316; ProceduralMean::color, GPF.hpp:1065-1073)
+GPIS_DEV V3d path_color_point(const DevModel &M, V3d p) { return GPIS_FLAG_sdf_mean(M) ? sdf::color_point(M, p) : p; }
+
 // ---- covariance layer --------------------------------------------------------------------
 GPIS_DEV float ls_field(const DevModel &M, V3d p)   // getKernelScale: the largest component of the ProceduralNoiseVec, GPF.cpp:87-120, 1729-1735
 {
@@ -765,7 +797,7 @@ GPIS_PATH_EVAL float evaluate_value(const DevModel &M, Realization &r, V3 p, V3 
     float noise_val = GPIS_FLAG_sampling_1d(M) ? eval_value_noise1d(M, r, p, rayDir, seed, true) : eval_noise3d(M, r, p, rayDir, seed, true).v;
     double mean;
     int id;
-    mean_weight_space(M, to_d(p), mean, id);
+    path_mean_weight_space(M, to_d(p), mean, id);
     gp_id = id;
     if (M.surf_vol_phase_separate) {          // getUnscaledVariance = 1 (GPF.hpp:1185) except in the grid flavour (GPF.cpp:1386-1391)
         float uv = 1.f;
@@ -787,8 +819,8 @@ GPIS_PATH_EVAL V3 evaluate_gradient(const DevModel &M, Realization &r, V3 p, flo
     }
     double mean;
     int id;
-    mean_weight_space(M, to_d(p), mean, id);
-    V3 mg = to_f(mean_grad(M, id, to_d(p)));
+    path_mean_weight_space(M, to_d(p), mean, id);
+    V3 mg = to_f(path_mean_grad(M, id, to_d(p)));
     return cov_amplitude(M, p) * ng + mg;
 }
 
@@ -806,7 +838,7 @@ GPIS_DEV bool conditioning_begin(const DevModel &M, Realization &r, V3 p)
     return cov_amplitude(M, p) != 0;
 }
 // c4 = evaluateNoise3D(p, conditioning = false) (value and gradient)
-GPIS_DEV void conditioning_finish3d(const DevModel &M, Realization &r, V3 p, V3 rayDir, float targetVal, V3 targetGrad, V4 c4)
+template <bool SDF_MEAN = false> GPIS_DEV void conditioning_finish3d(const DevModel &M, Realization &r, V3 p, V3 rayDir, float targetVal, V3 targetGrad, V4 c4)
 {
     LevelInfo K{};
     if (GPIS_FLAG_multi_res(M))
@@ -814,7 +846,7 @@ GPIS_DEV void conditioning_finish3d(const DevModel &M, Realization &r, V3 p, V3 
     float amplitude = cov_amplitude(M, p);
     double mean_d;
     int id;
-    mean_weight_space(M, to_d(p), mean_d, id);
+    cond_mean_weight_space<SDF_MEAN>(M, to_d(p), mean_d, id);
     float mean = (float)mean_d;
     const bool plus = M.ctx == GPIS_CTX_RENEWAL_PLUS;
     float cur = c4.v;
@@ -823,7 +855,7 @@ GPIS_DEV void conditioning_finish3d(const DevModel &M, Realization &r, V3 p, V3 
         r.c.value_scale /= K.ratio_lo + K.ratio_hi;
     r.n_eval++;                       // the discarded re-evaluation
     if (plus) {
-        V3 mg = to_f(mean_grad(M, id, to_d(p)));
+        V3 mg = to_f(cond_mean_grad<SDF_MEAN>(M, id, to_d(p)));
         r.n_eval++;                   // the reference evaluates the unconditioned field a second time: same value
         V3 delta = (targetGrad - mg) / amplitude - v3(c4.gx, c4.gy, c4.gz);
         float S[9];
@@ -854,7 +886,7 @@ GPIS_DEV void conditioning_finish3d(const DevModel &M, Realization &r, V3 p, V3 
     }
 }
 // bl / bh = evaluateNoise1DNormalized(p, conditioning = false) of the level(s) (bh = bl when not multi-resolution)
-GPIS_DEV void conditioning_finish1d(const DevModel &M, Realization &r, V3 p, V3 rayDir, float targetVal, V3 targetGrad, const RayInfo &info, V4 bl, V4 bh)
+template <bool SDF_MEAN = false> GPIS_DEV void conditioning_finish1d(const DevModel &M, Realization &r, V3 p, V3 rayDir, float targetVal, V3 targetGrad, const RayInfo &info, V4 bl, V4 bh)
 {
     LevelInfo K{};
     if (GPIS_FLAG_multi_res(M))
@@ -862,7 +894,7 @@ GPIS_DEV void conditioning_finish1d(const DevModel &M, Realization &r, V3 p, V3 
     float amplitude = cov_amplitude(M, p);
     double mean_d;
     int id;
-    mean_weight_space(M, to_d(p), mean_d, id);
+    cond_mean_weight_space<SDF_MEAN>(M, to_d(p), mean_d, id);
     float mean = (float)mean_d;
     const bool plus = M.ctx == GPIS_CTX_RENEWAL_PLUS;
     float cur = GPIS_FLAG_multi_res(M) ? K.ratio_lo * bl.v + K.ratio_hi * bh.v : bl.v;
@@ -871,7 +903,7 @@ GPIS_DEV void conditioning_finish1d(const DevModel &M, Realization &r, V3 p, V3 
         r.c.value_scale /= K.ratio_lo * K.ratio_lo + K.ratio_hi * K.ratio_hi;
     r.n_eval++;
     if (plus) {
-        V3 mg = to_f(mean_grad(M, id, to_d(p)));
+        V3 mg = to_f(cond_mean_grad<SDF_MEAN>(M, id, to_d(p)));
         r.n_eval++;
         V3 cgw = gradient_noise1d_finish(M, p, 0.f, rayDir, info, K, bl, bh);
         V3 delta = (targetGrad - mg) / amplitude - cgw;
@@ -902,11 +934,11 @@ GPIS_PATH_EVAL void conditioning(const DevModel &M, Realization &r, V3 p, V3 ray
             bl = eval_noise1d_normalized(M, r, p, rayDir, seed, L.add_lo, R, L.lo, false, 1.0f);
             bh = eval_noise1d_normalized(M, r, p, rayDir, seed, L.add_hi, R, L.hi, false, 1.0f);
         }
-        conditioning_finish1d(M, r, p, rayDir, targetVal, targetGrad, info, bl, bh);
+        conditioning_finish1d<true>(M, r, p, rayDir, targetVal, targetGrad, info, bl, bh);
         return;
     }
     V4 c4 = eval_noise3d(M, r, p, rayDir, seed, false);
-    conditioning_finish3d(M, r, p, rayDir, targetVal, targetGrad, c4);
+    conditioning_finish3d<true>(M, r, p, rayDir, targetVal, targetGrad, c4);
 }
 
 // neeShared / neeGrad / neePDF, SCN.cpp:601-743
@@ -916,8 +948,8 @@ GPIS_DEV void nee_shared(const DevModel &M, Realization &r, V3 rayDir, V3 normal
     float amplitude = cov_amplitude(M, p);
     double mean_d;
     int id;
-    mean_weight_space(M, to_d(p), mean_d, id);
-    V3 mg = to_f(mean_grad(M, id, to_d(p)));
+    path_mean_weight_space(M, to_d(p), mean_d, id);
+    V3 mg = to_f(path_mean_grad(M, id, to_d(p)));
     Frame coord = frame_from_normal(normalized(cov_pos_w2l(M, rayDir, 1.0f)));
     float rc[9] = {coord.tangent.x, coord.bitangent.x, coord.normal.x,
                    coord.tangent.y, coord.bitangent.y, coord.normal.y,
@@ -1186,7 +1218,7 @@ GPIS_DEV void sample_distance_one(const DevModel &M, Realization &noise, const g
         out.sample_t = ft < maxT ? ft : maxT;
         out.continued_t = ft;
         double col[3] = {1., 1., 1.};
-        if (!exited && M.color.enabled) field_vec(M.color, ray_at(ro, rd, t), GPIS_FLAG_fbm_noise(M), col);   // color(ro + rd*t), GPM.cpp:316
+        if (!exited && M.color.enabled) field_vec(M.color, path_color_point(M, ray_at(ro, rd, t)), GPIS_FLAG_fbm_noise(M), col);   // color(ro + rd*t), GPM.cpp:316
         for (int c = 0; c < 3; ++c) {
             out.weight[c] = (float)col[c] * M.sigma_s_over_t[c];
             out.continued_weight[c] = (float)col[c] * M.sigma_s_over_t[c];
@@ -1230,6 +1262,7 @@ struct Path {
 
 #undef GPIS_PATH_NS
 #undef GPIS_FLAG_fbm_noise
+#undef GPIS_FLAG_sdf_mean
 #undef GPIS_PATH_OUTLINE_NOISE3D
 #undef GPIS_PATH_EVAL
 #undef GPIS_FLAG_other_kernels

@@ -24,7 +24,7 @@ struct FastTable {
 
 inline bool fast_supported(const DevModel &M)
 {
-    return M.single_realization && !M.sampling_1d && !M.nonstationary && !M.use_aniso_mtx && !M.absorption_only && !M.color.enabled && M.kernel_type == GPIS_KERNEL_SQUARED_EXPONENTIAL &&
+    return M.single_realization && !M.sampling_1d && !M.nonstationary && !M.use_aniso_mtx && !M.absorption_only && !M.color.enabled && !M.sdf_mean && M.kernel_type == GPIS_KERNEL_SQUARED_EXPONENTIAL &&
            M.n_impulses >= 1 && M.n_impulses <= 64;
 }
 inline void fast_table_free(FastTable *t)

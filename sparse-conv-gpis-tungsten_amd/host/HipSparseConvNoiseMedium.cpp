@@ -107,6 +107,7 @@ struct HostJson {
         out = v;
         return true;
     }
+    static bool has(const Node &o, const char *key) { return o->get(key) != nullptr; }
     template <typename T> static void num(const Node &o, const char *key, T &dst)
     {
         if (const JValue *v = o->get(key)) {
@@ -136,6 +137,17 @@ struct HostJson {
             if (m->kind == JValue::Array && m->arr.size() == 9)
                 for (int i = 0; i < 9; ++i) dst9[i] = (float)m->arr[i].num;
     }
+    static int mat4f(const Node &o, const char *key, float *dst16)
+    {
+        const JValue *m = o->get(key);
+        if (!m) return 0;
+        if (m->kind != JValue::Array || m->arr.size() != 16) return -1;
+        for (int i = 0; i < 16; ++i) {
+            if (m->arr[i].kind != JValue::Number) return -1;
+            dst16[i] = (float)m->arr[i].num;
+        }
+        return 1;
+    }
     [[noreturn]] static void fail(const std::string &what) { throw std::runtime_error(what); }
 };
 
@@ -160,7 +172,12 @@ void HipSparseConvNoiseMedium::fromJson(const std::string &json)
     JValue v = parser.parse();
     if (v.kind != JValue::Object) throw std::runtime_error("medium JSON must be an object");
     HostJson::num(&v, "max_bounces", _params.max_bounces);      // Medium::fromJson (Medium.cpp:29-38)
-    gpis_json::readMedium<HostJson>(&v, _params);               // the key table shared with the integration adapter (include/gpis_json.hpp)
+    gpis_json::MeanTransforms tf;
+    gpis_json::readMedium<HostJson>(&v, _params, &tf);          // the key table shared with the integration adapter (include/gpis_json.hpp)
+    for (int w = 0; w < 2; ++w) {
+        _meanTransformSet[w] = tf.set[w];
+        std::memcpy(_meanTransform[w], tf.m[w], sizeof tf.m[w]);
+    }
 }
 
 void HipSparseConvNoiseMedium::prepareForRender(int device)
@@ -176,6 +193,12 @@ void HipSparseConvNoiseMedium::prepareForRender(int device)
         _handle = nullptr;
         throw std::runtime_error(std::string("gpis_create failed: ") + gpis_last_error());
     }
+    for (int w = 0; w < 2; ++w)        // the "transform" of a procedural mean
+        if (_meanTransformSet[w] && gpis_set_mean_transform(_handle, w, _meanTransform[w]) != GPIS_OK) {
+            const std::string msg = std::string("gpis_set_mean_transform failed: ") + gpis_last_error();
+            teardownAfterRender();
+            throw std::runtime_error(msg);
+        }
 }
 void HipSparseConvNoiseMedium::teardownAfterRender()
 {

@@ -112,6 +112,10 @@ public:
     void fromJson(const std::string &json);
     void setParams(const gpis_params &p) { _params = p; }
     const gpis_params &params() const { return _params; }
+    // the "transform" of a procedural mean as read from the JSON (which = 0: mean, 1: mean_additional); handed to
+    // gpis_set_mean_transform by prepareForRender
+    int meanTransformSet(int which) const { return _meanTransformSet[which]; }
+    const float *meanTransform(int which) const { return _meanTransform[which]; }
 
     bool isHomogeneous() const { return false; }                  // GPM.cpp:147-150
     void prepareForRender(int device = 0);                        // GPM.cpp:152-158 + device handle
@@ -145,6 +149,8 @@ private:
     void applyResult(const Ray &ray, const gpis_seg_out &o, const gpis_cond_coeff &c, MediumState &state, MediumSample &sample) const;
 
     gpis_params _params;
+    int _meanTransformSet[2] = {0, 0};             // "transform" of a procedural mean (mean, mean_additional): set on the handle after gpis_create
+    float _meanTransform[2][16] = {};
     gpis_medium *_handle = nullptr;
     float _sigmaA[3] = {0, 0, 0}, _sigmaS[3] = {0, 0, 0}, _sigmaT[3] = {0, 0, 0};
 };
