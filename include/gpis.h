@@ -72,12 +72,13 @@ typedef enum gpis_corr_ctx {
 /* SparseConv1DSamplingScheme, src/core/media/Medium.hpp:40-44. */
 typedef enum gpis_scheme_1d { GPIS_UNI = 0, GPIS_NEE = 1, GPIS_MIS = 2 } gpis_scheme_1d;
 
-/* Mean functions, src/core/math/GPFunctions.hpp:867-1005. */
+/* Mean functions, src/core/math/GPFunctions.hpp:867-1087. */
 typedef enum gpis_mean_type {
     GPIS_MEAN_HOMOGENEOUS = 0,   /* offset                       GPF.hpp:867-901  */
     GPIS_MEAN_SPHERICAL = 1,     /* |p-c| - r                    GPF.hpp:903-945  */
     GPIS_MEAN_LINEAR = 2,        /* max((p-ref).dir*scale, min)  GPF.hpp:947-1005 */
-    GPIS_MEAN_PROCEDURAL = 3     /* max(min, sdf(T^-1 p)*scale + offset)  GPF.hpp:1049-1087, GPF.cpp:250-296 */
+    GPIS_MEAN_PROCEDURAL = 3,    /* max(min, sdf(T^-1 p)*scale + offset)  GPF.hpp:1049-1087, GPF.cpp:250-296 */
+    GPIS_MEAN_TABULATED = 4      /* (grid(W p) + offset)*scale, W = world -> index; "volume": -log(max(1e-4, grid))  GPF.hpp:1007-1025, GPF.cpp:143-194 */
 } gpis_mean_type;
 
 /* SdfFunctions::Function (math/SdfFunctions.hpp:12-18, same numeric order): the shape of a procedural mean, "func". */
@@ -126,18 +127,34 @@ typedef enum gpis_kernel_type {
 typedef struct gpis_mean {
     int32_t type;          /* gpis_mean_type */
     float radius;          /* spherical */
-    float offset;          /* homogeneous; procedural "offset" */
-    float scale;           /* linear; procedural "scale" */
+    float offset;          /* homogeneous; procedural "offset"; tabulated "offset" (JSON default 0) */
+    float scale;           /* linear; procedural "scale"; tabulated "scale" (JSON default 1) */
     float min;             /* linear, procedural (default -FLT_MAX) */
-    int32_t func;          /* procedural: gpis_sdf_function; not read for the other types */
+    int32_t func;          /* procedural: gpis_sdf_function; tabulated: != 0 is the "volume" flag (the field is reused, as the
+                              procedural mean reused the former padding word); not read for the other types */
     double center[3];      /* spherical centre / linear reference_point */
     double dir[3];         /* linear direction (normalised by gpis_create as LinearMean::fromJson does) */
 } gpis_mean;
 /* A procedural mean is ProceduralMean over one of the reference's SDF shapes: mean(a) = max(min, sdf(T^-1 . float(a)) * scale + offset)
- * in float, widened; dmean_da is the reference's one-sided difference with eps = 0.001f (GPF.cpp:279-296).  T is the mean's
- * "transform" (identity until gpis_set_mean_transform).  Such a medium runs on the lane-per-ray all-features path instance (GPIS_OPT_PERSISTENT
- * has no effect on it): no fast table, no guide field, no wavefront form; the function-space and weight-space media refuse it.  Scalar-field objects ("f") are outside
- * the built scope. */
+ * in float, widened; dmean_da is the reference's one-sided difference with eps = 0.001f, evaluated in the order a, +x, +y, +z
+ * (GPF.cpp:279-296).  T is the mean's "transform" (identity until gpis_set_mean_transform).  Scalar-field objects ("f") are
+ * outside the built scope.
+ *
+ * A tabulated mean is TabulatedMean over a dense voxel grid (gpis_set_mean_grid; the descriptor and the lookup are those of
+ * gpis_variance_grid below): res = double(density(W . float(a))) with W the grid's world -> index transform; with "volume"
+ * (func != 0) res = -log(max(0.0001, res)) in double; mean(a) = (res + offset) * scale in double — NOT the procedural
+ * sdf * scale + offset.  dmean_da is the one-sided difference with the double eps = 0.001, evaluated in the order +x, +y, +z, a
+ * (GPF.cpp:165-190).  It reads offset, scale and func only.  Until a grid is set the density is 0, the background of an empty
+ * tree.  Its colour field is evaluated at a itself; its emission is the grid's (GPF.cpp:174-177), and emission, detail and
+ * temperature grids are outside the built scope: a medium whose PRIMARY mean is tabulated emits 0 whatever its mean_emission
+ * field says.  The "quadratic" sampler is refused; sparse VDB files are read by the loader, which hands over a dense array.
+ *
+ * Where such media run: either type, in either slot of the CSG pair, is served by the sparse-convolution medium (gpis_create) on
+ * the lane-per-ray all-features path instance — all gpis_render_scene_s* frame drivers, both adaptive entries, the batch entry
+ * points.  GPIS_OPT_PERSISTENT has no effect on them; there is no fast table, no wavefront and no persistent form, and
+ * gpis_build_guide refuses them (GPIS_ERR_UNSUPPORTED).  The function-space entries (gpis_fs_*) refuse them with
+ * GPIS_ERR_UNSUPPORTED and gpis_ws_create (the weight-space medium) with GPIS_ERR_INVALID_ARG, each with a message that names the
+ * mean. */
 
 /*
  * All JSON keys of the hot path (SURVEY.md §5 "Config / flags"):
@@ -598,6 +615,14 @@ void gpis_default_scene_s(gpis_scene_s *s, uint32_t width, uint32_t height, uint
 /* Copies `voxels` (host pointer, dims[0] * dims[1] * dims[2] floats) to the device and switches the lookup on.  The medium must
  * have been created with grid_nonstationary = 1.  Not to be called while work of this handle is in flight. */
 int gpis_set_variance_grid(gpis_medium *m, const gpis_variance_grid *g, const float *voxels);
+
+/* The voxel grid of a tabulated mean (TabulatedMean::_grid, GPF.cpp:143-153), in the descriptor gpis_set_variance_grid takes.
+ * which = 0: mean, 1: mean_additional.  Copies `voxels` (host pointer, dims[0] * dims[1] * dims[2] floats) to the device; the copy
+ * belongs to the handle, is replaced by a second call for the same slot and freed by gpis_destroy.  It is independent of the
+ * variance grid's copy: a medium may carry both.  Waits for the device, takes the handle's lock; not to be called while work of
+ * this handle is in flight.  GPIS_ERR_INVALID_ARG for a slot that is not tabulated, for which = 1 without has_mean_additional,
+ * for null or non-positive dims and for interpolate outside {0, 1} ("quadratic" is refused, as for the variance grid). */
+int gpis_set_mean_grid(gpis_medium *m, int which, const gpis_variance_grid *g, const float *voxels);
 
 /* Allocates the workspace gpis_render_scene_s needs for `s` ahead of the first frame: 71 B per sample of the largest chunk the
  * device holds with the compact records (the resident march, GPIS_OPT_SCENE_COMPACT: 9.5 GB for a whole 1920x1080x64 frame),

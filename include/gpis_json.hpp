@@ -124,6 +124,14 @@ template <class A> void readMean(const typename A::Node &m, gpis_mean &dst, Mean
             tf->set[which] = 1;
             for (int i = 0; i < 16; ++i) tf->m[which][i] = t[i];
         }
+    } else if (type == "tabulated") {                // TabulatedMean::fromJson, GPFunctions.cpp:143-153
+        dst.type = GPIS_MEAN_TABULATED;
+        dst.offset = 0.f; dst.scale = 1.f;           // GPFunctions.hpp:1007-1025
+        dst.func = 0;                                // "volume" travels in gpis_mean.func (include/gpis.h)
+        A::num(m, "offset", dst.offset);
+        A::num(m, "scale", dst.scale);
+        A::flag(m, "volume", dst.func);
+        // the "grid" VDB itself is handed over by the loader with gpis_set_mean_grid
     } else {
         A::fail("Unsupported mean function type: '" + type + "'");
     }

@@ -19,7 +19,7 @@ class SCHEME:
 
 
 class MEAN_TYPE:
-    HOMOGENEOUS, SPHERICAL, LINEAR, PROCEDURAL = 0, 1, 2, 3
+    HOMOGENEOUS, SPHERICAL, LINEAR, PROCEDURAL, TABULATED = 0, 1, 2, 3, 4
 
 
 class SDF_FUNCTION:
@@ -349,7 +349,7 @@ class GpisLib:
         "gpis_sample_distance_batch", "gpis_transmittance_batch", "gpis_eval_value_batch",
         "gpis_eval_gradient_batch", "gpis_conditioning_batch", "gpis_nee_pdf_batch", "gpis_nee_grad_batch",
         "gpis_xxhash32_batch", "gpis_pcg32_stream_batch", "gpis_mean_color_emission_batch", "gpis_mean_color_emission_host",
-        "gpis_mean_batch", "gpis_mean_host", "gpis_set_mean_transform",
+        "gpis_mean_batch", "gpis_mean_host", "gpis_set_mean_transform", "gpis_set_mean_grid",
         "gpis_fs_sample_distance_batch", "gpis_fs_transmittance_batch", "gpis_fs_linalg_batch", "gpis_libm_batch", "gpis_sort_pairs_u32",
         "gpis_fs_sample_distance_host", "gpis_fs_transmittance_host",
         "gpis_sample_distance_host", "gpis_transmittance_host", "gpis_eval_value_host", "gpis_eval_gradient_host",
@@ -407,6 +407,7 @@ class GpisLib:
         L.gpis_mean_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp]
         L.gpis_mean_host.argtypes = [vp, sz, vp, vp, vp, vp]
         L.gpis_set_mean_transform.argtypes = [vp, i32, vp]
+        L.gpis_set_mean_grid.argtypes = [vp, i32, vp, vp]
         L.gpis_xxhash32_batch.argtypes = [vp, sz, i32, vp, vp, vp]
         L.gpis_pcg32_stream_batch.argtypes = [vp, sz, vp, u32, vp, vp]
         L.gpis_sample_distance_host.argtypes = [vp, sz, vp, vp, vp]
@@ -780,6 +781,11 @@ class Medium:
         """the "transform" of a procedural mean (a 4x4 matrix, row-major); which = 0: mean, 1: mean_additional"""
         t = np.ascontiguousarray(transform, dtype=np.float32).reshape(16)
         self.L.check(self.L.lib.gpis_set_mean_transform(self.h, int(which), _ptr(t)), "gpis_set_mean_transform")
+
+    def set_mean_grid(self, which, voxels, world_to_index, interpolate="linear", origin=(0, 0, 0)):
+        """the voxel grid of a tabulated mean (which = 0: mean, 1: mean_additional); arguments as variance_grid_desc / set_variance_grid"""
+        d, v = variance_grid_desc(voxels, world_to_index, interpolate, origin)
+        self.L.check(self.L.lib.gpis_set_mean_grid(self.h, int(which), d.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p)), "gpis_set_mean_grid")
 
     def eval_value(self, q):
         q = np.ascontiguousarray(q, dtype=QUERY)

@@ -112,9 +112,15 @@ struct DevModel {
     gpis_mean mean[2];
     double lin_dir[2][3];
     // procedural SDF means (gpis_sdf.hpp); behind everything else, so no other field moves
-    int32_t sdf_mean;             // a slot in use is GPIS_MEAN_PROCEDURAL: only the all-features path instance evaluates those
+    int32_t sdf_mean;             // a slot in use needs the out-of-line mean (GPIS_MEAN_PROCEDURAL or GPIS_MEAN_TABULATED): only the
+                                  // all-features path instance evaluates those
     float sdf_rot[3][9];          // Mat4f::rotAxis((1,0,0), -90 / 90 / -45), rows 0..2 (Mat4f.cpp:132-148, host libm)
     float sdf_inv[2][12];         // rows 0..2 of the slot's _invConfigTransform (gpis_set_mean_transform; identity by default)
+    // tabulated means (gpis_grid_mean.hpp): the slot's voxel grid (gpis_set_mean_grid; vox == nullptr: density 0) and "volume" flag.
+    // Of a mean grid only the lookup's fields are set (vox, interpolate, dims, origin, lo, hi, T): `on`, the DevGrid's own offset /
+    // scale and the surface / volume fields stay 0 and are not read — the mean's "offset" / "scale" are gpis_mean's, in mean[w]
+    DevGrid mean_grid[2];
+    int32_t mean_volume[2];
 };
 
 struct Counters {
@@ -359,35 +365,20 @@ GPIS_DEV void field_vec(const DevRamp &R, V3d p, bool fbm_possible, double out[3
     }
     out[0] = out[1] = out[2] = ramp_eval(R, p);
 }
-// ---- GridNonstationaryCovariance, GPF.cpp:1386-1427 over VdbGrid::density, VdbGrid.cpp:405-431 (OpenVDB's PointSampler / BoxSampler
-// restated from tools/Interpolation.h — absent dependency, parity unpinned for the lookup; same code as the oracle's).  Cold code of
+}   // namespace gpis
+
+// in mid-file on purpose: behind DevGrid, DevModel, V3d and log_glibc, which the header needs (it names them), and in front of
+// grid_unscaled_variance, which calls its grid_density
+#include "gpis_grid_mean.hpp"      // grid_density, tabulated_mean
+
+namespace gpis {
+
+// ---- GridNonstationaryCovariance, GPF.cpp:1386-1427 over VdbGrid::density (grid_density, gpis_grid_mean.hpp).  Cold code of
 // the all-features path instance: not inlined.
 static __device__ __attribute__((noinline)) float grid_unscaled_variance(const DevGrid &G, double pxd, double pyd, double pzd)
 {
     if (!G.vox) return 1.f;
-    const float x = (float)pxd, y = (float)pyd, z = (float)pzd;
-    float q[3] = {G.T[0] * x + G.T[1] * y + G.T[2] * z + G.T[3], G.T[4] * x + G.T[5] * y + G.T[6] * z + G.T[7], G.T[8] * x + G.T[9] * y + G.T[10] * z + G.T[11]};
-    for (int c = 0; c < 3; ++c) {
-        const float v = q[c] < G.lo[c] ? G.lo[c] : q[c];
-        q[c] = v < G.hi[c] ? v : G.hi[c];
-    }
-    auto voxel = [&](long i, long j, long k) -> float {
-        i -= G.origin[0]; j -= G.origin[1]; k -= G.origin[2];
-        if (i < 0 || j < 0 || k < 0 || i >= G.dims[0] || j >= G.dims[1] || k >= G.dims[2]) return 0.f;
-        return G.vox[(size_t)i + (size_t)G.dims[0] * ((size_t)j + (size_t)G.dims[1] * (size_t)k)];
-    };
-    auto lerp = [](float a, float b, double w) -> float { const double temp = (double)(b - a) * w; return a + (float)temp; };
-    const double xd = q[0], yd = q[1], zd = q[2];
-    float dens;
-    if (G.interpolate == 0) {
-        dens = voxel((long)floor(xd + 0.5), (long)floor(yd + 0.5), (long)floor(zd + 0.5));
-    } else {
-        const double fx = floor(xd), fy = floor(yd), fz = floor(zd);
-        const long i = (long)fx, j = (long)fy, k = (long)fz;
-        const double u = xd - fx, v = yd - fy, w = zd - fz;
-        dens = lerp(lerp(lerp(voxel(i, j, k), voxel(i, j, k + 1), w), lerp(voxel(i, j + 1, k), voxel(i, j + 1, k + 1), w), v),
-                    lerp(lerp(voxel(i + 1, j, k), voxel(i + 1, j, k + 1), w), lerp(voxel(i + 1, j + 1, k), voxel(i + 1, j + 1, k + 1), w), v), u);
-    }
+    const float dens = grid_density(G, (float)pxd, (float)pyd, (float)pzd);
     return (dens + G.offset) * G.scale;
 }
 // getVariance, GPF.cpp:1393-1403

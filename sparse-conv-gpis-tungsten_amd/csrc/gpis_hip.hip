@@ -321,7 +321,8 @@ static int build_model(const gpis_params &P, DevModel &M, gpis_derived &D)
         for (int k = 0; k < 3; ++k) M.lin_dir[w][k] = mu.dir[k] * inv;
     }
     {   // procedural SDF means (gpis_sdf.hpp): the three Mat4f::rotAxis((1,0,0), angle) of SdfFunctions.cpp, Mat4f.cpp:132-148 with the host libm
-        M.sdf_mean = M.mean[0].type == GPIS_MEAN_PROCEDURAL || (M.has_mean_additional && M.mean[1].type == GPIS_MEAN_PROCEDURAL);
+        auto out_of_line = [](const gpis_mean &mu) { return mu.type == GPIS_MEAN_PROCEDURAL || mu.type == GPIS_MEAN_TABULATED; };
+        M.sdf_mean = out_of_line(M.mean[0]) || (M.has_mean_additional && out_of_line(M.mean[1]));
         const float angles[3] = {-90.f, 90.f, -45.f};
         for (int r = 0; r < 3; ++r) {
             const float angle = angles[r] * (3.1415926536f / 180.0f);      // Angle::degToRad
@@ -334,6 +335,13 @@ static int build_model(const gpis_params &P, DevModel &M, gpis_derived &D)
         }
         for (int w = 0; w < 2; ++w)
             for (int i = 0; i < 12; ++i) M.sdf_inv[w][i] = (i % 5 == 0) ? 1.f : 0.f;       // Mat4f(): the identity
+    }
+    {   // tabulated means (gpis_grid_mean.hpp): no grid yet (gpis_set_mean_grid); "volume" travels in gpis_mean.func
+        for (int w = 0; w < 2; ++w)
+            M.mean_volume[w] = M.mean[w].type == GPIS_MEAN_TABULATED && M.mean[w].func != 0;
+        // TabulatedMean::emission (GPF.cpp:174-177) is the grid's, 0 without an emission grid, and GaussianProcess::emission asks the
+        // primary mean (GaussianProcess.hpp:258-260): such a medium emits nothing whatever its "emission" field says
+        if (M.mean[0].type == GPIS_MEAN_TABULATED) M.emission.enabled = 0;
     }
 
     memcpy(D.world_to_local, w2l, sizeof w2l);
@@ -467,8 +475,8 @@ extern "C" int gpis_create(const gpis_params *params, int device, gpis_medium **
     if (params->correlation_context < 0 || params->correlation_context > 3) return set_err(GPIS_ERR_INVALID_ARG, "Invalid correlation context: '%d'", params->correlation_context);
     if (params->scheme_1d < 0 || params->scheme_1d > 2) return set_err(GPIS_ERR_INVALID_ARG, "Invalid sparse conv sampling scheme: '%d'", params->scheme_1d);
     if (!(params->impulse_density >= 0.f) || params->impulse_density > 4096.f) return set_err(GPIS_ERR_INVALID_ARG, "impulse_density out of range");
-    if (params->mean.type < 0 || params->mean.type > GPIS_MEAN_PROCEDURAL ||
-        (params->has_mean_additional && (params->mean_additional.type < 0 || params->mean_additional.type > GPIS_MEAN_PROCEDURAL)))
+    if (params->mean.type < 0 || params->mean.type > GPIS_MEAN_TABULATED ||
+        (params->has_mean_additional && (params->mean_additional.type < 0 || params->mean_additional.type > GPIS_MEAN_TABULATED)))
         return set_err(GPIS_ERR_INVALID_ARG, "invalid mean type");
     for (int w = 0; w < (params->has_mean_additional ? 2 : 1); ++w) {
         const gpis_mean &mu = w ? params->mean_additional : params->mean;
@@ -594,6 +602,8 @@ extern "C" int gpis_destroy(gpis_medium *m)
     if (m->fs_scene_recs) (void)hipFree(m->fs_scene_recs);
     if (m->fs_scene_next) (void)hipFree(m->fs_scene_next);
     if (m->d_grid_vox) (void)hipFree(m->d_grid_vox);
+    for (float *v : m->d_mean_vox)
+        if (v) (void)hipFree(v);
     for (int k = 0; k < 3; ++k)
         if (m->fs_stage[k]) (void)hipFree(m->fs_stage[k]);
     for (int k = 0; k < 3; ++k)
@@ -737,7 +747,7 @@ static int wave_march(gpis_medium *m, size_t n, const gpis_ray_in *rays, const u
 
 // ---- persistent march launch (per-path media) ---------------------------------------------------------------
 // the lattice sums of gpis_persist.inc have a diagonal kernel matrix: every medium except world-space 3D with a full anisoMtx
-// (a procedural mean is evaluated by the lane-per-ray all-features instance only: gpis_persist.inc states the analytic means inline)
+// (a procedural or tabulated mean is evaluated by the lane-per-ray all-features instance only: gpis_persist.inc states the analytic means inline)
 static bool persist_supported(const DevModel &H) { return !H.aniso.enabled && !H.fbm_noise && !H.sdf_mean && (H.sampling_1d || H.iso3d || !H.use_aniso_mtx); }
 // sideways (lane = impulse) evaluation pays while at most this many lanes of a wave have a job: lockstep costs
 // 27 n g instructions per round whatever the number of jobs, one sideways job ~20.6 cells x (c0 + c1 n)
@@ -782,7 +792,7 @@ int gpis::nee_instance(const DevModel &H) { return (H.sampling_1d && !H.fbm_nois
 // the lane-per-ray instance whose compile-time flags equal the medium's
 static int lane_instance(const DevModel &H)
 {
-    if (H.fbm_noise || H.sdf_mean) return launch::INST_GENERIC;           // sandstone / rust fields, procedural means: all-features instance only
+    if (H.fbm_noise || H.sdf_mean) return launch::INST_GENERIC;           // sandstone / rust fields, procedural / tabulated means: all-features instance only
     if (H.sampling_1d) return launch::INST_1D;
     if (!H.nonstationary && !H.multi_res && !H.multi_resolution_grid && H.kernel_type == GPIS_KERNEL_SQUARED_EXPONENTIAL) return launch::INST_3D;
     if (H.nonstationary && H.multi_res && H.multi_resolution_grid && !H.aniso.enabled) return launch::INST_3D_MULTIRES;
@@ -995,7 +1005,7 @@ int gpis::fs_check(gpis_medium *m)
 {
     const DevModel &H = m->host_model;
     if (H.sdf_mean)
-        return set_err(GPIS_ERR_UNSUPPORTED, "function-space path: a procedural (SDF) mean is outside its built scope");
+        return set_err(GPIS_ERR_UNSUPPORTED, "function-space path: a procedural (SDF) or tabulated (voxel grid) mean is outside its built scope");
     if (H.fs_n < 2 || H.fs_n > GPIS_FS_MAX_POINTS || !(H.fs_step >= 0) || H.kernel_type != GPIS_KERNEL_SQUARED_EXPONENTIAL || H.nonstationary ||
         H.use_aniso_mtx || H.has_mean_additional || (H.color.enabled && H.color.type >= GPIS_NOISE_SANDSTONE))
         return set_err(GPIS_ERR_INVALID_ARG, "function-space path: squared-exponential covariance, analytic mean (ramp colour), 2..64 sample points");
@@ -1396,7 +1406,7 @@ extern "C" int gpis_build_guide(gpis_medium *m, int half_extent_cells, int point
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     if (m->host_model.sdf_mean)
-        return set_err(GPIS_ERR_UNSUPPORTED, "gpis_build_guide: a procedural (SDF) mean has no guide field (no per-brick bound of such a mean is built)");
+        return set_err(GPIS_ERR_UNSUPPORTED, "gpis_build_guide: a procedural (SDF) or tabulated (voxel grid) mean has no guide field (no per-brick bound of such a mean is built)");
     if (!m->fast.enabled)
         return set_err(GPIS_ERR_UNSUPPORTED, "gpis_build_guide: the medium is not covered by the wave-cooperative path (single_realization, 3D, stationary SE, diagonal anisotropy)");
     int st = launch::guide_build(m->host_model, m->d_model, m->fast, half_extent_cells, points_per_cell, &m->guide, getenv("GPIS_GUIDE_DENSE") == nullptr);
@@ -1546,6 +1556,32 @@ extern "C" int gpis_set_variance_grid(gpis_medium *m, const gpis_variance_grid *
     for (int c = 0; c < 3; ++c) { G.dims[c] = g->dims[c]; G.origin[c] = g->origin[c]; G.lo[c] = g->bounds_min[c] + 2; G.hi[c] = g->bounds_max[c] - 3; }
     for (int i = 0; i < 12; ++i) G.T[i] = g->inv_natural_transform[i];
     HIP_TRY(hipMemcpy(m->d_model, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
+    return GPIS_OK;
+}
+
+// TabulatedMean's grid: the descriptor and the discipline of gpis_set_variance_grid, one device copy per slot
+extern "C" int gpis_set_mean_grid(gpis_medium *m, int which, const gpis_variance_grid *g, const float *voxels)
+{
+    CHECK_ARGS(std_handle(m) && g && voxels && (which == 0 || which == 1));
+    CHECK_ARGS(g->dims[0] >= 1 && g->dims[1] >= 1 && g->dims[2] >= 1 && (g->interpolate == 0 || g->interpolate == 1));
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (m->host_model.mean[which].type != GPIS_MEAN_TABULATED || (which == 1 && !m->host_model.has_mean_additional))
+        return set_err(GPIS_ERR_INVALID_ARG, "gpis_set_mean_grid: slot %d holds no tabulated mean", which);
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t n = (size_t)g->dims[0] * (size_t)g->dims[1] * (size_t)g->dims[2];
+    float *d = nullptr;
+    HIP_TRY(hipMalloc(&d, n * sizeof(float)));
+    if (hipMemcpy(d, voxels, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return set_err(GPIS_ERR_DEVICE, "gpis_set_mean_grid: copy failed"); }
+    float *old = m->d_mean_vox[which];
+    m->d_mean_vox[which] = d;
+    DevGrid &G = m->host_model.mean_grid[which];
+    G.vox = d;
+    G.interpolate = g->interpolate;
+    for (int c = 0; c < 3; ++c) { G.dims[c] = g->dims[c]; G.origin[c] = g->origin[c]; G.lo[c] = g->bounds_min[c] + 2; G.hi[c] = g->bounds_max[c] - 3; }
+    for (int i = 0; i < 12; ++i) G.T[i] = g->inv_natural_transform[i];
+    HIP_TRY(hipMemcpy(m->d_model, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
+    if (old) HIP_TRY(hipFree(old));          // behind the model refresh: the device model never names a freed array
     return GPIS_OK;
 }
 

@@ -6,7 +6,7 @@
 namespace gpis {
 namespace GPIS_PATH_NS {
 
-// ---- means: the analytic ones of gpis_device.hpp or, in the all-features instance, a procedural SDF mean (gpis_sdf.hpp) ----
+// ---- means: the analytic ones of gpis_device.hpp or, in the all-features instance, a procedural SDF or tabulated mean (gpis_sdf.hpp) ----
 GPIS_DEV void path_mean_weight_space(const DevModel &M, V3d p, double &mean, int &id)
 {
     if (GPIS_FLAG_sdf_mean(M)) {
@@ -23,7 +23,7 @@ GPIS_DEV V3d path_mean_grad(const DevModel &M, int id, V3d p)
         return sdf::mean_grad(&M, id, p.x, p.y, p.z);
     return mean_grad(M, id, p);
 }
-// conditioning_finish3d / 1d are shared with the persistent march (gpis_persist.inc), which does not serve procedural means: its
+// conditioning_finish3d / 1d are shared with the persistent march (gpis_persist.inc), which does not serve procedural / tabulated means: its
 // calls take the default SDF_MEAN = false and compile to the analytic means alone, as before
 template <bool SDF_MEAN> GPIS_DEV void cond_mean_weight_space(const DevModel &M, V3d p, double &mean, int &id)
 {

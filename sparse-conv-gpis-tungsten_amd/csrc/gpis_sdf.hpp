@@ -6,7 +6,8 @@
 // in DevModel; nothing here evaluates a sine or a cosine.
 //
 // Included by gpis_device.hpp in front of the path section.  Only the all-features path instance reaches it (GPIS_FLAG_sdf_mean);
-// the bodies are out of line so that instance's register budget does not carry them.
+// the bodies are out of line so that instance's register budget does not carry them.  The two out-of-line functions also serve
+// TabulatedMean (gpis_grid_mean.hpp): DevModel::sdf_mean says "a slot in use needs the out-of-line mean".
 #pragma once
 
 #pragma clang fp contract(off)
@@ -116,10 +117,12 @@ GPIS_DEV double procedural_mean(const DevModel &M, int w, V3d a)
 }
 GPIS_DEV double slot_mean(const DevModel &M, int w, V3d a)
 {
+    if (M.mean[w].type == GPIS_MEAN_TABULATED)
+        return tabulated_mean(M, w, a);
     return M.mean[w].type == GPIS_MEAN_PROCEDURAL ? procedural_mean(M, w, a) : mean_eval(M, w, a);
 }
 
-// GaussianProcess::mean_weight_space (GaussianProcess.cpp:379-393) of a medium with a procedural mean in either slot
+// GaussianProcess::mean_weight_space (GaussianProcess.cpp:379-393) of a medium with a procedural or tabulated mean in either slot
 struct MeanId { double mean; int id; };
 GPIS_SDF_FN MeanId mean_weight_space(const DevModel *Mp, double ax, double ay, double az)
 {
@@ -133,11 +136,14 @@ GPIS_SDF_FN MeanId mean_weight_space(const DevModel *Mp, double ax, double ay, d
     }
     return MeanId{m, i};
 }
-// dmean_da of slot w: ProceduralMean's one-sided difference (GPF.cpp:287-296; the order a, +x, +y, +z) or the analytic gradient
+// dmean_da of slot w: ProceduralMean's one-sided difference (GPF.cpp:287-296; the order a, +x, +y, +z), TabulatedMean's
+// (GPF.cpp:179-190: a double eps, the order +x, +y, +z, a) or the analytic gradient
 GPIS_SDF_FN V3d mean_grad(const DevModel *Mp, int w, double ax, double ay, double az)
 {
     const DevModel &M = *Mp;
     const V3d a{ax, ay, az};
+    if (M.mean[w].type == GPIS_MEAN_TABULATED)
+        return tabulated_mean_grad(M, w, a);
     if (M.mean[w].type != GPIS_MEAN_PROCEDURAL) {
         return gpis::mean_grad(M, w, a);
     }

@@ -44,6 +44,7 @@ int ws_validate(const gpis_params &P, const gpis_ws_params &S)
         return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: a sandstone / rust mean colour is outside the built scope (ramp colours only)");
     for (int w = 0; w < 1 + (P.has_mean_additional ? 1 : 0); ++w) {
         const int t = w ? P.mean_additional.type : P.mean.type;
+        if (t == GPIS_MEAN_TABULATED) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: a tabulated (voxel grid) mean is outside the built scope of the weight-space medium");
         if (t == GPIS_MEAN_PROCEDURAL) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: a procedural (SDF) mean is outside the built scope of the weight-space medium");
         if (t < GPIS_MEAN_HOMOGENEOUS || t > GPIS_MEAN_LINEAR) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: mean type %d", t);
     }
