@@ -12,10 +12,18 @@ functions).  So, in the device's own float arithmetic (csrc/gpis_path.inc: evalu
 SdfComposite runs intersectGP (SparseConvolutionNoiseMedium.cpp:102-183) and the scattering branch of sampleDistance /
 transmittance (GaussianProcessMedium.cpp:221-393) over batches of rays on top of those three, and fills every field of gpis_seg_out.
 It offers sample_distance, transmittance, scene_s_primary, mean_color_emission and params, so it can stand in for the oracle in
-tests/paths_rgb_ref.py's PathsRgbRef.compose.
+tests/paths_rgb_ref.py's PathsRgbRef.compose, and nee_pdf / nee_grad, so it can in tests/nee_paths_ref.py's NeePathsRef.compose.
 
-Scope: media whose noise amplitude is a constant (stationary kernels; the multi-resolution wrapper is served for the three evaluator
-formulas only), sigma_s != 0, surf_vol_phase_separate off."""
+NEE.  neeShared (SCN.cpp:601-743) is not linear in the mean's gradient, so the noise-only decomposition does not carry over.  It reads
+the mean's GRADIENT only, narrowed to float, and the oracle's LinearMean with dir = +-e_k has exactly the gradient +-scale * e_k (the
+other components are positive zeros).  So for a query whose reference gradient, at double(float(p)) and from the slot the CSG id
+selects, has at most one non-zero component in float, nee_pdf / nee_grad are the ORACLE's own on this medium with the mean replaced by
+that linear one (the homogeneous mean 0 for a zero gradient): nothing of ours is restated.  A query with a general gradient (knob_inner,
+two_spheres, most of the knob) has no such stand-in: nee_pdf / nee_grad raise on it, and callers select their queries first.
+
+Scope of the march: media whose noise amplitude is a constant (stationary kernels, the Matern ones included; the multi-resolution
+wrapper is served for the three evaluator formulas only), 3D or 1D sampling (the evaluation count n_evals is the 3D evaluators'),
+one mean or a CSG pair, sigma_s != 0, surf_vol_phase_separate off.  Scope of NEE: axis-aligned mean gradients, as said above."""
 import numpy as np
 
 import sdf_mean_ref
@@ -70,6 +78,33 @@ def queries(pkg, n, seed, scale=0.9):
     return q
 
 
+def nee_queries(pkg, points, grad, seed):
+    """one NEE query per point: a random unit ray_dir, the normal = normalised (mean gradient + a random vector of length <= 0.8)
+    (random normals alone leave pdf > 0 on a fifth of the queries), path identities, and on every second query a conditioning record
+    anchored at the segment's start"""
+    rng = np.random.default_rng(seed)
+    n = len(points)
+    q = np.zeros(n, dtype=pkg.NEE_QUERY)
+    q["p"] = points
+    d = rng.normal(size=(n, 3))
+    q["ray_dir"] = (d / np.linalg.norm(d, axis=1)[:, None]).astype(f32)
+    v = rng.normal(size=(n, 3))
+    v = v / np.linalg.norm(v, axis=1)[:, None] * rng.uniform(0, 0.8, (n, 1))
+    nrm = np.asarray(grad, dtype=np.float64) + v
+    q["normal"] = (nrm / np.linalg.norm(nrm, axis=1)[:, None]).astype(f32)
+    q["t_segment"] = rng.uniform(0, 1.5, n)
+    q["info_t"] = rng.uniform(0, 3, n)
+    q["pixel"] = rng.integers(0, 512, (n, 2))
+    q["spp"] = rng.integers(0, 64, n)
+    q["segment"] = rng.integers(0, 4, n)
+    q["scene_seed"] = rng.integers(0, 2 ** 31, n)
+    cond = (np.arange(n) % 2 == 1)[:, None]
+    q["coeff"]["value_scale"] = np.where(cond[:, 0], rng.normal(0, 0.05, n), 0)
+    q["coeff"]["gradient_scale"] = np.where(cond, rng.normal(0, 0.5, (n, 3)), 0)
+    q["coeff"]["ray_origin"] = np.where(cond, q["p"] - q["ray_dir"] * q["t_segment"][:, None], 0)
+    return q
+
+
 def camera_rays(pkg, n, seed, bound=1.5, first_scatter=True, state=None):
     """n camera-like rays through the ball of radius `bound`: from a pinhole at (0.3, 0.4, 4) towards points of the ball, clipped
     to it (near_t / far_t); continued segments start from `state` = (last_val, last_aniso, last_gp_id) arrays"""
@@ -109,6 +144,7 @@ class SdfComposite:
         self.pkg, self.ob = pkg, ob
         self.params = np.array(pkg.as_params(params))
         self.transforms = transforms
+        self.threads = threads
         self.noise = ob.Oracle(noise_only(pkg, params), threads=threads)
         self.mref = sdf_mean_ref.SdfMeanRef()
         self.derived = self.noise.derived()
@@ -149,6 +185,58 @@ class SdfComposite:
         col, _ = orc.mean_color_emission(pc)
         _, emi = orc.mean_color_emission(p)
         return col, emi
+
+    # ---- NEE: the oracle itself through a linear stand-in ------------------------------------------------------------
+    def nee_standin(self, q):
+        """(k, s) per NEE query: the mean's gradient at double(float(p)), from the slot the CSG id selects, narrowed to float, is
+        s * e_k (k = -1, s = 0: the zero gradient).  Raises on a query whose gradient has more than one non-zero component."""
+        p = np.asarray(q["p"], dtype=f32).astype(np.float64).reshape(-1, 3)
+        g = self.mean(p)[2].astype(f32)
+        nz = g != 0
+        if (nz.sum(axis=1) > 1).any():
+            bad = np.nonzero(nz.sum(axis=1) > 1)[0]
+            raise ValueError("NEE reference: the mean gradient of %d queries is not axis-aligned (first: %d, %r)" % (len(bad), bad[0], g[bad[0]]))
+        k = np.where(nz.any(axis=1), nz.argmax(axis=1), -1)
+        s = np.where(k >= 0, g[np.arange(len(g)), np.maximum(k, 0)], f32(0)).astype(f32)
+        return k, s
+
+    def _nee_oracle(self, k, s):
+        """the oracle of this medium with the mean replaced by the one whose gradient is exactly s * e_k in float: LinearMean with
+        dir = sign(s) * e_k, scale = |s|, min = -FLT_MAX, centre 0, no CSG partner (the zeros of its gradient are positive, as the
+        one-sided difference's are); the homogeneous mean 0 for the zero gradient.  nee_shared reads the mean's gradient alone."""
+        if k < 0:
+            return self.noise
+        cache = self.__dict__.setdefault("_nee_oracles", {})
+        key = (int(k), np.array(s, dtype=f32).view(np.uint32).item())
+        if key not in cache:
+            p = noise_only(self.pkg, self.params)
+            mu = p["mean"]
+            mu["type"] = self.pkg.MEAN_TYPE.LINEAR
+            mu["center"] = 0.0
+            d = np.zeros(3)
+            d[k] = -1.0 if s < 0 else 1.0
+            mu["dir"] = d
+            mu["scale"] = abs(f32(s))
+            mu["min"] = -np.finfo(f32).max
+            cache[key] = self.ob.Oracle(p, threads=self.threads)
+        return cache[key]
+
+    def _nee(self, q, what):
+        q = np.ascontiguousarray(q, dtype=self.pkg.NEE_QUERY)
+        k, s = self.nee_standin(q)
+        out = np.zeros(len(q), dtype=f32) if what == "pdf" else np.zeros((len(q), 3), dtype=f32)
+        keys = np.stack([k.astype(np.int64), s.view(np.uint32).astype(np.int64)], axis=1)
+        for kk, sb in np.unique(keys, axis=0):
+            idx = np.nonzero((keys[:, 0] == kk) & (keys[:, 1] == sb))[0]
+            orc = self._nee_oracle(int(kk), np.array(sb, dtype=np.uint32).view(f32))
+            out[idx] = orc.nee_pdf(q[idx]) if what == "pdf" else orc.nee_grad(q[idx])
+        return out
+
+    def nee_pdf(self, q):
+        return self._nee(q, "pdf")
+
+    def nee_grad(self, q):
+        return self._nee(q, "grad")
 
     # ---- the march ------------------------------------------------------------------------------------------------
     def _query(self, rays, idx, t, coeff):
@@ -279,10 +367,13 @@ class SdfComposite:
         for k in range(3):
             d = d + aniso[:, k] * dirs[:, k]
             l2 = l2 + aniso[:, k] * aniso[:, k]
-        wrong = hit & (d > 0)
-        zero = hit & ~wrong & (l2 < np.float64(f32(0.0000001)))
-        bad = wrong | zero
-        aniso[zero] = (1.0, 0.0, 0.0)
+        # a hit whose gradient is not finite (a refinement that fell back to t = 0 on a continued segment of a Matern medium: the
+        # conditioning kernel's derivative at distance 0 is 0 / 0) fails the segment before the two sign tests (GPM.cpp:291)
+        nonfinite = hit & ~np.isfinite((aniso[:, 0] + aniso[:, 1] + aniso[:, 2]) / 3.0)
+        wrong = hit & ~nonfinite & (d > 0)
+        zero = hit & ~nonfinite & ~wrong & (l2 < np.float64(f32(0.0000001)))
+        bad = wrong | zero | nonfinite
+        aniso[zero | nonfinite] = (1.0, 0.0, 0.0)
         out["t"] = t
         out["exited"] = ~hit
         out["aniso"] = aniso
@@ -320,12 +411,7 @@ class SdfComposite:
         hit, t, trips, gp, exit_val, coeff, nev = self._intersect(rays, first, rays["last_val"], rays["last_aniso"])
         vis = ~hit
         self.last_n_eval = int(nev.sum() + hit.sum())         # a hit evaluates the gradient, an exit does not
-        h = np.nonzero(hit)[0]          # t < maxT: the gradient is evaluated and must be finite
-        if len(h):
-            g, _ = self._gradient(rays, h, t[h], coeff)
-            avg = (g[:, 0] + g[:, 1] + g[:, 2]) / 3.0
-            assert np.isfinite(avg).all()
-        return vis.astype(np.uint8)
+        return vis.astype(np.uint8)     # t < maxT: the gradient is evaluated; finite or not, the segment is blocked
 
     def scene_s_primary(self, scene, x, y, spp):
         return self.noise.scene_s_primary(scene, x, y, spp)

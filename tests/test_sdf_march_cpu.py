@@ -130,3 +130,51 @@ def test_plane_mean_is_the_linear_mean(pkg, ob, case):
         # an ulp of 1.5 (1.2e-7) over eps = 1.2e-4, narrowed to float once more
         assert np.allclose(got["aniso"][agree], want["aniso"][agree], rtol=1e-6, atol=2e-4)
         assert np.array_equal(comp.transmittance(rays), case["orc"].transmittance(rays))
+
+
+# ---- (c) a CSG pair and a non-finite gradient, on analytic media ---------------------------------------------------------------------
+@pytest.mark.parametrize("name", ("none", "renewal+"))
+def test_composite_on_an_analytic_csg_pair_is_the_oracle(pkg, ob, name):
+    """LinearMean (y, scale 1) united with a sphere of radius 0.5 about (0.7, 0.3, 0): the composite takes value, gradient and the
+    conditioning's reduction from the slot the CSG minimum chose and carries gp_id into the continued segments, as the oracle does.
+    Both ids occur among the hits and among the continued segments' last_gp_id."""
+    import mean_features_ref as mfr
+    p = linear(pkg, base(pkg, name))
+    p["has_mean_additional"] = 1
+    p["mean_additional"]["type"] = pkg.MEAN_TYPE.SPHERICAL
+    p["mean_additional"]["radius"] = 0.5
+    p["mean_additional"]["center"] = (0.7, 0.3, 0.0)
+    orc = ob.Oracle(p, threads=8)
+    comp = smr.SdfComposite(pkg, ob, p, threads=8)
+    rays = smr.camera_rays(pkg, N, 5)
+    first = orc.sample_distance(rays)
+    for r in (rays, mfr.continued(pkg, first, 6)):
+        want, wcoeff = orc.sample_distance(r, want_coeff=True)
+        hit = want["exited"] == 0
+        ids = [int((hit & (want["gp_id"] == i)).sum()) for i in (0, 1)]
+        last = [int((r["last_gp_id"] == i).sum()) for i in (0, 1)]
+        print(name, "hits per gp_id", ids, "last_gp_id", last)
+        assert min(ids) >= 16 and (r["first_scatter"].all() or min(last) >= 16)
+        got, coeff = comp.sample_distance(r, want_coeff=True)
+        _same(got, want, pkg.SEG_OUT.names)
+        _same(coeff, wcoeff, ("value_scale", "gradient_scale", "ray_origin", "n_evals"))
+        assert np.array_equal(comp.transmittance(r), orc.transmittance(r))
+
+
+def test_composite_with_a_non_finite_gradient_is_the_oracle(pkg, ob):
+    """Matern 5/2, Renewal: a continued segment whose refinement falls back to t = 0 evaluates the gradient at the conditioning point,
+    where the kernel's derivative is 0 / 0; sampleDistance fails such a segment with aniso = (1, 0, 0) (GPM.cpp:291) and transmittance
+    blocks it.  The spherical mean is the oracle's own, so the composite's handling of that class is pinned here."""
+    import mean_features_ref as mfr
+    p = mfr.config(pkg, "matern")
+    orc = ob.Oracle(p, threads=8)
+    comp = smr.SdfComposite(pkg, ob, p, threads=8)
+    first = orc.sample_distance(smr.camera_rays(pkg, N, 5))
+    r = mfr.continued(pkg, first, 22)
+    want, wcoeff = orc.sample_distance(r, want_coeff=True)
+    failed = (want["ok"] == 0) & (want["exited"] == 0) & (want["t"] == 0) & (want["aniso"] == (1.0, 0.0, 0.0)).all(axis=1)
+    assert failed.sum() == 4
+    got, coeff = comp.sample_distance(r, want_coeff=True)
+    _same(got, want, pkg.SEG_OUT.names)
+    _same(coeff, wcoeff, ("value_scale", "gradient_scale", "ray_origin", "n_evals"))
+    assert np.array_equal(comp.transmittance(r), orc.transmittance(r))
