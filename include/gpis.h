@@ -624,6 +624,43 @@ int gpis_set_variance_grid(gpis_medium *m, const gpis_variance_grid *g, const fl
  * for null or non-positive dims and for interpolate outside {0, 1} ("quadratic" is refused, as for the variance grid). */
 int gpis_set_mean_grid(gpis_medium *m, int which, const gpis_variance_grid *g, const float *voxels);
 
+/* A neural SDF mean (NeuralMean over GPNeuralNetwork's mean network, GPF.cpp:197-248, GPNeuralNetwork.hpp): an fp64 MLP
+ * v = W0 p + b0 (no activation), v = sin(Wk v + bk) per hidden layer, (Wout v + bout)(0), evaluated at
+ * q = mult(transform^-1, p) clamped to the bounds when it lies outside them; mean = (nn(q) + offset) * scale.  The library
+ * evaluates it with the reference's arithmetic bit for bit (Eigen's three summation orders, the host's sin) and hands it to the
+ * march as the voxels of a tabulated mean (gpis_bake_mean_network): the march itself never evaluates the network.
+ * dims[k] = (in, out) of layer k: dims[0].in = 3, dims[k].in = dims[k-1].out, the last out = 1, every width <= 256, n_layers in
+ * 2 .. 16; anything else is GPIS_ERR_INVALID_ARG with a message.  The weights are one array of doubles in the order of the
+ * reference's file: per layer out x in column-major, then out biases. */
+#define GPIS_NN_MAX_LAYERS 16
+#define GPIS_NN_MAX_WIDTH 256
+typedef struct gpis_mean_network {
+    int32_t n_layers;
+    int32_t _pad;
+    int32_t dims[GPIS_NN_MAX_LAYERS][2];
+    double bounds_min[3], bounds_max[3];   /* GPNeuralNetwork::_bounds */
+    float offset, scale;
+    float transform[16];                   /* row-major Mat4f; inverted as gpis_set_mean_transform inverts one */
+} gpis_mean_network;
+
+/* NeuralMean::mean (value) and dmean_da (grad3: eps = 0.001 in double, mean at +x, +y, +z and a, each difference / eps) at n
+ * double-precision points.  Either output may be null.  No medium handle: the _host form takes host pointers and runs on the
+ * current device; the _batch form takes device pointers for the weights, the points and the outputs and allocates its
+ * activation workspace (networks wider than 64 only) for the call.  `weights` holds the sum over the layers of out * (in + 1)
+ * doubles. */
+int gpis_network_mean_host(const gpis_mean_network *net, const double *weights, size_t n, const double *p3, double *value, double *grad3);
+int gpis_network_mean_batch(const gpis_mean_network *net, const double *weights, size_t n, const double *p3, double *value, double *grad3,
+                            void *stream);
+
+/* Evaluates the network on the lattice of `g` and installs the result as the voxel grid of the tabulated mean in slot `which`,
+ * exactly as gpis_set_mean_grid installs one (same lock, same model refresh, an earlier grid of the slot replaced).  Voxel
+ * (i, j, k) gets float(mean(x)) with x_r = double(A[4r]) (origin_i + i) + double(A[4r+1]) (origin_j + j) +
+ * double(A[4r+2]) (origin_k + k) + double(A[4r+3]), A = index_to_world (rows 0..2 of a row-major Mat4f), summed left to right,
+ * unfused.  `weights` is a host pointer.  The voxels stay on the device unless voxels_out (host pointer, dims[0] * dims[1] *
+ * dims[2] floats) is given.  GPIS_ERR_INVALID_ARG as gpis_set_mean_grid and for an invalid network. */
+int gpis_bake_mean_network(gpis_medium *m, int which, const gpis_mean_network *net, const double *weights, const gpis_variance_grid *g,
+                           const float index_to_world[12], float *voxels_out);
+
 /* Allocates the workspace gpis_render_scene_s needs for `s` ahead of the first frame: 71 B per sample of the largest chunk the
  * device holds with the compact records (the resident march, GPIS_OPT_SCENE_COMPACT: 9.5 GB for a whole 1920x1080x64 frame),
  * 236 B per sample (31.3 GB) otherwise.  The call is meant to run beside gpis_build_guide, so it does not look at whether a guide

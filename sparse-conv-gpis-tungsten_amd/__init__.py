@@ -11,6 +11,7 @@ from .bindings import (  # noqa: F401
     PARAMS, MEAN, RAMP, VARIANCE_GRID, variance_grid_desc, FS_STATE, FS_MAX_POINTS, FS_MAX_CTX, RAY_IN, SEG_OUT, COND_COEFF, QUERY, NEE_QUERY, DERIVED, SCENE_S, SURFACE_S, default_surface_s, default_scene_s,
     default_params, params_for_config, as_params, CTX, SCHEME, MEAN_TYPE, SDF_FUNCTION,
     ADAPTIVE_S, ADAPTIVE_RECORD, ADAPTIVE_INFO, default_adaptive_s,
+    MEAN_NETWORK, NN_MAX_LAYERS, NN_MAX_WIDTH, Network, load_network, network_mean, index_to_world,
     WeightSpaceMedium, WS_PARAMS, WS_QUERY, WS_MAX_BASIS, NORMAL, INTERSECT, default_ws_params,
 )
 from . import dist  # noqa: F401

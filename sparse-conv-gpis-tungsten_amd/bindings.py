@@ -83,6 +83,85 @@ def variance_grid_desc(voxels, world_to_index, interpolate="linear", origin=(0, 
     d["inv_natural_transform"] = np.asarray(world_to_index, dtype=np.float32).reshape(16)
     return d, v
 
+def index_to_world(world_to_index):
+    """rows 0..2 of the inverse of a world -> index transform (row-major 4x4): inverted in float64, rounded to float32 — the
+    lattice of Medium.bake_mean_network"""
+    inv = np.linalg.inv(np.asarray(world_to_index, dtype=np.float32).reshape(4, 4).astype(np.float64))
+    return np.ascontiguousarray(inv[:3].astype(np.float32).reshape(12))
+
+
+NN_MAX_LAYERS, NN_MAX_WIDTH = 16, 256
+MEAN_NETWORK = np.dtype([
+    ("n_layers", "<i4"), ("_pad", "<i4"), ("dims", "<i4", (NN_MAX_LAYERS, 2)),
+    ("bounds_min", "<f8", 3), ("bounds_max", "<f8", 3), ("offset", "<f4"), ("scale", "<f4"), ("transform", "<f4", 16),
+], align=True)
+
+
+class Network:
+    """The mean network of the reference's GPNeuralNetwork descriptor: layers [(in, out), ...], the bounds box and the weights as
+    the file holds them (one float64 array: per layer out x in column-major, then out biases)."""
+
+    def __init__(self, layers, bounds_min, bounds_max, weights):
+        self.layers = [(int(a), int(b)) for a, b in layers]
+        self.bounds_min = np.array(bounds_min, dtype=np.float64).reshape(3)
+        self.bounds_max = np.array(bounds_max, dtype=np.float64).reshape(3)
+        self.weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        need = self.n_weights(self.layers)
+        if self.weights.size != need:
+            raise ValueError("the layers %s need %d doubles, got %d" % (self.layers, need, self.weights.size))
+
+    @staticmethod
+    def n_weights(layers):
+        return sum(int(o) * (int(i) + 1) for i, o in layers)
+
+    def layer(self, k):
+        """(W, b) of layer k: W[out, in] (read from the column-major block) and b[out]"""
+        off = self.n_weights(self.layers[:k])
+        i, o = self.layers[k]
+        return self.weights[off:off + i * o].reshape(i, o).T, self.weights[off + i * o:off + i * o + o]
+
+    def desc(self, offset=0.0, scale=1.0, transform=None):
+        """gpis_mean_network; the layer rules are the library's to check, so nothing is refused here but a count past the record"""
+        if len(self.layers) > NN_MAX_LAYERS:
+            raise ValueError("%d layers: gpis_mean_network holds at most %d" % (len(self.layers), NN_MAX_LAYERS))
+        d = np.zeros((), dtype=MEAN_NETWORK)
+        d["n_layers"] = len(self.layers)
+        for k, (i, o) in enumerate(self.layers):
+            d["dims"][k] = (i, o)
+        d["bounds_min"], d["bounds_max"] = self.bounds_min, self.bounds_max
+        d["offset"], d["scale"] = offset, scale
+        d["transform"] = np.asarray(np.eye(4) if transform is None else transform, dtype=np.float32).reshape(16)
+        return d
+
+
+def load_network(path):
+    """Reads the reference's network descriptor {"bounds": {"min", "max"}, "mean": {"file", "layers": [[in, out], ...]}}; the file
+    path is relative to the descriptor.  The "cov" part (NeuralNonstationaryCovariance's network) is ignored and its file need not
+    exist.  Raises on a weight file shorter than the layers need."""
+    import json
+    with open(path) as f:
+        doc = json.load(f)
+    layers = [(int(a), int(b)) for a, b in doc["mean"]["layers"]]
+    need = Network.n_weights(layers)
+    wpath = os.path.join(os.path.dirname(os.path.abspath(path)), doc["mean"]["file"])
+    w = np.fromfile(wpath, dtype="<f8", count=need)
+    if w.size < need:
+        raise ValueError("%s holds %d doubles; the layers %s need %d" % (wpath, w.size, layers, need))
+    return Network(layers, doc["bounds"]["min"], doc["bounds"]["max"], w)
+
+
+def network_mean(net, points, offset=0.0, scale=1.0, transform=None, want_grad=True, lib=None):
+    """NeuralMean::mean and dmean_da of `net` at double-precision points (n, 3), evaluated on the device in the reference's
+    arithmetic: (value, grad), or the value alone with want_grad=False"""
+    L = lib or load_library()
+    d = net.desc(offset, scale, transform)
+    p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    val = np.zeros(p.shape[0], dtype=np.float64)
+    grad = np.zeros((p.shape[0], 3), dtype=np.float64) if want_grad else None
+    L.check(L.lib.gpis_network_mean_host(_ptr(d), _ptr(net.weights), p.shape[0], _ptr(p), _ptr(val), _ptr(grad)), "gpis_network_mean_host")
+    return (val, grad) if want_grad else val
+
+
 FS_MAX_POINTS, FS_MAX_CTX = 64, 66
 FS_STATE = np.dtype([
     ("sampler_state", "<u8"), ("has_context", "<i4"), ("is_intersect", "<i4"), ("n_points", "<i4"), ("n_values", "<i4"),
@@ -216,6 +295,7 @@ _EXPECTED_SIZES = {
     "gpis_fs_state": FS_STATE.itemsize, "gpis_guide_info": GUIDE_INFO.itemsize,
     "gpis_ws_params": WS_PARAMS.itemsize, "gpis_ws_query": WS_QUERY.itemsize,
     "gpis_adaptive_s": ADAPTIVE_S.itemsize, "gpis_adaptive_record": ADAPTIVE_RECORD.itemsize, "gpis_adaptive_info": ADAPTIVE_INFO.itemsize,
+    "gpis_mean_network": MEAN_NETWORK.itemsize,
 }
 assert RAY_IN.itemsize == 128 and SEG_OUT.itemsize == 96 and COND_COEFF.itemsize == 32
 assert QUERY.itemsize == 96 and NEE_QUERY.itemsize == 96
@@ -364,6 +444,7 @@ class GpisLib:
         "gpis_fs_render_scene_s", "gpis_fs_render_scene_s_paths",
         "gpis_default_adaptive_s", "gpis_render_scene_s_adaptive", "gpis_adaptive_plan_host", "gpis_adaptive_rng_init_host", "gpis_adaptive_record_add_host",
         "gpis_render_scene_s_paths_rgb_adaptive", "gpis_adaptive_rgb_value_host",
+        "gpis_network_mean_host", "gpis_network_mean_batch", "gpis_bake_mean_network",
     ]
 
     def __init__(self, path=None):
@@ -408,6 +489,9 @@ class GpisLib:
         L.gpis_mean_host.argtypes = [vp, sz, vp, vp, vp, vp]
         L.gpis_set_mean_transform.argtypes = [vp, i32, vp]
         L.gpis_set_mean_grid.argtypes = [vp, i32, vp, vp]
+        L.gpis_network_mean_host.argtypes = [vp, vp, sz, vp, vp, vp]
+        L.gpis_network_mean_batch.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+        L.gpis_bake_mean_network.argtypes = [vp, i32, vp, vp, vp, vp, vp]
         L.gpis_xxhash32_batch.argtypes = [vp, sz, i32, vp, vp, vp]
         L.gpis_pcg32_stream_batch.argtypes = [vp, sz, vp, u32, vp, vp]
         L.gpis_sample_distance_host.argtypes = [vp, sz, vp, vp, vp]
@@ -786,6 +870,25 @@ class Medium:
         """the voxel grid of a tabulated mean (which = 0: mean, 1: mean_additional); arguments as variance_grid_desc / set_variance_grid"""
         d, v = variance_grid_desc(voxels, world_to_index, interpolate, origin)
         self.L.check(self.L.lib.gpis_set_mean_grid(self.h, int(which), d.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p)), "gpis_set_mean_grid")
+
+    def bake_mean_network(self, which, net, dims, world_to_index, interpolate="linear", origin=(0, 0, 0), offset=0.0, scale=1.0,
+                          transform=None, return_voxels=False):
+        """Evaluates the network `net` (load_network) exactly on the dims = (nx, ny, nz) voxels whose voxel (0, 0, 0) sits at the
+        index-space coordinate `origin`, and installs them as the grid of the tabulated mean in slot `which` (0: mean,
+        1: mean_additional), as set_mean_grid would.  offset / scale / transform are NeuralMean's, applied before the voxel is
+        narrowed to float; the slot's own offset and scale (gpis_params) apply to the lookup afterwards.  The lattice points are
+        index_to_world . (origin + (i, j, k), 1) with index_to_world derived from world_to_index ONCE: its inverse in float64,
+        rounded to float32.  return_voxels: the baked array voxels[k, j, i], as set_mean_grid takes it."""
+        nx, ny, nz = (int(v) for v in dims)
+        d, _ = variance_grid_desc(np.zeros((1, 1, 1), dtype=np.float32), world_to_index, interpolate, origin)
+        d["dims"] = (nx, ny, nz)
+        d["bounds_max"] = (origin[0] + nx - 1, origin[1] + ny - 1, origin[2] + nz - 1)
+        i2w = index_to_world(world_to_index)
+        nd = net.desc(offset, scale, transform)
+        out = np.zeros((nz, ny, nx), dtype=np.float32) if return_voxels else None
+        self.L.check(self.L.lib.gpis_bake_mean_network(self.h, int(which), _ptr(nd), _ptr(net.weights), _ptr(d), _ptr(i2w), _ptr(out)),
+                     "gpis_bake_mean_network")
+        return out
 
     def eval_value(self, q):
         q = np.ascontiguousarray(q, dtype=QUERY)

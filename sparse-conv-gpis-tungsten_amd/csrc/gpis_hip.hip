@@ -24,6 +24,7 @@
 #include "gpis_host.hpp"      // gpis_medium, HIP_TRY, CHECK_ARGS, ProfScope; gpis_tables.hpp (FastTable, fast_supported, fast_table_free,
                               // GuideField, kBrickFloats, guide_free) — none of the fast or guided device code is seen here
 #include "gpis_launch.hpp"    // the march kernels live in the tu_*.hip translation units
+#include "gpis_nn_mean.hpp"   // the exact evaluator of a neural SDF mean: k_mean over a network (this unit only)
 
 #pragma clang fp contract(off)
 
@@ -434,10 +435,10 @@ extern "C" const char *gpis_abi_sizes(void)
     snprintf(buf, sizeof buf,
              "gpis_params=%zu,gpis_mean=%zu,gpis_ray_in=%zu,gpis_seg_out=%zu,gpis_cond_coeff=%zu,gpis_query=%zu,"
              "gpis_nee_query=%zu,gpis_derived=%zu,gpis_scene_s=%zu,gpis_surface_s=%zu,gpis_ramp=%zu,gpis_fs_state=%zu,gpis_guide_info=%zu,"
-             "gpis_ws_params=%zu,gpis_ws_query=%zu,gpis_adaptive_s=%zu,gpis_adaptive_record=%zu,gpis_adaptive_info=%zu",
+             "gpis_ws_params=%zu,gpis_ws_query=%zu,gpis_adaptive_s=%zu,gpis_adaptive_record=%zu,gpis_adaptive_info=%zu,gpis_mean_network=%zu",
              sizeof(gpis_params), sizeof(gpis_mean), sizeof(gpis_ray_in), sizeof(gpis_seg_out), sizeof(gpis_cond_coeff),
              sizeof(gpis_query), sizeof(gpis_nee_query), sizeof(gpis_derived), sizeof(gpis_scene_s), sizeof(gpis_surface_s), sizeof(gpis_ramp), sizeof(gpis_fs_state), sizeof(gpis_guide_info),
-             sizeof(gpis_ws_params), sizeof(gpis_ws_query), sizeof(gpis_adaptive_s), sizeof(gpis_adaptive_record), sizeof(gpis_adaptive_info));
+             sizeof(gpis_ws_params), sizeof(gpis_ws_query), sizeof(gpis_adaptive_s), sizeof(gpis_adaptive_record), sizeof(gpis_adaptive_info), sizeof(gpis_mean_network));
     return buf;
 }
 
@@ -1559,6 +1560,21 @@ extern "C" int gpis_set_variance_grid(gpis_medium *m, const gpis_variance_grid *
     return GPIS_OK;
 }
 
+// the slot's device array `d` becomes its grid: descriptor into the host model, model refresh, the earlier array freed behind it.
+// The caller holds the handle's lock and has waited for the device.
+static int install_mean_grid(gpis_medium *m, int which, const gpis_variance_grid *g, float *d)
+{
+    float *old = m->d_mean_vox[which];
+    m->d_mean_vox[which] = d;
+    DevGrid &G = m->host_model.mean_grid[which];
+    G.vox = d;
+    G.interpolate = g->interpolate;
+    for (int c = 0; c < 3; ++c) { G.dims[c] = g->dims[c]; G.origin[c] = g->origin[c]; G.lo[c] = g->bounds_min[c] + 2; G.hi[c] = g->bounds_max[c] - 3; }
+    for (int i = 0; i < 12; ++i) G.T[i] = g->inv_natural_transform[i];
+    HIP_TRY(hipMemcpy(m->d_model, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
+    if (old) HIP_TRY(hipFree(old));          // behind the model refresh: the device model never names a freed array
+    return GPIS_OK;
+}
 // TabulatedMean's grid: the descriptor and the discipline of gpis_set_variance_grid, one device copy per slot
 extern "C" int gpis_set_mean_grid(gpis_medium *m, int which, const gpis_variance_grid *g, const float *voxels)
 {
@@ -1573,16 +1589,7 @@ extern "C" int gpis_set_mean_grid(gpis_medium *m, int which, const gpis_variance
     float *d = nullptr;
     HIP_TRY(hipMalloc(&d, n * sizeof(float)));
     if (hipMemcpy(d, voxels, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return set_err(GPIS_ERR_DEVICE, "gpis_set_mean_grid: copy failed"); }
-    float *old = m->d_mean_vox[which];
-    m->d_mean_vox[which] = d;
-    DevGrid &G = m->host_model.mean_grid[which];
-    G.vox = d;
-    G.interpolate = g->interpolate;
-    for (int c = 0; c < 3; ++c) { G.dims[c] = g->dims[c]; G.origin[c] = g->origin[c]; G.lo[c] = g->bounds_min[c] + 2; G.hi[c] = g->bounds_max[c] - 3; }
-    for (int i = 0; i < 12; ++i) G.T[i] = g->inv_natural_transform[i];
-    HIP_TRY(hipMemcpy(m->d_model, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
-    if (old) HIP_TRY(hipFree(old));          // behind the model refresh: the device model never names a freed array
-    return GPIS_OK;
+    return install_mean_grid(m, which, g, d);
 }
 
 // Mat4f::invert (Mat4f.hpp:75-101): the adjugate over the determinant, in float.  inv[4 i + j] is the cofactor of (row j, column i):
@@ -1633,4 +1640,149 @@ extern "C" int gpis_set_mean_transform(gpis_medium *m, int which, const float tr
     memcpy(m->host_model.sdf_inv[which], inv, 12 * sizeof(float));
     HIP_TRY(hipMemcpy(m->d_model, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
     return GPIS_OK;
+}
+
+// ======================================================================================
+// neural SDF means (gpis_nn_mean.hpp): the exact evaluator at points and on a lattice, and the bake into a tabulated slot
+// ======================================================================================
+constexpr size_t kNnChunkPoints = (size_t)1 << 18;          // points of one launch
+constexpr size_t kNnWorkspaceBytes = (size_t)64 << 20;      // activation workspace of one launch (networks wider than 64)
+
+static int nn_describe(const char *who, const gpis_mean_network *net, nn::Net &N, size_t &n_weights)
+{
+    if (net->n_layers < 2 || net->n_layers > GPIS_NN_MAX_LAYERS)
+        return set_err(GPIS_ERR_INVALID_ARG, "%s: n_layers = %d, outside 2 .. %d", who, net->n_layers, GPIS_NN_MAX_LAYERS);
+    memset(&N, 0, sizeof N);
+    N.n_layers = net->n_layers;
+    N.max_width = 3;
+    size_t off = 0;
+    for (int k = 0; k < net->n_layers; ++k) {
+        const int in = net->dims[k][0], out = net->dims[k][1];
+        if (in < 1 || out < 1 || in > GPIS_NN_MAX_WIDTH || out > GPIS_NN_MAX_WIDTH)
+            return set_err(GPIS_ERR_INVALID_ARG, "%s: layer %d is %d -> %d; a width is 1 .. %d", who, k, in, out, GPIS_NN_MAX_WIDTH);
+        if (k == 0 && in != 3) return set_err(GPIS_ERR_INVALID_ARG, "%s: the first layer takes %d inputs, not the 3 of a point", who, in);
+        if (k > 0 && in != net->dims[k - 1][1])
+            return set_err(GPIS_ERR_INVALID_ARG, "%s: layer %d takes %d inputs but layer %d gives %d", who, k, in, k - 1, net->dims[k - 1][1]);
+        if (k == net->n_layers - 1 && out != 1)
+            return set_err(GPIS_ERR_INVALID_ARG, "%s: the last layer gives %d outputs; only 1 is built (more rows sum in another order)", who, out);
+        N.dims[k][0] = in;
+        N.dims[k][1] = out;
+        N.w_off[k] = (uint32_t)off;
+        off += (size_t)out * (size_t)(in + 1);
+        if (out > N.max_width) N.max_width = out;
+    }
+    n_weights = off;
+    for (int c = 0; c < 3; ++c) { N.bmin[c] = net->bounds_min[c]; N.bmax[c] = net->bounds_max[c]; }
+    N.offset = net->offset;
+    N.scale = net->scale;
+    float inv[16];
+    mat4_invert_ref(net->transform, inv);
+    memcpy(N.inv, inv, sizeof N.inv);
+    return GPIS_OK;
+}
+// points of one launch, and the bytes of its workspace: two buffers of max_width doubles per lane of the launch
+static size_t nn_chunk(const nn::Net &N, size_t &ws_bytes)
+{
+    const size_t per_lane = 2 * (size_t)N.max_width * sizeof(double);
+    if (N.max_width <= 64) { ws_bytes = 0; return kNnChunkPoints; }
+    size_t c = kNnWorkspaceBytes / per_lane;
+    c -= c % nn::kLanes;
+    if (c > kNnChunkPoints) c = kNnChunkPoints;
+    ws_bytes = c * per_lane;
+    return c;
+}
+// a device allocation that a failing entry leaves behind freed
+struct NnDev {
+    void *p = nullptr;
+    ~NnDev() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+    void *release() { void *q = p; p = nullptr; return q; }
+};
+// lat == nullptr: value / grad3 at the n points p3; otherwise voxels [0, n) of the lattice
+static int nn_launch(const nn::Net &N, const double *W, size_t n, const double *p3, double *value, double *grad3, const nn::Lattice *lat, float *voxels,
+                     double *ws, hipStream_t s)
+{
+    size_t ws_bytes;
+    const size_t chunk = nn_chunk(N, ws_bytes);
+    for (size_t a = 0; a < n; a += chunk) {
+        const size_t c = n - a < chunk ? n - a : chunk;
+        const unsigned blocks = (unsigned)grid_of(c, nn::kLanes);
+        if (lat) {
+            if (N.max_width <= 32) k_mean<32><<<blocks, nn::kLanes, 0, s>>>(N, W, *lat, a, c, voxels, nullptr);
+            else if (N.max_width <= 64) k_mean<64><<<blocks, nn::kLanes, 0, s>>>(N, W, *lat, a, c, voxels, nullptr);
+            else k_mean<0><<<blocks, nn::kLanes, 0, s>>>(N, W, *lat, a, c, voxels, ws);
+        } else {
+            double *v = value ? value + a : nullptr, *g = grad3 ? grad3 + 3 * a : nullptr;
+            if (N.max_width <= 32) k_mean<32><<<blocks, nn::kLanes, 0, s>>>(N, W, c, p3 + 3 * a, v, g, nullptr);
+            else if (N.max_width <= 64) k_mean<64><<<blocks, nn::kLanes, 0, s>>>(N, W, c, p3 + 3 * a, v, g, nullptr);
+            else k_mean<0><<<blocks, nn::kLanes, 0, s>>>(N, W, c, p3 + 3 * a, v, g, ws);
+        }
+        if (int st = launch_check("k_mean (network)")) return st;
+    }
+    return GPIS_OK;
+}
+extern "C" int gpis_network_mean_batch(const gpis_mean_network *net, const double *weights, size_t n, const double *p3, double *value, double *grad3,
+                                       void *stream)
+{
+    CHECK_ARGS(net && weights && (n == 0 || p3));
+    nn::Net N;
+    size_t n_weights;
+    if (int st = nn_describe(__func__, net, N, n_weights)) return st;
+    if (n == 0 || (!value && !grad3)) return GPIS_OK;
+    size_t ws_bytes;
+    (void)nn_chunk(N, ws_bytes);
+    NnDev ws;
+    if (ws_bytes) HIP_TRY(ws.alloc(ws_bytes));
+    if (int st = nn_launch(N, weights, n, p3, value, grad3, nullptr, nullptr, (double *)ws.p, (hipStream_t)stream)) return st;
+    if (ws_bytes) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));        // the workspace is this call's: its kernels end before it goes
+    return GPIS_OK;
+}
+extern "C" int gpis_network_mean_host(const gpis_mean_network *net, const double *weights, size_t n, const double *p3, double *value, double *grad3)
+{
+    CHECK_ARGS(net && weights && (n == 0 || p3));
+    nn::Net N;
+    size_t n_weights;
+    if (int st = nn_describe(__func__, net, N, n_weights)) return st;
+    if (n == 0 || (!value && !grad3)) return GPIS_OK;
+    NnDev dW, dP, dV, dG;
+    HIP_TRY(dW.alloc(n_weights * sizeof(double)));
+    HIP_TRY(dP.alloc(3 * n * sizeof(double)));
+    if (value) HIP_TRY(dV.alloc(n * sizeof(double)));
+    if (grad3) HIP_TRY(dG.alloc(3 * n * sizeof(double)));
+    HIP_TRY(hipMemcpy(dW.p, weights, n_weights * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dP.p, p3, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+    if (int st = gpis_network_mean_batch(net, (const double *)dW.p, n, (const double *)dP.p, (double *)dV.p, (double *)dG.p, nullptr)) return st;
+    HIP_TRY(hipDeviceSynchronize());
+    if (value) HIP_TRY(hipMemcpy(value, dV.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (grad3) HIP_TRY(hipMemcpy(grad3, dG.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+    return GPIS_OK;
+}
+extern "C" int gpis_bake_mean_network(gpis_medium *m, int which, const gpis_mean_network *net, const double *weights, const gpis_variance_grid *g,
+                                      const float index_to_world[12], float *voxels_out)
+{
+    CHECK_ARGS(std_handle(m) && net && weights && g && index_to_world && (which == 0 || which == 1));
+    CHECK_ARGS(g->dims[0] >= 1 && g->dims[1] >= 1 && g->dims[2] >= 1 && (g->interpolate == 0 || g->interpolate == 1));
+    nn::Net N;
+    size_t n_weights;
+    if (int st = nn_describe(__func__, net, N, n_weights)) return st;
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (m->host_model.mean[which].type != GPIS_MEAN_TABULATED || (which == 1 && !m->host_model.has_mean_additional))
+        return set_err(GPIS_ERR_INVALID_ARG, "gpis_bake_mean_network: slot %d holds no tabulated mean", which);
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t n = (size_t)g->dims[0] * (size_t)g->dims[1] * (size_t)g->dims[2];
+    nn::Lattice lat;
+    for (int c = 0; c < 3; ++c) { lat.dims[c] = g->dims[c]; lat.origin[c] = g->origin[c]; }
+    memcpy(lat.A, index_to_world, sizeof lat.A);
+    size_t ws_bytes;
+    (void)nn_chunk(N, ws_bytes);
+    NnDev dW, ws, vox;
+    HIP_TRY(dW.alloc(n_weights * sizeof(double)));
+    if (ws_bytes) HIP_TRY(ws.alloc(ws_bytes));
+    HIP_TRY(vox.alloc(n * sizeof(float)));
+    HIP_TRY(hipMemcpy(dW.p, weights, n_weights * sizeof(double), hipMemcpyHostToDevice));
+    if (int st = nn_launch(N, (const double *)dW.p, n, nullptr, nullptr, nullptr, &lat, (float *)vox.p, (double *)ws.p, nullptr)) return st;
+    HIP_TRY(hipDeviceSynchronize());
+    if (voxels_out) HIP_TRY(hipMemcpy(voxels_out, vox.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    return install_mean_grid(m, which, g, (float *)vox.release());
 }
