@@ -549,6 +549,10 @@ typedef enum gpis_option {
     GPIS_OPT_SCENE_COMPACT = 10,     // gpis_render_scene_s on the resident guided march without exit state: 1 (default) = its kernels pass
                                      //   32-byte ray / hit records (71 B of workspace per sample); 0 = the 128 / 96-byte records of the batch
                                      //   ABI (236 B per sample).  The same evaluations either way; environment: GPIS_SCENE_COMPACT
+    GPIS_OPT_SHADOW_LEAN = 11,       // transmittance on the resident guided march: 1 (default) = the march ends at the first step whose sign
+                                     //   differs (exact or certified), keeps signs only and skips the start value of a continued segment;
+                                     //   0 = it refines the crossing as sampleDistance does.  The same visibility either way, fewer
+                                     //   evaluations with 1; environment: GPIS_SHADOW_LEAN
     GPIS_OPT_COUNT_
 } gpis_option;
 typedef enum gpis_march_form { GPIS_MARCH_FORM_AUTO = 0, GPIS_MARCH_FORM_RESIDENT = 1, GPIS_MARCH_FORM_WAVE = 2 } gpis_march_form;

@@ -66,6 +66,12 @@ GPIS_DEV uint64_t guide_rec_make(uint32_t slot, uint32_t err16, uint32_t amax16)
 // 4 waves 315 / 122, 5 waves 325 / 117
 #define GPIS_GUIDE_OCC_TR 5
 #endif
+#ifndef GPIS_GUIDE_OCC_TR_LEAN
+// the lean transmittance instances (guided_march: LEAN) carry no crossing state.  Whole C1 frames: 4 waves 558.5 Msamples/s
+// (128 VGPRs, 104-116 B of scratch), 5 waves 551.5 (96, 240-248 B), 6 waves 555.9 (80, 320-356 B); 5 is the setting at which
+// they take no more VGPRs and less scratch than their siblings (tests/test_gpu_shadow_lean.py)
+#define GPIS_GUIDE_OCC_TR_LEAN 5
+#endif
 #ifndef GPIS_SOLO_MAX
 #define GPIS_SOLO_MAX 3
 #endif
@@ -469,6 +475,7 @@ GPIS_DEV float mean_approx(const DevModel &M, V3 p, float perr, float &slack)
 //             value is only known by sign — at the previous position (X_PREV), before the reference's
 //             secant-and-shrink refinement (X_REFINE) runs on exact values only
 //   X_FINAL   exact lastVal at farT (sampleDistance only), G_GRAD exact gradient, G_DONE
+// The lean transmittance instances (LEAN, below) stop at the crossing step: G_INIT, G_MARCH, X_F0, X_CUR only.
 // Exact evaluations are cooperative (coop_evaluate_value); parked lanes are served in clusters whose
 // grid cells span at most 2 per axis, so the evaluator always takes its coherent path.
 constexpr int32_t kSegPending = 0x7FFFFFF0;     // gpis_seg_out::ok of a record that waits for its gradient (k_guided_range_grad)
@@ -622,11 +629,19 @@ GPIS_DEV int guide_sign_at(const DevModel &M, const GuideField &F, const GuideRa
 // call of the policy the same load cost k_guided_sample_distance_nograd<false> six spills less: its code is to stay as it was);
 // SceneRecords the 32-byte records of the Lambert frame driver, whose uniform origin / direction comes in `rec`.  Nothing between the
 // load and the store depends on the policy.
-template <bool WANT_SAMPLE, bool SMALLARG, bool DEFER_GRAD = false, bool EXIT_STATE = true, class REC = BatchRecords>
+// LEAN (transmittance only; GPIS_OPT_SHADOW_LEAN): the march evaluates only what visibility depends on.  transmittance returns by
+// `exited` alone (GPM.cpp:392) and both ways out of the refinement loop return true (SCNM.cpp:147-169), so the segment ends at the
+// first step whose sign differs from sign0 — an exact one (X_CUR) or a certified one, whose sign the certificate guarantees as it
+// does at every step the march skips.  Neither the previous value (X_PREV) nor the refinement (X_REFINE) runs, and a continued
+// segment (!first_scatter), whose first march step overwrites sign0 (SCNM.cpp:138-140) and pf (:172), does not look at f(nearT)
+// at all: nothing else reads it.  Only signs are kept: every statement that names pf, fc, pf_valid, t_prevpos, a_lo, intp, t_test
+// or t_prev is discarded from this instance (if constexpr), and its phases are G_INIT, G_MARCH, X_F0 (first_scatter only), X_CUR.
+template <bool WANT_SAMPLE, bool SMALLARG, bool DEFER_GRAD = false, bool EXIT_STATE = true, class REC = BatchRecords, bool LEAN = false>
 GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideField &F, FastLds &lds, bool valid,
                            const typename REC::Ray *__restrict__ rayp, typename REC::Out *out, bool &visible, uint32_t &n_eval, uint32_t &n_guide,
                            const REC &rec = REC())
 {
+    static_assert(!LEAN || !WANT_SAMPLE, "the lean march answers visibility only");
     V3 pos = v3(0.f, 0.f, 1.f), dir = v3(0.f, 0.f, 1.f);
     float nearT = 0.f, farT = 1.f, u_jitter = 0.f;
     bool first_scatter = true;
@@ -675,6 +690,7 @@ GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideFie
         early_ok = true;
     }
     double t = (double)nearT;          // position of the march step being decided
+    // the crossing state (unused in the LEAN instance)
     double t_prevpos = (double)nearT;  // position the previous value `pf` belongs to
     double a_lo = 0., intp = 0., t_test = 0., t_prev = 0.;
     float pf = 0.f, fc = 0.f;
@@ -686,44 +702,50 @@ GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideFie
     auto world_at = [&](double tq) { return to_f(ray_at(to_d(pos), to_d(dir), tq)); };
     // after the evaluation at nearT: t = nearT + step*u (float arithmetic, SCNM.cpp:129)
     auto begin_march = [&]() {
-        t_prevpos = (double)nearT;
+        if constexpr (!LEAN)
+            t_prevpos = (double)nearT;
         t = (double)(nearT + step_size * u_jitter);
         phase = (t < (double)farT) ? G_MARCH : X_FINAL;
     };
     auto advance = [&]() {
-        t_prevpos = t;
+        if constexpr (!LEAN)
+            t_prevpos = t;
         t += (double)step_size;
         phase = (t < (double)farT) ? G_MARCH : X_FINAL;
     };
     auto begin_refine = [&]() {   // SCNM.cpp:143-146
-        intp = (double)pf / ((double)pf - (double)fc);
-        a_lo = t - (double)step_size;
-        t_prev = lerp_d(a_lo, t, intp);
-        t_test = t_prev;
-        phase = X_REFINE;
+        if constexpr (!LEAN) {
+            intp = (double)pf / ((double)pf - (double)fc);
+            a_lo = t - (double)step_size;
+            t_prev = lerp_d(a_lo, t, intp);
+            t_test = t_prev;
+            phase = X_REFINE;
+        }
     };
     // one trip of the shrink loop (SCNM.cpp:147-160).  It consumes only the SIGN of f(t_test), but asking
     // the guide first does not pay: t_test lies inside the crossing step, i.e. inside the uncertainty band
     // (measured on C1: 4 033 of 86.9 M trips certified)
     auto refine_step = [&](int sign_test) {
-        bool done = false;
-        if (sign_test == sign0) {
-            done = true;
-        } else {
-            intp *= 0.9;
-            if (intp <= 0.01) {
-                t_prev = t_test = 0;
+        if constexpr (!LEAN) {
+            bool done = false;
+            if (sign_test == sign0) {
                 done = true;
             } else {
-                t_prev = t_test;
-                t_test = lerp_d(a_lo, t, intp);
+                intp *= 0.9;
+                if (intp <= 0.01) {
+                    t_prev = t_test = 0;
+                    done = true;
+                } else {
+                    t_prev = t_test;
+                    t_test = lerp_d(a_lo, t, intp);
+                }
             }
-        }
-        if (done) {
-            t = t_prev;
-            hit = true;
-            last_val = 0.0f;
-            phase = WANT_SAMPLE ? G_GRAD : G_DONE;
+            if (done) {
+                t = t_prev;
+                hit = true;
+                last_val = 0.0f;
+                phase = WANT_SAMPLE ? G_GRAD : G_DONE;
+            }
         }
     };
 
@@ -751,12 +773,16 @@ GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideFie
             FSTAT(20, 1);
             FSTAT(21, __popcll(step_mask));
             if (stepping) {
-                if (phase == G_INIT) {
+                if (LEAN && phase == G_INIT && !first_scatter) {
+                    n_guide++;              // stands for the reference's f0, which the adopting step overwrites unread
+                    begin_march();
+                } else if (phase == G_INIT) {
                     const int s = guide_sign_at(M, F, gr, (double)nearT);
                     if (s != 0) {
                         n_guide++;          // counts certified steps: each stands for one evaluateValue of the reference
                         sign0 = s;
-                        pf_valid = false;
+                        if constexpr (!LEAN)
+                            pf_valid = false;
                         begin_march();
                     } else {
                         phase = X_F0;
@@ -768,10 +794,16 @@ GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideFie
                         n_guide++;
                         step++;
                         if (adopt) sign0 = s;
-                        pf_valid = false;
+                        if constexpr (!LEAN)
+                            pf_valid = false;
                         advance();
+                    } else if (LEAN && s != 0) {
+                        n_guide++;          // a certified sign change: the crossing step itself, and all that visibility asks
+                        step++;
+                        hit = true;
+                        phase = G_DONE;
                     } else {
-                        phase = X_CUR;      // uncertain, or a certified sign change: exact values needed
+                        phase = X_CUR;      // uncertain, or (!LEAN) a certified sign change: exact values needed
                     }
                 }
             }
@@ -783,7 +815,8 @@ GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideFie
         const unsigned long long need_mask = __ballot(need);
         if (need_mask == 0ULL)
             break;
-        const double tq = phase == X_F0 ? (double)nearT : (phase == X_PREV ? t_prevpos : (phase == X_REFINE ? t_test : (phase == X_FINAL ? (double)farT : t)));
+        const double tq = LEAN ? (phase == X_F0 ? (double)nearT : t)
+                               : (phase == X_F0 ? (double)nearT : (phase == X_PREV ? t_prevpos : (phase == X_REFINE ? t_test : (phase == X_FINAL ? (double)farT : t))));
         const V3 pq = world_at(tq);
         const Frame coord = ray_frame();
         const V3 ug = grid_point(M, F, pq, coord);
@@ -819,7 +852,27 @@ GPIS_DEV void guided_march(const DevModel &M, const FastTable &T, const GuideFie
             FSTAT(26 + ph - X_F0, served);
         }
 #endif
-        if (in_cluster) {
+        if constexpr (LEAN) {
+            // X_F0 (first_scatter) and X_CUR are the phases a lane can wait in: X_FINAL was retired at the top of loop A
+            if (in_cluster) {
+                const int signc = fv < 0 ? -1 : 1;
+                if (phase == X_F0) {                       // SCNM.cpp:125-126
+                    sign0 = signc;
+                    begin_march();
+                } else {                                   // X_CUR: SCNM.cpp:133-141
+                    step++;
+                    if (!first_scatter && step == 1) {
+                        sign0 = signc;
+                        advance();
+                    } else if (signc != sign0) {
+                        hit = true;                        // the crossing step: wherever the refinement would end, it returns true
+                        phase = G_DONE;
+                    } else {
+                        advance();
+                    }
+                }
+            }
+        } else if (in_cluster) {
             gp = gp_new;
             const double f = (double)fv;
             if (phase == X_F0) {                       // SCNM.cpp:125-128
@@ -1049,6 +1102,49 @@ __global__ void __launch_bounds__(kFastBlock, GPIS_GUIDE_OCC_TR) k_guided_transm
     bool vis = false;
     const SceneRecords<true> rec{v3(lx, ly, lz)};
     guided_march<false, SMALLARG, false, true, SceneRecords<true>>(*Mp, T, *Fp, lds, valid, rays + (valid ? i : 0), nullptr, vis, n_eval, n_guide, rec);
+    if (i < n)
+        visible[i] = (valid && vis) ? 1 : 0;
+    fast_flush_counters(cnt, n_eval, valid ? 1u : 0u);
+    unsigned long long gsum = n_guide;
+    for (int off = 32; off > 0; off >>= 1) gsum += __shfl_down(gsum, off, 64);
+    if ((threadIdx.x & 63) == 0 && gsum) atomicAdd(guide_cnt, gsum);
+}
+
+// ---- the lean forms of k_guided_transmittance and k_guided_transmittance_scene (guided_march: LEAN; GPIS_OPT_SHADOW_LEAN, default):
+// the same launches and arguments, the same visibility; fewer exact evaluations and no crossing state.  Their names share no prefix
+// with the kernels they stand in for, which the resource tests find by the start of their mangled names.
+template <bool SMALLARG>
+__global__ void __launch_bounds__(kFastBlock, GPIS_GUIDE_OCC_TR_LEAN) k_shadow_lean(const DevModel *__restrict__ Mp, FastTable T, const GuideField *__restrict__ Fp, size_t n,
+                                                                               const gpis_ray_in *__restrict__ rays, uint8_t *__restrict__ visible,
+                                                                               const uint8_t *__restrict__ mask, Counters *cnt, unsigned long long *guide_cnt)
+{
+    __shared__ FastLds lds;
+    fast_lds_init(lds);
+    size_t i = (size_t)blockIdx.x * kFastBlock + threadIdx.x;
+    const bool valid = i < n && (!mask || mask[i]);
+    uint32_t n_eval = 0, n_guide = 0;
+    bool vis = false;
+    guided_march<false, SMALLARG, false, true, BatchRecords, true>(*Mp, T, *Fp, lds, valid, rays + (valid ? i : 0), nullptr, vis, n_eval, n_guide);
+    if (i < n)
+        visible[i] = (valid && vis) ? 1 : 0;
+    fast_flush_counters(cnt, n_eval, valid ? 1u : 0u);
+    unsigned long long gsum = n_guide;
+    for (int off = 32; off > 0; off >>= 1) gsum += __shfl_down(gsum, off, 64);
+    if ((threadIdx.x & 63) == 0 && gsum) atomicAdd(guide_cnt, gsum);
+}
+template <bool SMALLARG>
+__global__ void __launch_bounds__(kFastBlock, GPIS_GUIDE_OCC_TR_LEAN) k_shadow_lean_scene(const DevModel *__restrict__ Mp, FastTable T, const GuideField *__restrict__ Fp, size_t n,
+                                                                                     const SceneRay *__restrict__ rays, float lx, float ly, float lz,
+                                                                                     uint8_t *__restrict__ visible, Counters *cnt, unsigned long long *guide_cnt)
+{
+    __shared__ FastLds lds;
+    fast_lds_init(lds);
+    size_t i = (size_t)blockIdx.x * kFastBlock + threadIdx.x;
+    const bool valid = i < n && (rays[i].flags & kSceneRayLive) != 0u;
+    uint32_t n_eval = 0, n_guide = 0;
+    bool vis = false;
+    const SceneRecords<true> rec{v3(lx, ly, lz)};
+    guided_march<false, SMALLARG, false, true, SceneRecords<true>, true>(*Mp, T, *Fp, lds, valid, rays + (valid ? i : 0), nullptr, vis, n_eval, n_guide, rec);
     if (i < n)
         visible[i] = (valid && vis) ? 1 : 0;
     fast_flush_counters(cnt, n_eval, valid ? 1u : 0u);

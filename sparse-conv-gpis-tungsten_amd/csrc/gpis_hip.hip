@@ -549,6 +549,8 @@ extern "C" int gpis_create(const gpis_params *params, int device, gpis_medium **
         if (const char *e = getenv("GPIS_SCENE_EXIT_STATE")) m->opt[GPIS_OPT_SCENE_EXIT_STATE] = e[0] != '0';
         m->opt[GPIS_OPT_SCENE_COMPACT] = 1;
         if (const char *e = getenv("GPIS_SCENE_COMPACT")) m->opt[GPIS_OPT_SCENE_COMPACT] = e[0] != '0';
+        m->opt[GPIS_OPT_SHADOW_LEAN] = 1;
+        if (const char *e = getenv("GPIS_SHADOW_LEAN")) m->opt[GPIS_OPT_SHADOW_LEAN] = e[0] != '0';
         m->opt[GPIS_OPT_CHUNK_LOG2] = 0;
         if (const char *e = getenv("GPIS_CHUNK_LOG2")) { int l = atoi(e); m->opt[GPIS_OPT_CHUNK_LOG2] = l < 16 ? 16 : (l > 28 ? 28 : l); }
     }
@@ -857,8 +859,8 @@ int gpis::transmittance_impl(gpis_medium *m, size_t n, const gpis_ray_in *rays, 
         return launch_check("k_guided_range_tr");
     }
     if (m->guide.enabled) {
-        launch::guided_transmittance(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->d_guide, n, rays, visible, mask, m->d_counters + 1, m->d_guide_cnt, s);
-        return launch_check("k_guided_transmittance");
+        launch::guided_transmittance(m->host_model.exp_arg_max < 100.f, m->opt[GPIS_OPT_SHADOW_LEAN] != 0, m->d_model, m->fast, m->d_guide, n, rays, visible, mask, m->d_counters + 1, m->d_guide_cnt, s);
+        return launch_check(m->opt[GPIS_OPT_SHADOW_LEAN] ? "k_shadow_lean" : "k_guided_transmittance");
     }
     if (m->fast.enabled) {
         launch::fast_transmittance(m->d_model, m->fast, n, rays, visible, mask, m->d_counters + 1, s);
@@ -896,8 +898,8 @@ int gpis::scene_transmittance_compact(gpis_medium *m, size_t n, const SceneRay *
 {
     if (n == 0) return GPIS_OK;
     ProfScope prof(m, 1, s);
-    launch::guided_transmittance_scene(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->d_guide, n, rays, light, visible, m->d_counters + 1, m->d_guide_cnt, s);
-    return launch_check("k_guided_transmittance_scene");
+    launch::guided_transmittance_scene(m->host_model.exp_arg_max < 100.f, m->opt[GPIS_OPT_SHADOW_LEAN] != 0, m->d_model, m->fast, m->d_guide, n, rays, light, visible, m->d_counters + 1, m->d_guide_cnt, s);
+    return launch_check(m->opt[GPIS_OPT_SHADOW_LEAN] ? "k_shadow_lean_scene" : "k_guided_transmittance_scene");
 }
 
 extern "C" int gpis_sample_distance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, gpis_cond_coeff *coeff, void *stream)
@@ -927,7 +929,7 @@ extern "C" int gpis_set_option(gpis_medium *m, int option, long long value)
     switch (option) {
     case GPIS_OPT_MARCH_FORM: CHECK_ARGS(value >= GPIS_MARCH_FORM_AUTO && value <= GPIS_MARCH_FORM_WAVE); break;
     case GPIS_OPT_WAVE_TAIL: CHECK_ARGS(value >= 0); break;
-    case GPIS_OPT_PATHS_SORT: case GPIS_OPT_PATHS_PRESORT: case GPIS_OPT_PERSISTENT: case GPIS_OPT_DEFER_GRAD: case GPIS_OPT_SCENE_EXIT_STATE: case GPIS_OPT_SCENE_COMPACT: CHECK_ARGS(value == 0 || value == 1); break;
+    case GPIS_OPT_PATHS_SORT: case GPIS_OPT_PATHS_PRESORT: case GPIS_OPT_PERSISTENT: case GPIS_OPT_DEFER_GRAD: case GPIS_OPT_SCENE_EXIT_STATE: case GPIS_OPT_SCENE_COMPACT: case GPIS_OPT_SHADOW_LEAN: CHECK_ARGS(value == 0 || value == 1); break;
     case GPIS_OPT_CHUNK_LOG2: CHECK_ARGS(value == 0 || (value >= 16 && value <= 28)); break;
     case GPIS_OPT_SOLO_MAX: CHECK_ARGS(value >= -1 && value <= 64); break;
     case GPIS_OPT_RANGE_LEN: CHECK_ARGS(value >= 0 && value <= (1 << 24) && value % 64 == 0); break;
@@ -1531,6 +1533,15 @@ extern "C" int gpis_debug_fast_stats(uint64_t *out32)
 {
     unsigned long long h[32];
     int st = launch::fast_stats_read(h);
+    if (st != GPIS_OK) return st;
+    for (int i = 0; i < 32; ++i) out32[i] = h[i];
+    return GPIS_OK;
+}
+// ... and of the guided transmittance kernels' TU
+extern "C" int gpis_debug_fast_stats_tr(uint64_t *out32)
+{
+    unsigned long long h[32];
+    int st = launch::fast_stats_read_tr(h);
     if (st != GPIS_OK) return st;
     for (int i = 0; i < 32; ++i) out32[i] = h[i];
     return GPIS_OK;

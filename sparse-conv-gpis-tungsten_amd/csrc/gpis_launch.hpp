@@ -50,6 +50,7 @@ void fast_sample_distance(const DevModel *d_model, const FastTable &T, size_t n,
 void fast_transmittance(const DevModel *d_model, const FastTable &T, size_t n, const gpis_ray_in *rays, uint8_t *visible, const uint8_t *mask,
                         Counters *cnt, hipStream_t s);
 int fast_stats_read(unsigned long long *out32);                 // GPIS_FAST_STATS builds only; GPIS_ERR_UNSUPPORTED otherwise
+int fast_stats_read_tr(unsigned long long *out32);              // the same for the guided transmittance kernels (tu_guided_tr.hip has its own copy)
 // ---- certified guide field (tu_guide_build.hip: build + checks; tu_guided_sd.hip / tu_guided_tr.hip: the resident guided march) -----
 int guide_build(const DevModel &M, const DevModel *d_model, const FastTable &T, int half, int ppc, GuideField *F, bool sparse);
 void guide_selfcheck(const DevModel *d_model, const FastTable &T, const GuideField &F, size_t n, const float *points3, unsigned long long *stats,
@@ -64,13 +65,14 @@ void guided_sample_distance_noexit(bool small_arg, const DevModel *d_model, cons
                                    gpis_seg_out *out, gpis_cond_coeff *coeff, const uint8_t *mask, Counters *cnt, unsigned long long *guide_cnt, hipStream_t s);   // exit records without state
 void range_grad(bool small_arg, const DevModel *d_model, const FastTable &T, const GuideField &F, size_t n, const gpis_ray_in *rays, gpis_seg_out *out,
                 gpis_cond_coeff *coeff, const uint8_t *mask, Counters *cnt, hipStream_t s);      // completes the records a *_nograd / range march left pending
-void guided_transmittance(bool small_arg, const DevModel *d_model, const FastTable &T, const GuideField *d_guide, size_t n, const gpis_ray_in *rays,
+// lean: the instances that evaluate only what visibility depends on (gpis_guide.hpp: guided_march LEAN; GPIS_OPT_SHADOW_LEAN)
+void guided_transmittance(bool small_arg, bool lean, const DevModel *d_model, const FastTable &T, const GuideField *d_guide, size_t n, const gpis_ray_in *rays,
                           uint8_t *visible, const uint8_t *mask, Counters *cnt, unsigned long long *guide_cnt, hipStream_t s);
 // the same two marches as k_guided_sample_distance_noexit / k_guided_transmittance on the compact records of the Lambert frame driver
 // (gpis_scene.hpp): flag bit 0 of a ray is its mask; `origin` (camera) / `light` (direction) is the vector all rays of the launch share
 void guided_sample_distance_scene(bool small_arg, const DevModel *d_model, const FastTable &T, const GuideField *d_guide, size_t n, const SceneRay *rays,
                                   SceneHit *out, const float origin[3], Counters *cnt, unsigned long long *guide_cnt, hipStream_t s);
-void guided_transmittance_scene(bool small_arg, const DevModel *d_model, const FastTable &T, const GuideField *d_guide, size_t n, const SceneRay *rays,
+void guided_transmittance_scene(bool small_arg, bool lean, const DevModel *d_model, const FastTable &T, const GuideField *d_guide, size_t n, const SceneRay *rays,
                                 const float light[3], uint8_t *visible, Counters *cnt, unsigned long long *guide_cnt, hipStream_t s);
 // ---- guided march with in-wave refill from a range of the batch (tu_range.hip; off by default) ------------------
 void range_sample_distance(bool small_arg, const DevModel *d_model, const FastTable &T, const GuideField &F, size_t n, const gpis_ray_in *rays,

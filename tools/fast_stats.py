@@ -30,25 +30,37 @@ if paths_bounces:
 else:
     med.call("gpis_render_scene_s", scene.ctypes.data_as(ctypes.c_void_p), rad.data_ptr(), None, None)
 torch.cuda.synchronize()
+def report(out, label):
+    names = ["wave_evals", "active_lanes", "cells_visited", "cells_mine", "cells_cand", "candidates", "union_pass", "lane_pass", "incoherent",
+             "lanes_1_2", "lanes_3_4", "lanes_5_8", "lanes_9_16", "lanes_17_32", "lanes_33_64"]
+    st = dict(zip(names, list(out)))
+    e = max(st["wave_evals"], 1)
+    print("----", label)
+    print(st)
+    print("per wave-eval: active lanes %.1f, cells visited %.1f, processed %.1f, with candidates %.1f, candidates %.1f, bodies %.1f, "
+          "lane-passes/body %.1f, incoherent %.4f" % (st["active_lanes"] / e, st["cells_visited"] / e, st["cells_mine"] / e, st["cells_cand"] / e,
+                                                     st["candidates"] / e, st["union_pass"] / e, st["lane_pass"] / max(st["union_pass"], 1), st["incoherent"] / e))
+    g = list(out)[16:26]
+    if g[2]:
+        tot = g[2] + g[3]
+        print("guided kernels (wave cycles): guide loop %.1f%%, exact values %.1f%%, gradient tail %.1f%%; "
+              "guide-loop iterations %d (%.1f lanes stepping), exact rounds %d (%.1f lanes parked), of which sideways %d (%.1f lanes)" % (
+              100.0 * g[0] / tot, 100.0 * g[1] / tot, 100.0 * g[3] / tot, g[4], g[5] / max(g[4], 1), g[6], g[7] / max(g[6], 1), g[8], g[9] / max(g[8], 1)))
+    ph = list(out)[26:31]
+    if sum(ph):
+        print("exact value requests served, by phase: " + ", ".join("%s %d" % (n, v) for n, v in zip(("X_F0", "X_CUR", "X_PREV", "X_REFINE", "X_FINAL"), ph)))
+    return e
+
+
+# the diagnostic counters are one copy per translation unit: the sampleDistance kernels' and the transmittance kernels'
 out = (ctypes.c_uint64 * 32)()
 lib.lib.gpis_debug_fast_stats(out)
-names = ["wave_evals", "active_lanes", "cells_visited", "cells_mine", "cells_cand", "candidates", "union_pass", "lane_pass", "incoherent",
-         "lanes_1_2", "lanes_3_4", "lanes_5_8", "lanes_9_16", "lanes_17_32", "lanes_33_64"]
-st = dict(zip(names, list(out)))
-e = max(st["wave_evals"], 1)
-print(st)
-print("per wave-eval: active lanes %.1f, cells visited %.1f, processed %.1f, with candidates %.1f, candidates %.1f, bodies %.1f, "
-      "lane-passes/body %.1f, incoherent %.4f" % (st["active_lanes"] / e, st["cells_visited"] / e, st["cells_mine"] / e, st["cells_cand"] / e,
-                                                 st["candidates"] / e, st["union_pass"] / e, st["lane_pass"] / max(st["union_pass"], 1), st["incoherent"] / e))
-g = list(out)[16:26]
-if g[2]:
-    tot = g[2] + g[3]
-    print("guided kernels (wave cycles, both kernels): guide loop %.1f%%, exact values %.1f%%, gradient tail %.1f%%; "
-          "guide-loop iterations %d (%.1f lanes stepping), exact rounds %d (%.1f lanes parked), of which sideways %d (%.1f lanes)" % (
-          100.0 * g[0] / tot, 100.0 * g[1] / tot, 100.0 * g[3] / tot, g[4], g[5] / max(g[4], 1), g[6], g[7] / max(g[6], 1), g[8], g[9] / max(g[8], 1)))
-ph = list(out)[26:31]
-if sum(ph):
-    print("exact value requests served, by phase: " + ", ".join("%s %d (%.2f/segment)" % (n, v, v / max(med.counters()[1], 1))
-                                                               for n, v in zip(("X_F0", "X_CUR", "X_PREV", "X_REFINE", "X_FINAL"), ph)))
+e = report(out, "guided sampleDistance kernels (tu_guided_sd)")
+if hasattr(lib.lib, "gpis_debug_fast_stats_tr"):
+    out_tr = (ctypes.c_uint64 * 32)()
+    lib.lib.gpis_debug_fast_stats_tr(out_tr)
+    e += report(out_tr, "guided transmittance kernels (tu_guided_tr), shadow_lean = %d" % med.get_option("shadow_lean"))
+sd, tr = med.kernel_profile(0), med.kernel_profile(1)
+print("sampleDistance: %d lane evals, %d segments; transmittance: %d lane evals, %d segments" % (sd[2], sd[3], tr[2], tr[3]))
 print("lane evals", med.counters(), "guide steps", med.guide_steps())
 print("active lanes per exact wave-eval: %.1f" % (med.counters()[0] / e))
