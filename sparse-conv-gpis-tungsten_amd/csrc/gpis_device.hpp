@@ -769,6 +769,9 @@ enum PersistPhase : int {
     PP_GRAD = 6,      // sampleGradient                              SCNM.cpp:93-100, GPM.cpp:283 / 319
     PP_DONE = 7       // result complete: write it, take the next ray
 };
+// launch constants the kernels (gpis_lane.hpp) and the host side (gpis_hip.hip) agree on, stated here once
+constexpr int kBlock = 64;                // one wave per workgroup: rays are independent, small blocks balance the march
+constexpr unsigned kPersistSlots = 256;   // ring of ray counters: one per persistent launch in flight
 struct PersistArgs {
     size_t n;
     const gpis_ray_in *rays;

@@ -1,6 +1,6 @@
 // gpis_hip.hip — C ABI (include/gpis.h) of the MI355X sparse-convolution GPIS path: the model build, the handle, the batch and
 // *_host entries, the guide and profiling entries.  The staged scene-S frame drivers are tu_scene.hip; both share gpis_host.hpp.
-//
+// Errors, owning buffers and the round trip of a *_host entry: gpis_host_base.hpp (shared with the weight-space units).
 // Build (see __graft_entry__.build): every .hip of this directory for gfx950, -O3 -ffp-contract=off, linked into libgpis_hip.so.
 //
 // Layout in HBM: rays and results are arrays of the 128-/96-byte PODs of gpis.h (a wave reads
@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "gpis.h"
-#include "gpis_host.hpp"      // gpis_medium, HIP_TRY, CHECK_ARGS, ProfScope; gpis_tables.hpp (FastTable, fast_supported, fast_table_free,
+#include "gpis_host.hpp"      // gpis_medium, ProfScope; HIP_TRY, CHECK_ARGS, DevBuf (gpis_host_base.hpp); gpis_tables.hpp (FastTable, fast_supported, fast_table_free,
                               // GuideField, kBrickFloats, guide_free) — none of the fast or guided device code is seen here
 #include "gpis_launch.hpp"    // the march kernels live in the tu_*.hip translation units
 #include "gpis_nn_mean.hpp"   // the exact evaluator of a neural SDF mean: k_mean over a network (this unit only)
@@ -30,11 +30,9 @@
 
 using namespace gpis;
 using gpis::launch::grid_of;
-constexpr int kBlock = 64;   // one wave per workgroup (gpis_lane.hpp)
-constexpr unsigned kPersistSlots = 256;   // ring of ray counters: one per persistent launch in flight
 
 // ======================================================================================
-// errors
+// errors: the one definition of the text both handle families report through (gpis_host_base.hpp)
 // ======================================================================================
 static thread_local char g_err[512] = "";
 
@@ -51,7 +49,6 @@ extern "C" const char *gpis_last_error(void) { return g_err; }
 // ---- shared with the weight-space medium's translation unit (tu_ws.hip) ----
 namespace gpis {
 int ws_destroy(gpis_medium *m);
-int host_set_err(int code, const char *msg) { return set_err(code, "%s", msg); }
 // a weight-space handle starts with kWsHandleTag where a gpis_medium holds params.abi_version (GPIS_ABI_VERSION)
 bool ws_is_handle(const void *m)
 {
@@ -65,21 +62,19 @@ bool gpis::std_handle(const gpis_medium *m) { return m && !gpis::ws_is_handle(m)
 int gpis::ensure_stage(gpis_medium *m, int slot, size_t bytes, bool exact)
 {
     std::lock_guard<std::mutex> lock(m->stage_mu[slot]);
-    if (m->stage_bytes[slot] >= bytes)
-        return GPIS_OK;
-    if (m->stage[slot])
-        HIP_TRY(hipFree(m->stage[slot]));
-    m->stage[slot] = nullptr;
-    m->stage_bytes[slot] = 0;
-    size_t want = exact ? bytes : bytes + bytes / 4 + 4096;     // exact: whole-frame workspaces (tens of GB; allocation time is per byte)
-    HIP_TRY(hipMalloc(&m->stage[slot], want));
-    m->stage_bytes[slot] = want;
+    HIP_TRY(m->stage[slot].grow(bytes, !exact));     // exact: whole-frame workspaces (tens of GB; allocation time is per byte)
     return GPIS_OK;
 }
 size_t gpis::stage_size(gpis_medium *m, int slot)
 {
     std::lock_guard<std::mutex> lock(m->stage_mu[slot]);
-    return m->stage_bytes[slot];
+    return m->stage[slot].bytes;
+}
+// the *_host round trip (gpis_host_base.hpp) on this handle's lock and staging slots 0..2
+template <typename Call>
+static int host_trip(gpis_medium *m, std::initializer_list<HostArray> arrays, Call call)
+{
+    return host_round_trip(m->mu, m->device, m->stage, [m](int slot, size_t bytes) { return ensure_stage(m, slot, bytes); }, arrays, call);
 }
 
 // ======================================================================================
@@ -517,15 +512,9 @@ extern "C" int gpis_create(const gpis_params *params, int device, gpis_medium **
         return set_err(GPIS_ERR_NO_DEVICE, "gpis_create: device %d is %s, this library is built for gfx950 only", device, prop.gcnArchName);
     gpis_medium *m = new (std::nothrow) gpis_medium();
     if (!m) return set_err(GPIS_ERR_DEVICE, "out of host memory");
-    m->params = *params;
+    m->params = *params;       // every other member starts from its initialiser (gpis_host.hpp)
     m->device = device;
-    for (int i = 0; i < gpis_medium::kStageSlots; ++i) { m->stage[i] = nullptr; m->stage_bytes[i] = 0; }
-    m->d_model = nullptr; m->d_counters = nullptr; m->d_guide_cnt = nullptr; m->d_guide = nullptr;
-    m->batch_hint = GPIS_ORDER_COHERENT;
-    for (int k = 0; k < 2; ++k) { m->ws_event[k] = nullptr; m->ws_event_set[k] = false; }
-    memset(m->hs, 0, sizeof m->hs);
-    m->d_next = nullptr; m->next_slot = 0; m->n_cus = prop.multiProcessorCount;
-    for (int k = 0; k < 8; ++k) m->persist_waves[k] = 0;
+    m->n_cus = prop.multiProcessorCount;
     {   // diagnostic overrides, read here and nowhere else (include/gpis.h: gpis_set_option)
         m->opt[GPIS_OPT_MARCH_FORM] = GPIS_MARCH_FORM_AUTO;
         if (const char *e = getenv("GPIS_MARCH")) {
@@ -554,35 +543,25 @@ extern "C" int gpis_create(const gpis_params *params, int device, gpis_medium **
         m->opt[GPIS_OPT_CHUNK_LOG2] = 0;
         if (const char *e = getenv("GPIS_CHUNK_LOG2")) { int l = atoi(e); m->opt[GPIS_OPT_CHUNK_LOG2] = l < 16 ? 16 : (l > 28 ? 28 : l); }
     }
-    memset(&m->guide, 0, sizeof m->guide);
-    m->profiling = false;
-    for (int k = 0; k < 3; ++k) { m->events_used[k] = 0; m->prof_ms[k] = 0.; m->prof_launches[k] = 0; }
-    memset(&m->fast, 0, sizeof m->fast);
     int st = build_model(*params, m->host_model, m->derived);
     if (st != GPIS_OK) { delete m; return st; }
-    hipError_t e = hipMalloc(&m->d_model, sizeof(DevModel));
-    if (e == hipSuccess) e = hipMalloc(&m->d_counters, 2 * sizeof(Counters));
-    if (e == hipSuccess) e = hipMalloc(&m->d_guide_cnt, 8 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(m->d_guide_cnt, 0, 8 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc(&m->d_guide, sizeof(GuideField));
-    if (e == hipSuccess) e = hipMemset(m->d_guide, 0, sizeof(GuideField));
-    if (e == hipSuccess) e = hipMalloc(&m->d_next, kPersistSlots * sizeof(unsigned int));
-    if (e == hipSuccess) e = hipMemcpy(m->d_model, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(m->d_counters, 0, 2 * sizeof(Counters));
+    hipError_t e = m->d_model.grow(sizeof(DevModel));
+    if (e == hipSuccess) e = m->d_counters.grow(2 * sizeof(Counters));
+    if (e == hipSuccess) e = m->d_guide_cnt.grow(8 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(m->d_guide_cnt.p, 0, 8 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = m->d_guide.grow(sizeof(GuideField));
+    if (e == hipSuccess) e = hipMemset(m->d_guide.p, 0, sizeof(GuideField));
+    if (e == hipSuccess) e = m->d_next.grow(kPersistSlots * sizeof(unsigned int));
+    if (e == hipSuccess) e = hipMemcpy(m->d_model.p, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(m->d_counters.p, 0, 2 * sizeof(Counters));
     if (e != hipSuccess) {
         set_err(GPIS_ERR_DEVICE, "gpis_create: %s", hipGetErrorString(e));
-        if (m->d_model) (void)hipFree(m->d_model);
-        if (m->d_counters) (void)hipFree(m->d_counters);
-        if (m->d_guide_cnt) (void)hipFree(m->d_guide_cnt);
-        if (m->d_guide) (void)hipFree(m->d_guide);
-        if (m->d_next) (void)hipFree(m->d_next);
         delete m;
         return GPIS_ERR_DEVICE;
     }
     st = launch::fast_table_build(m->host_model, &m->fast);
     if (st != GPIS_OK) {
         set_err(st, "gpis_create: building the cell table failed");
-        (void)hipFree(m->d_model); (void)hipFree(m->d_counters); (void)hipFree(m->d_guide_cnt); (void)hipFree(m->d_guide); (void)hipFree(m->d_next);
         delete m;
         return st;
     }
@@ -597,38 +576,6 @@ extern "C" int gpis_destroy(gpis_medium *m)
     if (gpis::ws_is_handle(m)) return gpis::ws_destroy(m);
     (void)hipSetDevice(m->device);
     (void)hipDeviceSynchronize();
-    fast_table_free(&m->fast);
-    guide_free(&m->guide);
-    if (m->d_guide_cnt) (void)hipFree(m->d_guide_cnt);
-    if (m->d_guide) (void)hipFree(m->d_guide);
-    if (m->fs_ws) (void)hipFree(m->fs_ws);
-    if (m->fs_scene_recs) (void)hipFree(m->fs_scene_recs);
-    if (m->fs_scene_next) (void)hipFree(m->fs_scene_next);
-    if (m->d_grid_vox) (void)hipFree(m->d_grid_vox);
-    for (float *v : m->d_mean_vox)
-        if (v) (void)hipFree(v);
-    for (int k = 0; k < 3; ++k)
-        if (m->fs_stage[k]) (void)hipFree(m->fs_stage[k]);
-    for (int k = 0; k < 3; ++k)
-        for (auto &ev : m->events[k]) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    for (int i = 0; i < gpis_medium::kStageSlots; ++i)
-        if (m->stage[i]) (void)hipFree(m->stage[i]);
-    for (int k = 0; k < 2; ++k)
-        if (m->ws_event[k]) (void)hipEventDestroy(m->ws_event[k]);
-    for (int k = 0; k < 2; ++k) {
-        gpis_medium::HostSlot &S = m->hs[k];
-        if (S.pin_in) (void)hipHostFree(S.pin_in);
-        if (S.pin_out) (void)hipHostFree(S.pin_out);
-        if (S.pin_aux) (void)hipHostFree(S.pin_aux);
-        if (S.dev_in) (void)hipFree(S.dev_in);
-        if (S.dev_out) (void)hipFree(S.dev_out);
-        if (S.dev_aux) (void)hipFree(S.dev_aux);
-        if (S.done) (void)hipEventDestroy(S.done);
-        if (S.stream) (void)hipStreamDestroy(S.stream);
-    }
-    if (m->d_model) (void)hipFree(m->d_model);
-    if (m->d_counters) (void)hipFree(m->d_counters);
-    if (m->d_next) (void)hipFree(m->d_next);
     delete m;
     return GPIS_OK;
 }
@@ -686,12 +633,12 @@ static int wave_march(gpis_medium *m, size_t n, const gpis_ray_in *rays, const u
     int rc = ensure_stage(m, 4, off);
     if (rc) return rc;
     if ((rc = ws_acquire(m, 1, s))) return rc;
-    char *ws = (char *)m->stage[4];
+    char *ws = (char *)m->stage[4].p;
     unsigned long long *d_req = (unsigned long long *)(ws + o_cnt);
     uint32_t *k0 = (uint32_t *)(ws + o_k0), *v0 = (uint32_t *)(ws + o_v0), *k1 = (uint32_t *)(ws + o_k1), *v1 = (uint32_t *)(ws + o_v1);
     const launch::WaveBufs wb{ws + o_state, k0, v0, k1, v1, d_req};
     const bool small_arg = m->host_model.exp_arg_max < 100.f;
-    Counters *cnt = m->d_counters + (want_sample ? 0 : 1);
+    Counters *cnt = m->d_counters.p + (want_sample ? 0 : 1);
     auto read_requests = [&](size_t &n_req) -> int {
         unsigned long long h = 0;
         HIP_TRY(hipMemcpyAsync(&h, d_req, sizeof h, hipMemcpyDeviceToHost, s));
@@ -706,7 +653,7 @@ static int wave_march(gpis_medium *m, size_t n, const gpis_ray_in *rays, const u
     const uint32_t *active = nullptr;
     int init = 1;
     for (;;) {
-        launch::wave_step(want_sample, m->d_model, m->guide, n_active, active, init, rays, mask, wb, m->d_guide_cnt, s);
+        launch::wave_step(want_sample, m->d_model.p, m->guide, n_active, active, init, rays, mask, wb, m->d_guide_cnt.p, s);
         if ((rc = launch_check("k_wave_step"))) return rc;
         size_t n_req = 0;
         if ((rc = read_requests(n_req))) return rc;
@@ -715,20 +662,20 @@ static int wave_march(gpis_medium *m, size_t n, const gpis_ray_in *rays, const u
         size_t tb = temp_bytes;
         if (sort_pairs_u32(ws + o_temp, tb, k0, k1, v0, v1, n_active, s) != hipSuccess)
             return set_err(GPIS_ERR_DEVICE, "radix sort failed");
-        launch::wave_eval(small_arg, m->d_model, m->fast, m->guide, n_req, v1, rays, wb, cnt, s);
+        launch::wave_eval(small_arg, m->d_model.p, m->fast, m->guide, n_req, v1, rays, wb, cnt, s);
         if ((rc = launch_check("k_wave_eval"))) return rc;
         active = v1;            // the sorted requesters are the rays still marching
         n_active = n_req;
         init = 0;
         if (n_active <= tail_limit) {
             // few rays left: one wave per ray runs them to the end of their value requests
-            launch::wave_tail(want_sample, m->d_model, m->fast, m->guide, n_active, active, rays, wb, cnt, m->d_guide_cnt, s);
+            launch::wave_tail(want_sample, m->d_model.p, m->fast, m->guide, n_active, active, rays, wb, cnt, m->d_guide_cnt.p, s);
             if ((rc = launch_check("k_wave_tail"))) return rc;
             break;
         }
     }
     if (want_sample) {
-        launch::wave_grad_keys(m->d_model, m->guide, n, rays, wb, s);
+        launch::wave_grad_keys(m->d_model.p, m->guide, n, rays, wb, s);
         if ((rc = launch_check("k_wave_grad_keys"))) return rc;
         size_t n_grad = 0;
         if ((rc = read_requests(n_grad))) return rc;
@@ -736,10 +683,10 @@ static int wave_march(gpis_medium *m, size_t n, const gpis_ray_in *rays, const u
             size_t tb = temp_bytes;
             if (sort_pairs_u32(ws + o_temp, tb, k0, k1, v0, v1, n, s) != hipSuccess)
                 return set_err(GPIS_ERR_DEVICE, "radix sort failed");
-            launch::wave_grad(small_arg, m->d_model, m->fast, m->guide, n_grad, v1, rays, wb, cnt, s);
+            launch::wave_grad(small_arg, m->d_model.p, m->fast, m->guide, n_grad, v1, rays, wb, cnt, s);
             if ((rc = launch_check("k_wave_grad"))) return rc;
         }
-        launch::wave_finish_sd(m->d_model, n, rays, mask, wb, out, coeff, cnt, s);
+        launch::wave_finish_sd(m->d_model.p, n, rays, mask, wb, out, coeff, cnt, s);
         if ((rc = launch_check("k_wave_finish_sd"))) return rc;
         return ws_release(m, 1, s);
     }
@@ -785,9 +732,9 @@ static int launch_persist(gpis_medium *m, PersistArgs a, hipStream_t s)
     }
     const size_t waves_needed = (a.n + kBlock - 1) / kBlock;
     const unsigned grid = (unsigned)(waves_needed < (size_t)m->persist_waves[slot_id] ? waves_needed : (size_t)m->persist_waves[slot_id]);
-    a.next = m->d_next + (m->next_slot++ % kPersistSlots);
+    a.next = m->d_next.p + (m->next_slot++ % kPersistSlots);
     HIP_TRY(hipMemsetAsync(a.next, 0, sizeof(unsigned int), s));
-    launch::persist_march(inst, WANT_SAMPLE, grid, m->d_model, a, s);
+    launch::persist_march(inst, WANT_SAMPLE, grid, m->d_model.p, a, s);
     return launch_check("k_persist_march");
 }
 // neePDF / neeGrad: the 1D-sampling instance for the media the NEE estimators are built for, else the all-features one
@@ -813,37 +760,37 @@ int gpis::sample_distance_impl(gpis_medium *m, size_t n, const gpis_ray_in *rays
         return wave_march(m, n, rays, mask, true, out, coeff, nullptr, s);
     if (m->guide.enabled && m->opt[GPIS_OPT_RANGE_LEN] > 0) {
         // guided march with in-wave refill (gpis_guide_range.hpp) + one coherent gradient pass
-        launch::range_sample_distance(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->guide, n, rays, out, coeff, mask, m->d_counters, m->d_guide_cnt,
+        launch::range_sample_distance(m->host_model.exp_arg_max < 100.f, m->d_model.p, m->fast, m->guide, n, rays, out, coeff, mask, m->d_counters.p, m->d_guide_cnt.p,
                                       (uint32_t)m->opt[GPIS_OPT_RANGE_LEN], s);
         return launch_check("k_guided_range_sd / k_guided_range_grad");
     }
     if (m->guide.enabled) {
         if (m->opt[GPIS_OPT_DEFER_GRAD]) {
-            launch::guided_sample_distance_nograd(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->d_guide, n, rays, out, coeff, mask, m->d_counters, m->d_guide_cnt, s);
+            launch::guided_sample_distance_nograd(m->host_model.exp_arg_max < 100.f, m->d_model.p, m->fast, m->d_guide.p, n, rays, out, coeff, mask, m->d_counters.p, m->d_guide_cnt.p, s);
             int rc = launch_check("k_guided_sample_distance_nograd");
             if (rc) return rc;
-            launch::range_grad(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->guide, n, rays, out, coeff, mask, m->d_counters, s);
+            launch::range_grad(m->host_model.exp_arg_max < 100.f, m->d_model.p, m->fast, m->guide, n, rays, out, coeff, mask, m->d_counters.p, s);
             return launch_check("k_guided_range_grad");
         }
         if (!exit_state) {
-            launch::guided_sample_distance_noexit(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->d_guide, n, rays, out, coeff, mask, m->d_counters, m->d_guide_cnt, s);
+            launch::guided_sample_distance_noexit(m->host_model.exp_arg_max < 100.f, m->d_model.p, m->fast, m->d_guide.p, n, rays, out, coeff, mask, m->d_counters.p, m->d_guide_cnt.p, s);
             return launch_check("k_guided_sample_distance_noexit");
         }
-        launch::guided_sample_distance(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->d_guide, n, rays, out, coeff, mask, m->d_counters, m->d_guide_cnt, s);
+        launch::guided_sample_distance(m->host_model.exp_arg_max < 100.f, m->d_model.p, m->fast, m->d_guide.p, n, rays, out, coeff, mask, m->d_counters.p, m->d_guide_cnt.p, s);
         return launch_check("k_guided_sample_distance");
     }
     if (m->fast.enabled) {
-        launch::fast_sample_distance(m->d_model, m->fast, n, rays, out, coeff, mask, m->d_counters, s);
+        launch::fast_sample_distance(m->d_model.p, m->fast, n, rays, out, coeff, mask, m->d_counters.p, s);
         return launch_check("k_fast_sample_distance");
     }
     // pick the instance whose compile-time flags equal the medium's
     const DevModel &H = m->host_model;
     if (m->opt[GPIS_OPT_PERSISTENT] && persist_supported(H)) {
         PersistArgs a{};
-        a.n = n; a.rays = rays; a.out = out; a.coeff = coeff; a.visible = nullptr; a.mask = mask; a.cnt = m->d_counters;
+        a.n = n; a.rays = rays; a.out = out; a.coeff = coeff; a.visible = nullptr; a.mask = mask; a.cnt = m->d_counters.p;
         return launch_persist<true>(m, a, s);
     }
-    launch::lane_sample_distance(lane_instance(H), m->d_model, n, rays, out, coeff, mask, m->d_counters, s);
+    launch::lane_sample_distance(lane_instance(H), m->d_model.p, n, rays, out, coeff, mask, m->d_counters.p, s);
     return launch_check("k_sample_distance");
 }
 int gpis::transmittance_impl(gpis_medium *m, size_t n, const gpis_ray_in *rays, uint8_t *visible, const uint8_t *mask, hipStream_t s,
@@ -854,25 +801,25 @@ int gpis::transmittance_impl(gpis_medium *m, size_t n, const gpis_ray_in *rays, 
     if (m->guide.enabled && wave_march_selected(m, hint))
         return wave_march(m, n, rays, mask, false, nullptr, nullptr, visible, s);
     if (m->guide.enabled && m->opt[GPIS_OPT_RANGE_LEN] > 0) {
-        launch::range_transmittance(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->guide, n, rays, visible, mask, m->d_counters + 1, m->d_guide_cnt,
+        launch::range_transmittance(m->host_model.exp_arg_max < 100.f, m->d_model.p, m->fast, m->guide, n, rays, visible, mask, m->d_counters.p + 1, m->d_guide_cnt.p,
                                     (uint32_t)m->opt[GPIS_OPT_RANGE_LEN], s);
         return launch_check("k_guided_range_tr");
     }
     if (m->guide.enabled) {
-        launch::guided_transmittance(m->host_model.exp_arg_max < 100.f, m->opt[GPIS_OPT_SHADOW_LEAN] != 0, m->d_model, m->fast, m->d_guide, n, rays, visible, mask, m->d_counters + 1, m->d_guide_cnt, s);
+        launch::guided_transmittance(m->host_model.exp_arg_max < 100.f, m->opt[GPIS_OPT_SHADOW_LEAN] != 0, m->d_model.p, m->fast, m->d_guide.p, n, rays, visible, mask, m->d_counters.p + 1, m->d_guide_cnt.p, s);
         return launch_check(m->opt[GPIS_OPT_SHADOW_LEAN] ? "k_shadow_lean" : "k_guided_transmittance");
     }
     if (m->fast.enabled) {
-        launch::fast_transmittance(m->d_model, m->fast, n, rays, visible, mask, m->d_counters + 1, s);
+        launch::fast_transmittance(m->d_model.p, m->fast, n, rays, visible, mask, m->d_counters.p + 1, s);
         return launch_check("k_fast_transmittance");
     }
     const DevModel &H = m->host_model;
     if (m->opt[GPIS_OPT_PERSISTENT] && persist_supported(H)) {
         PersistArgs a{};
-        a.n = n; a.rays = rays; a.out = nullptr; a.coeff = nullptr; a.visible = visible; a.mask = mask; a.cnt = m->d_counters + 1;
+        a.n = n; a.rays = rays; a.out = nullptr; a.coeff = nullptr; a.visible = visible; a.mask = mask; a.cnt = m->d_counters.p + 1;
         return launch_persist<false>(m, a, s);
     }
-    launch::lane_transmittance(lane_instance(H), m->d_model, n, rays, visible, mask, m->d_counters + 1, s);
+    launch::lane_transmittance(lane_instance(H), m->d_model.p, n, rays, visible, mask, m->d_counters.p + 1, s);
     return launch_check("k_transmittance");
 }
 
@@ -891,14 +838,14 @@ int gpis::scene_sample_distance_compact(gpis_medium *m, size_t n, const SceneRay
 {
     if (n == 0) return GPIS_OK;
     ProfScope prof(m, 0, s);
-    launch::guided_sample_distance_scene(m->host_model.exp_arg_max < 100.f, m->d_model, m->fast, m->d_guide, n, rays, out, origin, m->d_counters, m->d_guide_cnt, s);
+    launch::guided_sample_distance_scene(m->host_model.exp_arg_max < 100.f, m->d_model.p, m->fast, m->d_guide.p, n, rays, out, origin, m->d_counters.p, m->d_guide_cnt.p, s);
     return launch_check("k_guided_sample_distance_scene");
 }
 int gpis::scene_transmittance_compact(gpis_medium *m, size_t n, const SceneRay *rays, const float light[3], uint8_t *visible, hipStream_t s)
 {
     if (n == 0) return GPIS_OK;
     ProfScope prof(m, 1, s);
-    launch::guided_transmittance_scene(m->host_model.exp_arg_max < 100.f, m->opt[GPIS_OPT_SHADOW_LEAN] != 0, m->d_model, m->fast, m->d_guide, n, rays, light, visible, m->d_counters + 1, m->d_guide_cnt, s);
+    launch::guided_transmittance_scene(m->host_model.exp_arg_max < 100.f, m->opt[GPIS_OPT_SHADOW_LEAN] != 0, m->d_model.p, m->fast, m->d_guide.p, n, rays, light, visible, m->d_counters.p + 1, m->d_guide_cnt.p, s);
     return launch_check(m->opt[GPIS_OPT_SHADOW_LEAN] ? "k_shadow_lean_scene" : "k_guided_transmittance_scene");
 }
 
@@ -951,7 +898,7 @@ extern "C" int gpis_eval_value_batch(gpis_medium *m, size_t n, const gpis_query 
     CHECK_ARGS(std_handle(m) && (n == 0 || (q && value)));
     if (n == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
-    launch::eval_value(m->d_model, n, q, value, gp_id, m->d_counters, (hipStream_t)stream);
+    launch::eval_value(m->d_model.p, n, q, value, gp_id, m->d_counters.p, (hipStream_t)stream);
     return launch_check("k_eval_value");
 }
 extern "C" int gpis_eval_gradient_batch(gpis_medium *m, size_t n, const gpis_query *q, float *grad3, void *stream)
@@ -959,7 +906,7 @@ extern "C" int gpis_eval_gradient_batch(gpis_medium *m, size_t n, const gpis_que
     CHECK_ARGS(std_handle(m) && (n == 0 || (q && grad3)));
     if (n == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
-    launch::eval_gradient(m->d_model, n, q, grad3, m->d_counters, (hipStream_t)stream);
+    launch::eval_gradient(m->d_model.p, n, q, grad3, m->d_counters.p, (hipStream_t)stream);
     return launch_check("k_eval_gradient");
 }
 extern "C" int gpis_conditioning_batch(gpis_medium *m, size_t n, const gpis_query *q, const float *target_val, const float *target_grad3,
@@ -968,7 +915,7 @@ extern "C" int gpis_conditioning_batch(gpis_medium *m, size_t n, const gpis_quer
     CHECK_ARGS(std_handle(m) && (n == 0 || (q && target_val && target_grad3 && coeff_out)));
     if (n == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
-    launch::conditioning(m->d_model, n, q, target_val, target_grad3, coeff_out, m->d_counters, (hipStream_t)stream);
+    launch::conditioning(m->d_model.p, n, q, target_val, target_grad3, coeff_out, m->d_counters.p, (hipStream_t)stream);
     return launch_check("k_conditioning");
 }
 extern "C" int gpis_nee_pdf_batch(gpis_medium *m, size_t n, const gpis_nee_query *q, float *pdf, void *stream)
@@ -976,7 +923,7 @@ extern "C" int gpis_nee_pdf_batch(gpis_medium *m, size_t n, const gpis_nee_query
     CHECK_ARGS(std_handle(m) && (n == 0 || (q && pdf)));
     if (n == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
-    launch::nee(nee_instance(m->host_model), m->d_model, n, q, pdf, nullptr, m->d_counters, nullptr, (hipStream_t)stream);
+    launch::nee(nee_instance(m->host_model), m->d_model.p, n, q, pdf, nullptr, m->d_counters.p, nullptr, (hipStream_t)stream);
     return launch_check("k_nee");
 }
 extern "C" int gpis_nee_grad_batch(gpis_medium *m, size_t n, const gpis_nee_query *q, float *grad3, void *stream)
@@ -984,7 +931,7 @@ extern "C" int gpis_nee_grad_batch(gpis_medium *m, size_t n, const gpis_nee_quer
     CHECK_ARGS(std_handle(m) && (n == 0 || (q && grad3)));
     if (n == 0) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
-    launch::nee(nee_instance(m->host_model), m->d_model, n, q, nullptr, grad3, m->d_counters, nullptr, (hipStream_t)stream);
+    launch::nee(nee_instance(m->host_model), m->d_model.p, n, q, nullptr, grad3, m->d_counters.p, nullptr, (hipStream_t)stream);
     return launch_check("k_nee");
 }
 extern "C" int gpis_mean_color_emission_batch(gpis_medium *m, size_t n, const double *p3, float *color3, float *emission3, void *stream)
@@ -992,7 +939,7 @@ extern "C" int gpis_mean_color_emission_batch(gpis_medium *m, size_t n, const do
     CHECK_ARGS(std_handle(m) && (n == 0 || p3));
     if (n == 0 || (!color3 && !emission3)) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
-    k_mean_color_emission<<<grid_of(n, 256), 256, 0, (hipStream_t)stream>>>(m->d_model, n, p3, color3, emission3);
+    k_mean_color_emission<<<grid_of(n, 256), 256, 0, (hipStream_t)stream>>>(m->d_model.p, n, p3, color3, emission3);
     return launch_check("k_mean_color_emission");
 }
 extern "C" int gpis_mean_batch(gpis_medium *m, size_t n, const double *p3, double *value, int32_t *id, double *grad3, void *stream)
@@ -1000,7 +947,7 @@ extern "C" int gpis_mean_batch(gpis_medium *m, size_t n, const double *p3, doubl
     CHECK_ARGS(std_handle(m) && (n == 0 || p3));
     if (n == 0 || (!value && !id && !grad3)) return GPIS_OK;
     HIP_TRY(hipSetDevice(m->device));
-    k_mean<<<grid_of(n, 256), 256, 0, (hipStream_t)stream>>>(m->d_model, n, p3, value, id, grad3);
+    k_mean<<<grid_of(n, 256), 256, 0, (hipStream_t)stream>>>(m->d_model.p, n, p3, value, id, grad3);
     return launch_check("k_mean");
 }
 // function-space comparison path: gpis_fs.hpp
@@ -1023,20 +970,20 @@ int gpis::fs_workspace(gpis_medium *m, unsigned &cap, size_t scene_rec_bytes)
     cap = (unsigned)(m->n_cus > 0 ? m->n_cus : 256) * 4u;
     std::lock_guard<std::mutex> lock(m->mu);
     if (m->fs_ws_blocks < cap) {
-        if (m->fs_ws) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(m->fs_ws); m->fs_ws = nullptr; m->fs_slots = nullptr; m->fs_ws_blocks = 0; }
+        if (m->fs_ws.p) HIP_TRY(hipDeviceSynchronize());
+        m->fs_slots = nullptr; m->fs_ws_blocks = 0;
         const size_t slices = (size_t)cap * launch::fs_workspace_bytes_per_block();
-        if (hipMalloc(&m->fs_ws, slices + 2 * (size_t)cap * sizeof(gpis_fs_state)) != hipSuccess) { (void)hipGetLastError(); return set_err(GPIS_ERR_DEVICE, "function-space workspace allocation failed"); }
-        m->fs_slots = (gpis_fs_state *)((char *)m->fs_ws + slices);
+        if (m->fs_ws.grow(slices + 2 * (size_t)cap * sizeof(gpis_fs_state)) != hipSuccess) { (void)hipGetLastError(); return set_err(GPIS_ERR_DEVICE, "function-space workspace allocation failed"); }
+        m->fs_slots = (gpis_fs_state *)((char *)m->fs_ws.p + slices);
         m->fs_ws_blocks = cap;
     }
-    if (scene_rec_bytes && !m->fs_scene_next && hipMalloc(&m->fs_scene_next, sizeof(uint32_t)) != hipSuccess) {
+    if (scene_rec_bytes && m->fs_scene_next.grow(sizeof(uint32_t)) != hipSuccess) {
         (void)hipGetLastError();
         return set_err(GPIS_ERR_DEVICE, "function-space frame counter allocation failed");
     }
-    if (m->fs_scene_rec_bytes < scene_rec_bytes) {
-        if (m->fs_scene_recs) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(m->fs_scene_recs); m->fs_scene_recs = nullptr; m->fs_scene_rec_bytes = 0; }
-        if (hipMalloc(&m->fs_scene_recs, scene_rec_bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(GPIS_ERR_DEVICE, "function-space frame records: no memory for %zu bytes", scene_rec_bytes); }
-        m->fs_scene_rec_bytes = scene_rec_bytes;
+    if (m->fs_scene_recs.bytes < scene_rec_bytes) {
+        if (m->fs_scene_recs.p) HIP_TRY(hipDeviceSynchronize());
+        if (m->fs_scene_recs.grow(scene_rec_bytes) != hipSuccess) { (void)hipGetLastError(); return set_err(GPIS_ERR_DEVICE, "function-space frame records: no memory for %zu bytes", scene_rec_bytes); }
     }
     return GPIS_OK;
 }
@@ -1046,7 +993,7 @@ static int fs_launch(bool want_sample, gpis_medium *m, size_t n, const gpis_ray_
     unsigned cap = 0;
     if (int st = fs_workspace(m, cap)) return st;
     const unsigned grid = (unsigned)(n < cap ? n : cap);
-    launch::fs_march(want_sample, grid, m->d_model, n, rays, states, out, visible, m->fs_ws, s);
+    launch::fs_march(want_sample, grid, m->d_model.p, n, rays, states, out, visible, m->fs_ws.p, s);
     return launch_check("k_fs_march");
 }
 #ifdef GPIS_FS_PROF
@@ -1059,7 +1006,7 @@ extern "C" int gpis_fs_linalg_batch(gpis_medium *m, int op, int n, size_t count,
     HIP_TRY(hipSetDevice(m->device));
     unsigned cap = 0;
     if (int st = fs_workspace(m, cap)) return st;
-    launch::fs_linalg((unsigned)(count < cap ? count : cap), op, n, count, in, out, evals, m->fs_ws, (hipStream_t)stream);
+    launch::fs_linalg((unsigned)(count < cap ? count : cap), op, n, count, in, out, evals, m->fs_ws.p, (hipStream_t)stream);
     return launch_check("k_fs_linalg");
 }
 extern "C" int gpis_sort_pairs_u32(size_t n, const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out, void *stream)
@@ -1069,11 +1016,10 @@ extern "C" int gpis_sort_pairs_u32(size_t n, const uint32_t *keys_in, const uint
     if (sort_pairs_u32(nullptr, tb, nullptr, nullptr, nullptr, nullptr, n, (hipStream_t)stream) != hipSuccess)
         return set_err(GPIS_ERR_INVALID_ARG, "gpis_sort_pairs_u32: batch too large");
     if (n == 0) return GPIS_OK;
-    void *temp = nullptr;
-    HIP_TRY(hipMalloc(&temp, tb));
-    hipError_t e = sort_pairs_u32(temp, tb, keys_in, keys_out, vals_in, vals_out, n, (hipStream_t)stream);
+    DevBuf<> temp;
+    HIP_TRY(temp.grow(tb));
+    hipError_t e = sort_pairs_u32(temp.p, tb, keys_in, keys_out, vals_in, vals_out, n, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(temp);
     if (e != hipSuccess) return set_err(GPIS_ERR_DEVICE, "gpis_sort_pairs_u32: %s", hipGetErrorString(e));
     return GPIS_OK;
 }
@@ -1104,26 +1050,11 @@ static int fs_host(gpis_medium *m, bool want_sample, size_t n, const gpis_ray_in
 {
     if (int st = fs_check(m)) return st;
     if (n == 0) return GPIS_OK;
-    std::lock_guard<std::mutex> lock(m->fs_host_mu);
-    HIP_TRY(hipSetDevice(m->device));
-    const size_t out_rec = want_sample ? sizeof(gpis_seg_out) : 1;
-    const size_t need[3] = {n * sizeof(gpis_ray_in), n * sizeof(gpis_fs_state), n * out_rec};
-    for (int k = 0; k < 3; ++k)
-        if (m->fs_stage_bytes[k] < need[k]) {
-            if (m->fs_stage[k]) { HIP_TRY(hipFree(m->fs_stage[k])); m->fs_stage[k] = nullptr; m->fs_stage_bytes[k] = 0; }
-            HIP_TRY(hipMalloc(&m->fs_stage[k], need[k] + need[k] / 4 + 4096));
-            m->fs_stage_bytes[k] = need[k] + need[k] / 4 + 4096;
-        }
-    void *d_rays = m->fs_stage[0], *d_states = m->fs_stage[1], *d_out = m->fs_stage[2];
-    HIP_TRY(hipMemcpy(d_rays, rays, n * sizeof(gpis_ray_in), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_states, states, n * sizeof(gpis_fs_state), hipMemcpyHostToDevice));
-    int st = fs_launch(want_sample, m, n, (const gpis_ray_in *)d_rays, (gpis_fs_state *)d_states, want_sample ? (gpis_seg_out *)d_out : nullptr,
-                       want_sample ? nullptr : (uint8_t *)d_out, nullptr);
-    if (st) return st;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(states, d_states, n * sizeof(gpis_fs_state), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out, d_out, n * out_rec, hipMemcpyDeviceToHost));
-    return GPIS_OK;
+    DevBuf<> *d = m->fs_stage;
+    return host_round_trip(m->fs_host_mu, m->device, d, GrowStage{d},
+                           {{rays, nullptr, n * sizeof(gpis_ray_in), 0}, {states, states, n * sizeof(gpis_fs_state), 1}, {nullptr, out, n * (want_sample ? sizeof(gpis_seg_out) : 1), 2}},
+                           [&] { return fs_launch(want_sample, m, n, (const gpis_ray_in *)d[0].p, (gpis_fs_state *)d[1].p, want_sample ? (gpis_seg_out *)d[2].p : nullptr,
+                                                  want_sample ? nullptr : (uint8_t *)d[2].p, nullptr); });
 }
 extern "C" int gpis_fs_sample_distance_host(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_fs_state *states, gpis_seg_out *out)
 {
@@ -1139,38 +1070,17 @@ extern "C" int gpis_mean_color_emission_host(gpis_medium *m, size_t n, const dou
 {
     CHECK_ARGS(std_handle(m) && (n == 0 || p3));
     if (n == 0 || (!color3 && !emission3)) return GPIS_OK;
-    std::lock_guard<std::mutex> lock(m->mu);
-    HIP_TRY(hipSetDevice(m->device));
-    int st;
-    if ((st = ensure_stage(m, 0, 3 * n * sizeof(double))) || (st = ensure_stage(m, 1, 3 * n * sizeof(float))) || (st = ensure_stage(m, 2, 3 * n * sizeof(float))))
-        return st;
-    HIP_TRY(hipMemcpy(m->stage[0], p3, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    st = gpis_mean_color_emission_batch(m, n, (const double *)m->stage[0], color3 ? (float *)m->stage[1] : nullptr, emission3 ? (float *)m->stage[2] : nullptr, nullptr);
-    if (st) return st;
-    HIP_TRY(hipDeviceSynchronize());
-    if (color3) HIP_TRY(hipMemcpy(color3, m->stage[1], 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-    if (emission3) HIP_TRY(hipMemcpy(emission3, m->stage[2], 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-    return GPIS_OK;
+    return host_trip(m, {{p3, nullptr, 3 * n * sizeof(double), 0}, {nullptr, color3, 3 * n * sizeof(float), 1}, {nullptr, emission3, 3 * n * sizeof(float), 2}},
+                     [&] { return gpis_mean_color_emission_batch(m, n, (const double *)m->stage[0].p, color3 ? (float *)m->stage[1].p : nullptr, emission3 ? (float *)m->stage[2].p : nullptr, nullptr); });
 }
 extern "C" int gpis_mean_host(gpis_medium *m, size_t n, const double *p3, double *value, int32_t *id, double *grad3)
 {
     CHECK_ARGS(std_handle(m) && (n == 0 || p3));
     if (n == 0 || (!value && !id && !grad3)) return GPIS_OK;
-    std::lock_guard<std::mutex> lock(m->mu);
-    HIP_TRY(hipSetDevice(m->device));
-    int st;
     // stage[1]: n values, then 3 n gradient components; stage[2]: n ids
-    if ((st = ensure_stage(m, 0, 3 * n * sizeof(double))) || (st = ensure_stage(m, 1, 4 * n * sizeof(double))) || (st = ensure_stage(m, 2, n * sizeof(int32_t))))
-        return st;
-    double *d_val = (double *)m->stage[1], *d_grad = d_val + n;
-    HIP_TRY(hipMemcpy(m->stage[0], p3, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    st = gpis_mean_batch(m, n, (const double *)m->stage[0], value ? d_val : nullptr, id ? (int32_t *)m->stage[2] : nullptr, grad3 ? d_grad : nullptr, nullptr);
-    if (st) return st;
-    HIP_TRY(hipDeviceSynchronize());
-    if (value) HIP_TRY(hipMemcpy(value, d_val, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (id) HIP_TRY(hipMemcpy(id, m->stage[2], n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (grad3) HIP_TRY(hipMemcpy(grad3, d_grad, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
-    return GPIS_OK;
+    return host_trip(m, {{p3, nullptr, 3 * n * sizeof(double), 0}, {nullptr, value, n * sizeof(double), 1}, {nullptr, id, n * sizeof(int32_t), 2}, {nullptr, grad3, 3 * n * sizeof(double), 1, n * sizeof(double)}},
+                     [&] { double *d_val = (double *)m->stage[1].p;
+                           return gpis_mean_batch(m, n, (const double *)m->stage[0].p, value ? d_val : nullptr, id ? (int32_t *)m->stage[2].p : nullptr, grad3 ? d_val + n : nullptr, nullptr); });
 }
 extern "C" int gpis_xxhash32_batch(gpis_medium *m, size_t n, int arity, const uint32_t *words, uint32_t *out, void *stream)
 {
@@ -1214,14 +1124,13 @@ static int host_slot_ensure(gpis_medium *m, int k, size_t cap)
     if (!S.done) HIP_TRY(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
     if (S.cap >= cap) return GPIS_OK;
     HIP_TRY(hipStreamSynchronize(S.stream));
-    if (S.pin_in) { (void)hipHostFree(S.pin_in); (void)hipHostFree(S.pin_out); (void)hipHostFree(S.pin_aux); (void)hipFree(S.dev_in); (void)hipFree(S.dev_out); (void)hipFree(S.dev_aux); }
-    S.pin_in = S.pin_out = S.pin_aux = S.dev_in = S.dev_out = S.dev_aux = nullptr; S.cap = 0;
-    HIP_TRY(hipHostMalloc((void **)&S.pin_in, cap * kInRec, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void **)&S.pin_out, cap * kOutRecMax, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void **)&S.pin_aux, cap * kAuxRec, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&S.dev_in, cap * kInRec));
-    HIP_TRY(hipMalloc((void **)&S.dev_out, cap * kOutRecMax));
-    HIP_TRY(hipMalloc((void **)&S.dev_aux, cap * kAuxRec));
+    S.pin_in.reset(); S.pin_out.reset(); S.pin_aux.reset(); S.dev_in.reset(); S.dev_out.reset(); S.dev_aux.reset(); S.cap = 0;      // all six go before the first comes back
+    HIP_TRY(S.pin_in.grow(cap * kInRec));
+    HIP_TRY(S.pin_out.grow(cap * kOutRecMax));
+    HIP_TRY(S.pin_aux.grow(cap * kAuxRec));
+    HIP_TRY(S.dev_in.grow(cap * kInRec));
+    HIP_TRY(S.dev_out.grow(cap * kOutRecMax));
+    HIP_TRY(S.dev_aux.grow(cap * kAuxRec));
     S.cap = cap;
     return GPIS_OK;
 }
@@ -1245,8 +1154,8 @@ static int host_march(gpis_medium *m, bool sample, size_t n, const gpis_ray_in *
         gpis_medium::HostSlot &S = m->hs[k];
         if (!pend[k].live) return GPIS_OK;
         HIP_TRY(hipEventSynchronize(S.done));
-        if (!out_pinned) memcpy((char *)out + pend[k].first * out_rec, S.pin_out, pend[k].count * out_rec);
-        if (aux && !aux_pinned) memcpy(aux + pend[k].first, S.pin_aux, pend[k].count * kAuxRec);
+        if (!out_pinned) memcpy((char *)out + pend[k].first * out_rec, S.pin_out.p, pend[k].count * out_rec);
+        if (aux && !aux_pinned) memcpy(aux + pend[k].first, S.pin_aux.p, pend[k].count * kAuxRec);
         pend[k].live = false;
         return GPIS_OK;
     };
@@ -1256,15 +1165,15 @@ static int host_march(gpis_medium *m, bool sample, size_t n, const gpis_ray_in *
         if ((st = retire(k))) return st;
         const size_t first = c * chunk, count = n - first < chunk ? n - first : chunk;
         const void *src = rays + first;
-        if (!in_pinned) { memcpy(S.pin_in, src, count * kInRec); src = S.pin_in; }
-        HIP_TRY(hipMemcpyAsync(S.dev_in, src, count * kInRec, hipMemcpyHostToDevice, S.stream));
+        if (!in_pinned) { memcpy(S.pin_in.p, src, count * kInRec); src = S.pin_in.p; }
+        HIP_TRY(hipMemcpyAsync(S.dev_in.p, src, count * kInRec, hipMemcpyHostToDevice, S.stream));
         if (sample)
-            st = sample_distance_impl(m, count, (const gpis_ray_in *)S.dev_in, (gpis_seg_out *)S.dev_out, aux ? (gpis_cond_coeff *)S.dev_aux : nullptr, nullptr, S.stream);
+            st = sample_distance_impl(m, count, (const gpis_ray_in *)S.dev_in.p, (gpis_seg_out *)S.dev_out.p, aux ? (gpis_cond_coeff *)S.dev_aux.p : nullptr, nullptr, S.stream);
         else
-            st = transmittance_impl(m, count, (const gpis_ray_in *)S.dev_in, (uint8_t *)S.dev_out, nullptr, S.stream);
+            st = transmittance_impl(m, count, (const gpis_ray_in *)S.dev_in.p, (uint8_t *)S.dev_out.p, nullptr, S.stream);
         if (st) return st;
-        HIP_TRY(hipMemcpyAsync(out_pinned ? (char *)out + first * out_rec : S.pin_out, S.dev_out, count * out_rec, hipMemcpyDeviceToHost, S.stream));
-        if (aux) HIP_TRY(hipMemcpyAsync(aux_pinned ? (char *)(aux + first) : S.pin_aux, S.dev_aux, count * kAuxRec, hipMemcpyDeviceToHost, S.stream));
+        HIP_TRY(hipMemcpyAsync(out_pinned ? (char *)out + first * out_rec : S.pin_out.p, S.dev_out.p, count * out_rec, hipMemcpyDeviceToHost, S.stream));
+        if (aux) HIP_TRY(hipMemcpyAsync(aux_pinned ? (char *)(aux + first) : S.pin_aux.p, S.dev_aux.p, count * kAuxRec, hipMemcpyDeviceToHost, S.stream));
         HIP_TRY(hipEventRecord(S.done, S.stream));
         pend[k] = {first, count, true};
     }
@@ -1301,34 +1210,15 @@ extern "C" int gpis_eval_value_host(gpis_medium *m, size_t n, const gpis_query *
 {
     CHECK_ARGS(std_handle(m) && (n == 0 || (q && value)));
     if (n == 0) return GPIS_OK;
-    std::lock_guard<std::mutex> lock(m->mu);
-    HIP_TRY(hipSetDevice(m->device));
-    int st;
-    if ((st = ensure_stage(m, 0, n * sizeof(gpis_query))) || (st = ensure_stage(m, 1, n * sizeof(float))) || (st = ensure_stage(m, 2, n * sizeof(int32_t))))
-        return st;
-    HIP_TRY(hipMemcpy(m->stage[0], q, n * sizeof(gpis_query), hipMemcpyHostToDevice));
-    st = gpis_eval_value_batch(m, n, (const gpis_query *)m->stage[0], (float *)m->stage[1], (int32_t *)m->stage[2], nullptr);
-    if (st) return st;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(value, m->stage[1], n * sizeof(float), hipMemcpyDeviceToHost));
-    if (gp_id) HIP_TRY(hipMemcpy(gp_id, m->stage[2], n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return GPIS_OK;
+    return host_trip(m, {{q, nullptr, n * sizeof(gpis_query), 0}, {nullptr, value, n * sizeof(float), 1}, {nullptr, gp_id, n * sizeof(int32_t), 2}},
+                     [&] { return gpis_eval_value_batch(m, n, (const gpis_query *)m->stage[0].p, (float *)m->stage[1].p, (int32_t *)m->stage[2].p, nullptr); });
 }
 extern "C" int gpis_eval_gradient_host(gpis_medium *m, size_t n, const gpis_query *q, float *grad3)
 {
     CHECK_ARGS(std_handle(m) && (n == 0 || (q && grad3)));
     if (n == 0) return GPIS_OK;
-    std::lock_guard<std::mutex> lock(m->mu);
-    HIP_TRY(hipSetDevice(m->device));
-    int st;
-    if ((st = ensure_stage(m, 0, n * sizeof(gpis_query))) || (st = ensure_stage(m, 1, 3 * n * sizeof(float))))
-        return st;
-    HIP_TRY(hipMemcpy(m->stage[0], q, n * sizeof(gpis_query), hipMemcpyHostToDevice));
-    st = gpis_eval_gradient_batch(m, n, (const gpis_query *)m->stage[0], (float *)m->stage[1], nullptr);
-    if (st) return st;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(grad3, m->stage[1], 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-    return GPIS_OK;
+    return host_trip(m, {{q, nullptr, n * sizeof(gpis_query), 0}, {nullptr, grad3, 3 * n * sizeof(float), 1}},
+                     [&] { return gpis_eval_gradient_batch(m, n, (const gpis_query *)m->stage[0].p, (float *)m->stage[1].p, nullptr); });
 }
 
 extern "C" int gpis_conditioning_host(gpis_medium *m, size_t n, const gpis_query *q, const float *target_val, const float *target_grad3,
@@ -1336,36 +1226,18 @@ extern "C" int gpis_conditioning_host(gpis_medium *m, size_t n, const gpis_query
 {
     CHECK_ARGS(std_handle(m) && (n == 0 || (q && target_val && target_grad3 && coeff_out)));
     if (n == 0) return GPIS_OK;
-    std::lock_guard<std::mutex> lock(m->mu);
-    HIP_TRY(hipSetDevice(m->device));
-    int st;
-    if ((st = ensure_stage(m, 0, n * sizeof(gpis_query))) || (st = ensure_stage(m, 1, 4 * n * sizeof(float))) ||
-        (st = ensure_stage(m, 2, n * sizeof(gpis_cond_coeff))))
-        return st;
-    float *d_tv = (float *)m->stage[1], *d_tg = d_tv + n;
-    HIP_TRY(hipMemcpy(m->stage[0], q, n * sizeof(gpis_query), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_tv, target_val, n * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_tg, target_grad3, 3 * n * sizeof(float), hipMemcpyHostToDevice));
-    st = gpis_conditioning_batch(m, n, (const gpis_query *)m->stage[0], d_tv, d_tg, (gpis_cond_coeff *)m->stage[2], nullptr);
-    if (st) return st;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(coeff_out, m->stage[2], n * sizeof(gpis_cond_coeff), hipMemcpyDeviceToHost));
-    return GPIS_OK;
+    // stage[1]: n target values, then 3 n target gradient components
+    return host_trip(m, {{q, nullptr, n * sizeof(gpis_query), 0}, {target_val, nullptr, n * sizeof(float), 1}, {target_grad3, nullptr, 3 * n * sizeof(float), 1, n * sizeof(float)},
+                         {nullptr, coeff_out, n * sizeof(gpis_cond_coeff), 2}},
+                     [&] { float *d_tv = (float *)m->stage[1].p;
+                           return gpis_conditioning_batch(m, n, (const gpis_query *)m->stage[0].p, d_tv, d_tv + n, (gpis_cond_coeff *)m->stage[2].p, nullptr); });
 }
 static int nee_host(gpis_medium *m, size_t n, const gpis_nee_query *q, float *pdf, float *grad3)
 {
-    std::lock_guard<std::mutex> lock(m->mu);
-    HIP_TRY(hipSetDevice(m->device));
-    int st;
-    if ((st = ensure_stage(m, 0, n * sizeof(gpis_nee_query))) || (st = ensure_stage(m, 1, 3 * n * sizeof(float))))
-        return st;
-    HIP_TRY(hipMemcpy(m->stage[0], q, n * sizeof(gpis_nee_query), hipMemcpyHostToDevice));
-    st = pdf ? gpis_nee_pdf_batch(m, n, (const gpis_nee_query *)m->stage[0], (float *)m->stage[1], nullptr)
-             : gpis_nee_grad_batch(m, n, (const gpis_nee_query *)m->stage[0], (float *)m->stage[1], nullptr);
-    if (st) return st;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(pdf ? pdf : grad3, m->stage[1], (pdf ? 1 : 3) * n * sizeof(float), hipMemcpyDeviceToHost));
-    return GPIS_OK;
+    // stage[1] has room for the gradients whichever of the two is asked for
+    return host_trip(m, {{q, nullptr, n * sizeof(gpis_nee_query), 0}, {nullptr, nullptr, 3 * n * sizeof(float), 1}, {nullptr, pdf ? pdf : grad3, (pdf ? 1 : 3) * n * sizeof(float), 1}},
+                     [&] { return pdf ? gpis_nee_pdf_batch(m, n, (const gpis_nee_query *)m->stage[0].p, (float *)m->stage[1].p, nullptr)
+                                      : gpis_nee_grad_batch(m, n, (const gpis_nee_query *)m->stage[0].p, (float *)m->stage[1].p, nullptr); });
 }
 extern "C" int gpis_nee_pdf_host(gpis_medium *m, size_t n, const gpis_nee_query *q, float *pdf)
 {
@@ -1385,7 +1257,7 @@ extern "C" int gpis_get_counters(gpis_medium *m, uint64_t *n_eval, uint64_t *n_s
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     Counters c[2];
-    HIP_TRY(hipMemcpy(c, m->d_counters, sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c, m->d_counters.p, sizeof c, hipMemcpyDeviceToHost));
     if (n_eval) *n_eval = c[0].n_eval + c[1].n_eval;
     if (n_seg) *n_seg = c[0].n_seg + c[1].n_seg;
     return GPIS_OK;
@@ -1395,8 +1267,8 @@ extern "C" int gpis_reset_counters(gpis_medium *m)
     CHECK_ARGS(std_handle(m));
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(m->d_counters, 0, 2 * sizeof(Counters)));
-    HIP_TRY(hipMemset(m->d_guide_cnt, 0, 8 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(m->d_counters.p, 0, 2 * sizeof(Counters)));
+    HIP_TRY(hipMemset(m->d_guide_cnt.p, 0, 8 * sizeof(unsigned long long)));
     for (int k = 0; k < 3; ++k) { m->events_used[k] = 0; m->prof_ms[k] = 0.; m->prof_launches[k] = 0; }
     return GPIS_OK;
 }
@@ -1412,11 +1284,11 @@ extern "C" int gpis_build_guide(gpis_medium *m, int half_extent_cells, int point
         return set_err(GPIS_ERR_UNSUPPORTED, "gpis_build_guide: a procedural (SDF) or tabulated (voxel grid) mean has no guide field (no per-brick bound of such a mean is built)");
     if (!m->fast.enabled)
         return set_err(GPIS_ERR_UNSUPPORTED, "gpis_build_guide: the medium is not covered by the wave-cooperative path (single_realization, 3D, stationary SE, diagonal anisotropy)");
-    int st = launch::guide_build(m->host_model, m->d_model, m->fast, half_extent_cells, points_per_cell, &m->guide, getenv("GPIS_GUIDE_DENSE") == nullptr);
+    int st = launch::guide_build(m->host_model, m->d_model.p, m->fast, half_extent_cells, points_per_cell, &m->guide, getenv("GPIS_GUIDE_DENSE") == nullptr);
     if (st != GPIS_OK)
         return set_err(st, "gpis_build_guide(half=%d, ppc=%d) failed: %s", half_extent_cells, points_per_cell,
                        st == GPIS_ERR_UNSUPPORTED ? "unsupported arguments" : hipGetErrorString(hipGetLastError()));
-    HIP_TRY(hipMemcpy(m->d_guide, &m->guide, sizeof(GuideField), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_guide.p, &m->guide, sizeof(GuideField), hipMemcpyHostToDevice));
     return GPIS_OK;
 }
 extern "C" int gpis_drop_guide(gpis_medium *m)
@@ -1426,7 +1298,7 @@ extern "C" int gpis_drop_guide(gpis_medium *m)
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     guide_free(&m->guide);
-    HIP_TRY(hipMemcpy(m->d_guide, &m->guide, sizeof(GuideField), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_guide.p, &m->guide, sizeof(GuideField), hipMemcpyHostToDevice));
     return GPIS_OK;
 }
 extern "C" int gpis_get_guide_steps(gpis_medium *m, uint64_t *n_guide)
@@ -1435,7 +1307,7 @@ extern "C" int gpis_get_guide_steps(gpis_medium *m, uint64_t *n_guide)
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     unsigned long long v = 0;
-    HIP_TRY(hipMemcpy(&v, m->d_guide_cnt, sizeof v, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&v, m->d_guide_cnt.p, sizeof v, hipMemcpyDeviceToHost));
     *n_guide = v;
     return GPIS_OK;
 }
@@ -1446,10 +1318,10 @@ extern "C" int gpis_guide_selfcheck(gpis_medium *m, size_t n, const float *point
     if (!m->guide.enabled) return set_err(GPIS_ERR_UNSUPPORTED, "gpis_guide_selfcheck: no guide field built");
     HIP_TRY(hipSetDevice(m->device));
     // scratch: [0] = points inside the field, [1] = violations, word 2 = {max ratio bits, sum of bounds}, [3] = points in tabulated bricks
-    unsigned long long *st = m->d_guide_cnt + 1;
+    unsigned long long *st = m->d_guide_cnt.p + 1;
     HIP_TRY(hipMemsetAsync(st, 0, 4 * sizeof(unsigned long long), (hipStream_t)stream));
     if (n)
-        launch::guide_selfcheck(m->d_model, m->fast, m->guide, n, points3, st, (float *)(st + 2), (float *)(st + 2) + 1, (hipStream_t)stream);
+        launch::guide_selfcheck(m->d_model.p, m->fast, m->guide, n, points3, st, (float *)(st + 2), (float *)(st + 2) + 1, (hipStream_t)stream);
     int rc = launch_check("k_guide_selfcheck");
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -1486,10 +1358,10 @@ extern "C" int gpis_guide_raycheck(gpis_medium *m, size_t n, const gpis_ray_in *
     CHECK_ARGS(std_handle(m) && (n == 0 || rays));
     if (!m->guide.enabled) return set_err(GPIS_ERR_UNSUPPORTED, "gpis_guide_raycheck: no guide field built");
     HIP_TRY(hipSetDevice(m->device));
-    unsigned long long *st = m->d_guide_cnt + 1;
+    unsigned long long *st = m->d_guide_cnt.p + 1;
     HIP_TRY(hipMemsetAsync(st, 0, 3 * sizeof(unsigned long long), (hipStream_t)stream));
     if (n)
-        launch::guide_raycheck(m->d_model, m->fast, m->guide, n, rays, steps, st, (hipStream_t)stream);
+        launch::guide_raycheck(m->d_model.p, m->fast, m->guide, n, rays, steps, st, (hipStream_t)stream);
     int rc = launch_check("k_guide_raycheck");
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -1519,7 +1391,7 @@ extern "C" int gpis_get_kernel_profile(gpis_medium *m, int which, double *total_
     }
     m->events_used[which] = 0;
     Counters c[2];
-    HIP_TRY(hipMemcpy(c, m->d_counters, sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c, m->d_counters.p, sizeof c, hipMemcpyDeviceToHost));
     if (total_ms) *total_ms = m->prof_ms[which];
     if (launches) *launches = m->prof_launches[which];
     if (n_eval) *n_eval = which < 2 ? c[which].n_eval : 0;      // the NEE queries count into the sampleDistance pair
@@ -1557,32 +1429,31 @@ extern "C" int gpis_set_variance_grid(gpis_medium *m, const gpis_variance_grid *
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t n = (size_t)g->dims[0] * (size_t)g->dims[1] * (size_t)g->dims[2];
-    float *d = nullptr;
-    HIP_TRY(hipMalloc(&d, n * sizeof(float)));
-    if (hipMemcpy(d, voxels, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return set_err(GPIS_ERR_DEVICE, "gpis_set_variance_grid: copy failed"); }
-    if (m->d_grid_vox) HIP_TRY(hipFree(m->d_grid_vox));
-    m->d_grid_vox = d;
+    DevBuf<float> d;
+    HIP_TRY(d.grow(n * sizeof(float)));
+    if (hipMemcpy(d.p, voxels, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_err(GPIS_ERR_DEVICE, "gpis_set_variance_grid: copy failed");
+    m->d_grid_vox.adopt(d.release(), n * sizeof(float));      // frees the earlier array
     DevGrid &G = m->host_model.grid;
-    G.vox = d;
+    G.vox = m->d_grid_vox.p;
     G.interpolate = g->interpolate;
     for (int c = 0; c < 3; ++c) { G.dims[c] = g->dims[c]; G.origin[c] = g->origin[c]; G.lo[c] = g->bounds_min[c] + 2; G.hi[c] = g->bounds_max[c] - 3; }
     for (int i = 0; i < 12; ++i) G.T[i] = g->inv_natural_transform[i];
-    HIP_TRY(hipMemcpy(m->d_model, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_model.p, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
     return GPIS_OK;
 }
 
 // the slot's device array `d` becomes its grid: descriptor into the host model, model refresh, the earlier array freed behind it.
 // The caller holds the handle's lock and has waited for the device.
-static int install_mean_grid(gpis_medium *m, int which, const gpis_variance_grid *g, float *d)
+static int install_mean_grid(gpis_medium *m, int which, const gpis_variance_grid *g, size_t n, float *d)
 {
-    float *old = m->d_mean_vox[which];
-    m->d_mean_vox[which] = d;
+    float *old = m->d_mean_vox[which].release();
+    m->d_mean_vox[which].adopt(d, n * sizeof(float));
     DevGrid &G = m->host_model.mean_grid[which];
     G.vox = d;
     G.interpolate = g->interpolate;
     for (int c = 0; c < 3; ++c) { G.dims[c] = g->dims[c]; G.origin[c] = g->origin[c]; G.lo[c] = g->bounds_min[c] + 2; G.hi[c] = g->bounds_max[c] - 3; }
     for (int i = 0; i < 12; ++i) G.T[i] = g->inv_natural_transform[i];
-    HIP_TRY(hipMemcpy(m->d_model, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_model.p, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
     if (old) HIP_TRY(hipFree(old));          // behind the model refresh: the device model never names a freed array
     return GPIS_OK;
 }
@@ -1597,10 +1468,10 @@ extern "C" int gpis_set_mean_grid(gpis_medium *m, int which, const gpis_variance
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t n = (size_t)g->dims[0] * (size_t)g->dims[1] * (size_t)g->dims[2];
-    float *d = nullptr;
-    HIP_TRY(hipMalloc(&d, n * sizeof(float)));
-    if (hipMemcpy(d, voxels, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return set_err(GPIS_ERR_DEVICE, "gpis_set_mean_grid: copy failed"); }
-    return install_mean_grid(m, which, g, d);
+    DevBuf<float> d;
+    HIP_TRY(d.grow(n * sizeof(float)));
+    if (hipMemcpy(d.p, voxels, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_err(GPIS_ERR_DEVICE, "gpis_set_mean_grid: copy failed");
+    return install_mean_grid(m, which, g, n, d.release());
 }
 
 // Mat4f::invert (Mat4f.hpp:75-101): the adjugate over the determinant, in float.  inv[4 i + j] is the cofactor of (row j, column i):
@@ -1649,7 +1520,7 @@ extern "C" int gpis_set_mean_transform(gpis_medium *m, int which, const float tr
     float inv[16];
     mat4_invert_ref(transform, inv);
     memcpy(m->host_model.sdf_inv[which], inv, 12 * sizeof(float));
-    HIP_TRY(hipMemcpy(m->d_model, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_model.p, &m->host_model, sizeof(DevModel), hipMemcpyHostToDevice));
     return GPIS_OK;
 }
 
@@ -1702,13 +1573,6 @@ static size_t nn_chunk(const nn::Net &N, size_t &ws_bytes)
     ws_bytes = c * per_lane;
     return c;
 }
-// a device allocation that a failing entry leaves behind freed
-struct NnDev {
-    void *p = nullptr;
-    ~NnDev() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    void *release() { void *q = p; p = nullptr; return q; }
-};
 // lat == nullptr: value / grad3 at the n points p3; otherwise voxels [0, n) of the lattice
 static int nn_launch(const nn::Net &N, const double *W, size_t n, const double *p3, double *value, double *grad3, const nn::Lattice *lat, float *voxels,
                      double *ws, hipStream_t s)
@@ -1742,9 +1606,9 @@ extern "C" int gpis_network_mean_batch(const gpis_mean_network *net, const doubl
     if (n == 0 || (!value && !grad3)) return GPIS_OK;
     size_t ws_bytes;
     (void)nn_chunk(N, ws_bytes);
-    NnDev ws;
-    if (ws_bytes) HIP_TRY(ws.alloc(ws_bytes));
-    if (int st = nn_launch(N, weights, n, p3, value, grad3, nullptr, nullptr, (double *)ws.p, (hipStream_t)stream)) return st;
+    DevBuf<double> ws;       // freed on every way out
+    HIP_TRY(ws.grow(ws_bytes));
+    if (int st = nn_launch(N, weights, n, p3, value, grad3, nullptr, nullptr, ws.p, (hipStream_t)stream)) return st;
     if (ws_bytes) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));        // the workspace is this call's: its kernels end before it goes
     return GPIS_OK;
 }
@@ -1755,14 +1619,14 @@ extern "C" int gpis_network_mean_host(const gpis_mean_network *net, const double
     size_t n_weights;
     if (int st = nn_describe(__func__, net, N, n_weights)) return st;
     if (n == 0 || (!value && !grad3)) return GPIS_OK;
-    NnDev dW, dP, dV, dG;
-    HIP_TRY(dW.alloc(n_weights * sizeof(double)));
-    HIP_TRY(dP.alloc(3 * n * sizeof(double)));
-    if (value) HIP_TRY(dV.alloc(n * sizeof(double)));
-    if (grad3) HIP_TRY(dG.alloc(3 * n * sizeof(double)));
+    DevBuf<double> dW, dP, dV, dG;
+    HIP_TRY(dW.grow(n_weights * sizeof(double)));
+    HIP_TRY(dP.grow(3 * n * sizeof(double)));
+    if (value) HIP_TRY(dV.grow(n * sizeof(double)));
+    if (grad3) HIP_TRY(dG.grow(3 * n * sizeof(double)));
     HIP_TRY(hipMemcpy(dW.p, weights, n_weights * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dP.p, p3, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    if (int st = gpis_network_mean_batch(net, (const double *)dW.p, n, (const double *)dP.p, (double *)dV.p, (double *)dG.p, nullptr)) return st;
+    if (int st = gpis_network_mean_batch(net, dW.p, n, dP.p, dV.p, dG.p, nullptr)) return st;
     HIP_TRY(hipDeviceSynchronize());
     if (value) HIP_TRY(hipMemcpy(value, dV.p, n * sizeof(double), hipMemcpyDeviceToHost));
     if (grad3) HIP_TRY(hipMemcpy(grad3, dG.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
@@ -1787,13 +1651,14 @@ extern "C" int gpis_bake_mean_network(gpis_medium *m, int which, const gpis_mean
     memcpy(lat.A, index_to_world, sizeof lat.A);
     size_t ws_bytes;
     (void)nn_chunk(N, ws_bytes);
-    NnDev dW, ws, vox;
-    HIP_TRY(dW.alloc(n_weights * sizeof(double)));
-    if (ws_bytes) HIP_TRY(ws.alloc(ws_bytes));
-    HIP_TRY(vox.alloc(n * sizeof(float)));
+    DevBuf<double> dW, ws;
+    DevBuf<float> vox;
+    HIP_TRY(dW.grow(n_weights * sizeof(double)));
+    HIP_TRY(ws.grow(ws_bytes));
+    HIP_TRY(vox.grow(n * sizeof(float)));
     HIP_TRY(hipMemcpy(dW.p, weights, n_weights * sizeof(double), hipMemcpyHostToDevice));
-    if (int st = nn_launch(N, (const double *)dW.p, n, nullptr, nullptr, nullptr, &lat, (float *)vox.p, (double *)ws.p, nullptr)) return st;
+    if (int st = nn_launch(N, dW.p, n, nullptr, nullptr, nullptr, &lat, vox.p, ws.p, nullptr)) return st;
     HIP_TRY(hipDeviceSynchronize());
     if (voxels_out) HIP_TRY(hipMemcpy(voxels_out, vox.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    return install_mean_grid(m, which, g, (float *)vox.release());
+    return install_mean_grid(m, which, g, n, vox.release());
 }

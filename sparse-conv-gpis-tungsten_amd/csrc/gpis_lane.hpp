@@ -12,7 +12,7 @@ namespace gpis {
 // ======================================================================================
 // kernels — generic path: one lane = one ray / query, impulses generated on the fly
 // ======================================================================================
-constexpr int kBlock = 64;   // one wave per workgroup: rays are independent, small blocks balance the march
+// (kBlock, one wave per workgroup, and kPersistSlots: gpis_device.hpp)
 #ifndef GPIS_GENERIC_OCC
 #define GPIS_GENERIC_OCC 4   // waves per SIMD the lane-per-ray march kernels are register-allocated for (C2 scene S: 1 wave 11.6, 2 → 20.4, 3 → 25.2, 4 → 26.6, 5 → 26.0 Msamples/s)
 #endif
@@ -84,7 +84,6 @@ __global__ void __launch_bounds__(kBlock, GPIS_GENERIC_OCC) k_transmittance(cons
 #define GPIS_PERSIST_Q 16
 #endif
 constexpr int kPersistQ = GPIS_PERSIST_Q;
-constexpr unsigned kPersistSlots = 256;   // ring of ray counters: one per persistent launch in flight
 #ifndef GPIS_PERSIST_OCC
 #define GPIS_PERSIST_OCC 3   // waves per SIMD of the register allocation (LDS: 12.5 KB per wave -> 12 waves per CU)
 #endif

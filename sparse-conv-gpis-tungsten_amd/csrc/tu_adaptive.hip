@@ -12,7 +12,7 @@
 
 namespace gpis {
 
-int host_set_err(int code, const char *msg);      // gpis_hip.hip: the library's thread-local error text
+int set_err(int code, const char *fmt, ...);      // gpis_hip.hip: the library's thread-local error text (gpis_host_base.hpp)
 
 // ---- the host plan step.  The integrator's sampler: UniformSampler.hpp:41-53 with sequence 0.
 namespace {
@@ -137,7 +137,7 @@ extern "C" int gpis_adaptive_plan_host(const gpis_adaptive_s *a, uint32_t width,
 {
     const uint32_t vw = (width + kVarianceTile - 1) / kVarianceTile, vh = (height + kVarianceTile - 1) / kVarianceTile;
     if (!a || !rng_state || !records || width == 0 || height == 0 || pass_spp == 0 || a->threshold < 2 || n_records != (size_t)vw * vh)
-        return host_set_err(GPIS_ERR_INVALID_ARG, "gpis_adaptive_plan_host: invalid argument");
+        return set_err(GPIS_ERR_INVALID_ARG, "gpis_adaptive_plan_host: invalid argument");
     for (size_t i = 0; i < n_records; ++i)                                                              // generateWork, :109-133
         records[i].sample_index += records[i].next_sample_count;
     if (current_spp >= a->threshold) {

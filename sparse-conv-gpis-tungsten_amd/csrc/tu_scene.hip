@@ -813,21 +813,21 @@ static int lambert_chunk(gpis_medium *m, const SceneConst &sc, const LambertWs &
 {
     int rc = GPIS_OK;
     if ((rc = ensure_stage(m, 3, W.b_prim, true))) return rc;
-    char *ws3 = (char *)m->stage[3];
+    char *ws3 = (char *)m->stage[3].p;
     SceneRay *cray = (SceneRay *)(ws3 + W.o_prim);
     gpis_ray_in *prim = (gpis_ray_in *)(ws3 + W.o_prim);
     float *us = (float *)(ws3 + W.o_us);
     uint8_t *v1 = (uint8_t *)(ws3 + W.o_v1);
     if ((rc = W.compact ? camera(cray) : camera(prim, us, v1))) return rc;
     if ((rc = ensure_stage(m, 5, W.b_seg, true))) return rc;
-    SceneHit *chit = (SceneHit *)m->stage[5];
-    gpis_seg_out *seg = (gpis_seg_out *)m->stage[5];
+    SceneHit *chit = (SceneHit *)m->stage[5].p;
+    gpis_seg_out *seg = (gpis_seg_out *)m->stage[5].p;
     // k_scene_shade reads only ok / exited of a segment that exits: its lastVal and gradient are not evaluated (GPIS_OPT_SCENE_EXIT_STATE)
     if ((rc = W.compact ? scene_sample_distance_compact(m, ns, cray, chit, sc.s.cam_pos, st)
                         : sample_distance_impl(m, ns, prim, seg, nullptr, v1, st, MARCH_COHERENT, m->opt[GPIS_OPT_SCENE_EXIT_STATE] != 0)))
         return rc;
     if ((rc = ensure_stage(m, 6, W.b_shadow, true))) return rc;
-    char *ws6 = (char *)m->stage[6];
+    char *ws6 = (char *)m->stage[6].p;
     float *cosl = (float *)(ws6 + W.o_cos);
     uint8_t *v2 = (uint8_t *)(ws6 + W.o_v2), *vis = (uint8_t *)(ws6 + W.o_vis), *hit = (uint8_t *)(ws6 + W.o_hit);
     if (W.compact) {
@@ -1023,7 +1023,7 @@ static int fs_frame(gpis_medium *m, const gpis_scene_s *s, size_t rec_bytes, con
     for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
         const size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
         const size_t ns = np * s->spp_count;
-        HIP_TRY(hipMemsetAsync(m->fs_scene_next, 0, sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(m->fs_scene_next.p, 0, sizeof(uint32_t), st));
         if (int rc = march(sc, (unsigned)(ns < cap ? ns : cap), p0, (uint32_t)ns)) return rc;
         if (int rc = sum(sc, p0, np)) return rc;
     }
@@ -1038,11 +1038,11 @@ extern "C" int gpis_fs_render_scene_s(gpis_medium *m, const gpis_scene_s *s, flo
     hipStream_t st = (hipStream_t)stream;
     return fs_frame(m, s, launch::fs_scene_rec_bytes(), __func__, st,
                     [&](const SceneConst &sc, unsigned grid, size_t p0, uint32_t ns) {
-                        launch::fs_scene(grid, m->d_model, sc, p0, ns, m->fs_scene_next, m->fs_scene_recs, m->fs_ws, m->fs_slots, st);
+                        launch::fs_scene(grid, m->d_model.p, sc, p0, ns, m->fs_scene_next.p, m->fs_scene_recs.p, m->fs_ws.p, m->fs_slots, st);
                         return launch_check("k_fs_scene");
                     },
                     [&](const SceneConst &sc, size_t p0, size_t np) {
-                        launch::fs_scene_sum(sc, p0, np, m->fs_scene_recs, radiance_sum, hit_count, st);
+                        launch::fs_scene_sum(sc, p0, np, m->fs_scene_recs.p, radiance_sum, hit_count, st);
                         return launch_check("k_fs_scene_sum");
                     });
 }
@@ -1057,12 +1057,12 @@ extern "C" int gpis_fs_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *
     hipStream_t st = (hipStream_t)stream;
     return fs_frame(m, s, launch::fs_paths_rec_bytes(), __func__, st,
                     [&](const SceneConst &sc, unsigned grid, size_t p0, uint32_t ns) {
-                        launch::fs_paths(grid, m->d_model, sc, p0, ns, max_path_bounces, albedo, m->fs_scene_next, m->fs_scene_recs, m->fs_ws, m->fs_slots,
+                        launch::fs_paths(grid, m->d_model.p, sc, p0, ns, max_path_bounces, albedo, m->fs_scene_next.p, m->fs_scene_recs.p, m->fs_ws.p, m->fs_slots,
                                          m->fs_slots + m->fs_ws_blocks, st);
                         return launch_check("k_fs_paths");
                     },
                     [&](const SceneConst &sc, size_t p0, size_t np) {
-                        launch::fs_paths_sum(sc, p0, np, m->fs_scene_recs, radiance_sum, seg_count, st);
+                        launch::fs_paths_sum(sc, p0, np, m->fs_scene_recs.p, radiance_sum, seg_count, st);
                         return launch_check("k_fs_paths_sum");
                     });
 }
@@ -1115,7 +1115,7 @@ static int lambert_paths_carve(gpis_medium *m, int n_marched, size_t ns_max, hip
 // the frame's arrays in stage[3], which holds W.bytes
 static PathsFrame lambert_paths_bind(gpis_medium *m, const PathsWs &W)
 {
-    char *ws = (char *)m->stage[3];
+    char *ws = (char *)m->stage[3].p;
     PathsFrame f;
     f.ws = ws;
     f.rays = (gpis_ray_in *)(ws + W.o_rays); f.seg = (gpis_seg_out *)(ws + W.o_seg); f.shadow = (gpis_ray_in *)(ws + W.o_sh);
@@ -1149,7 +1149,7 @@ static int lambert_paths_chunk(gpis_medium *m, const PathsWs &W, const PathsFram
         const int hint = bounce > 0 ? MARCH_SCATTERED : MARCH_COHERENT;
         // src rays + mask -> order, regrouped copy, live flags of the regrouped slots
         auto regroup_batch = [&](const gpis_ray_in *src, const uint8_t *mask, uint32_t *ord, gpis_ray_in *dst, uint8_t *live_out) -> int {
-            k_paths_keys<<<grid_of(ns, 256), 256, 0, st>>>(m->d_model, cell_size, ns, src, mask, keys, vals);
+            k_paths_keys<<<grid_of(ns, 256), 256, 0, st>>>(m->d_model.p, cell_size, ns, src, mask, keys, vals);
             int r = launch_check("k_paths_keys");
             if (r) return r;
             size_t tb = sort_temp_bytes;
@@ -1281,7 +1281,7 @@ extern "C" int gpis_render_scene_s_paths_rgb(gpis_medium *m, const gpis_scene_s 
             return launch_check("k_paths_rgb_begin");
         },
         [&](int bounce, size_t ns, const uint32_t *order, const gpis_ray_in *rays_in, const uint8_t *live) {
-            k_paths_rgb_shade<0><<<grid_of(ns, 256), 256, 0, st>>>(m->d_model, sc, ns, bounce, max_path_bounces, emissive ? 1 : 0, albedo[0], albedo[1],
+            k_paths_rgb_shade<0><<<grid_of(ns, 256), 256, 0, st>>>(m->d_model.p, sc, ns, bounce, max_path_bounces, emissive ? 1 : 0, albedo[0], albedo[1],
                                                                    albedo[2], a, order, rays_in, live);
             return launch_check("k_paths_rgb_shade");
         },
@@ -1345,7 +1345,7 @@ extern "C" int gpis_render_scene_s_paths_rgb_adaptive(gpis_medium *m, const gpis
                     return launch_check("k_paths_rgb_begin");
                 },
                 [&](int bounce, size_t n, const uint32_t *order, const gpis_ray_in *rays_in, const uint8_t *live) {
-                    k_paths_rgb_shade<0><<<grid_of(n, 256), 256, 0, st>>>(m->d_model, sc, n, bounce, max_path_bounces, emissive ? 1 : 0, albedo[0], albedo[1],
+                    k_paths_rgb_shade<0><<<grid_of(n, 256), 256, 0, st>>>(m->d_model.p, sc, n, bounce, max_path_bounces, emissive ? 1 : 0, albedo[0], albedo[1],
                                                                           albedo[2], arr, order, rays_in, live);
                     return launch_check("k_paths_rgb_shade");
                 },
@@ -1402,7 +1402,7 @@ static int nee_frames(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_
         if (l <= 20) return set_err(GPIS_ERR_DEVICE, "NEE driver: no memory for a 1 Mi-sample workspace");
     }
     if ((rc = ws_acquire(m, 0, st))) return rc;
-    char *ws = (char *)m->stage[3];
+    char *ws = (char *)m->stage[3].p;
     a.rays = (gpis_ray_in *)(ws + o_rays); a.seg = (gpis_seg_out *)(ws + o_seg); a.shadow = nullptr;
     a.rng = (uint64_t *)(ws + o_rng); a.throughput = (float *)(ws + o_thr); a.emission = (float *)(ws + o_em); a.contrib = nullptr;
     a.alive = (uint8_t *)(ws + o_alive); a.nee = nullptr; a.vis = nullptr;
@@ -1416,9 +1416,9 @@ static int nee_frames(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_
     // the light and the phase estimator of the hits of one march: neePDF / neeGrad between set-up and shade, then the shadow marches
     auto nee_queries = [&](size_t ns) -> int {
         ProfScope prof(m, 2, st);
-        launch::nee(nee_instance(m->host_model), m->d_model, ns, b.q_half, b.pdf_half, b.grad_half, m->d_counters, b.want_light, st);
+        launch::nee(nee_instance(m->host_model), m->d_model.p, ns, b.q_half, b.pdf_half, b.grad_half, m->d_counters.p, b.want_light, st);
         if (int r = launch_check("k_nee")) return r;
-        launch::nee(nee_instance(m->host_model), m->d_model, ns, b.q_normal, b.pdf_normal, nullptr, m->d_counters, b.want_pdf_normal, st);
+        launch::nee(nee_instance(m->host_model), m->d_model.p, ns, b.q_normal, b.pdf_normal, nullptr, m->d_counters.p, b.want_pdf_normal, st);
         return launch_check("k_nee");
     };
     auto shadow_marches = [&](size_t ns, int hint) -> int {

@@ -20,33 +20,33 @@ namespace {
 // the refusals of the built scope (include/gpis.h); no device needed
 int ws_validate(const gpis_params &P, const gpis_ws_params &S)
 {
-    if (P.abi_version != GPIS_ABI_VERSION) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: abi_version %u != %d", P.abi_version, GPIS_ABI_VERSION);
-    if (S.version != GPIS_WS_PARAMS_VERSION) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: gpis_ws_params.version %u != %d", S.version, GPIS_WS_PARAMS_VERSION);
+    if (P.abi_version != GPIS_ABI_VERSION) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: abi_version %u != %d", P.abi_version, GPIS_ABI_VERSION);
+    if (S.version != GPIS_WS_PARAMS_VERSION) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: gpis_ws_params.version %u != %d", S.version, GPIS_WS_PARAMS_VERSION);
     if (P.correlation_context < GPIS_CTX_GLOBAL || P.correlation_context > GPIS_CTX_NONE)
-        return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: correlation_context %d", P.correlation_context);
+        return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: correlation_context %d", P.correlation_context);
     if (S.basis_functions < 0 || S.basis_functions > GPIS_WS_MAX_BASIS)
-        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: basis_functions %d outside 0..%d", S.basis_functions, GPIS_WS_MAX_BASIS);
+        return set_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: basis_functions %d outside 0..%d", S.basis_functions, GPIS_WS_MAX_BASIS);
     if (!(P.step_size > 0.f))
-        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: step_size %g: only the ray march (step_size > 0) is built, not the affine-arithmetic "
+        return set_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: step_size %g: only the ray march (step_size > 0) is built, not the affine-arithmetic "
                                             "sphere trace of step_size == 0 (WSM:186-235)", (double)P.step_size);
     if (P.kernel_type != GPIS_KERNEL_SQUARED_EXPONENTIAL || P.nonstationary || P.grid_nonstationary)
-        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: only the stationary squared-exponential covariance is built: the spectral samplers of "
+        return set_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: only the stationary squared-exponential covariance is built: the spectral samplers of "
                                             "the other kernels and of the non-stationary wrappers draw from std::mt19937 / std::gamma_distribution");
     if (S.normal_method == GPIS_NORMAL_BECKMANN || S.normal_method == GPIS_NORMAL_GGX)
-        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: normal_method beckmann / ggx is outside the built scope");
+        return set_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: normal_method beckmann / ggx is outside the built scope");
     if (S.normal_method != GPIS_NORMAL_CONDITIONED_GAUSSIAN && S.normal_method != GPIS_NORMAL_FINITE_DIFFERENCES)
-        return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: normal_method %d", S.normal_method);
+        return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: normal_method %d", S.normal_method);
     if (S.intersect_method == GPIS_INTERSECT_MEAN)
-        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: intersect_method mean is outside the built scope");
+        return set_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: intersect_method mean is outside the built scope");
     if (S.intersect_method != GPIS_INTERSECT_GP_DISCRETE)
-        return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: intersect_method %d", S.intersect_method);
+        return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: intersect_method %d", S.intersect_method);
     if (P.mean_color.enabled && P.mean_color.type >= GPIS_NOISE_SANDSTONE)
-        return ws_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: a sandstone / rust mean colour is outside the built scope (ramp colours only)");
+        return set_err(GPIS_ERR_UNSUPPORTED, "gpis_ws_create: a sandstone / rust mean colour is outside the built scope (ramp colours only)");
     for (int w = 0; w < 1 + (P.has_mean_additional ? 1 : 0); ++w) {
         const int t = w ? P.mean_additional.type : P.mean.type;
-        if (t == GPIS_MEAN_TABULATED) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: a tabulated (voxel grid) mean is outside the built scope of the weight-space medium");
-        if (t == GPIS_MEAN_PROCEDURAL) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: a procedural (SDF) mean is outside the built scope of the weight-space medium");
-        if (t < GPIS_MEAN_HOMOGENEOUS || t > GPIS_MEAN_LINEAR) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: mean type %d", t);
+        if (t == GPIS_MEAN_TABULATED) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: a tabulated (voxel grid) mean is outside the built scope of the weight-space medium");
+        if (t == GPIS_MEAN_PROCEDURAL) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: a procedural (SDF) mean is outside the built scope of the weight-space medium");
+        if (t < GPIS_MEAN_HOMOGENEOUS || t > GPIS_MEAN_LINEAR) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: mean type %d", t);
     }
     return GPIS_OK;
 }
@@ -54,30 +54,25 @@ int ws_validate(const gpis_params &P, const gpis_ws_params &S)
 int march(WsHandle *h, bool want_sample, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, uint8_t *visible, hipStream_t s)
 {
     if (n == 0) return GPIS_OK;
-    WS_HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipSetDevice(h->device));
     const unsigned grid = (unsigned)(n < h->grid_cap ? n : h->grid_cap);
     if (int st = ws_ensure_work(h, grid)) return st;
     if (want_sample)
-        k_ws_march<true><<<grid, 64, 0, s>>>(h->d_model, n, rays, out, nullptr, h->d_work, h->d_counters);
+        k_ws_march<true><<<grid, 64, 0, s>>>(h->d_model.p, n, rays, out, nullptr, h->d_work.p, h->d_counters.p);
     else
-        k_ws_march<false><<<grid, 64, 0, s>>>(h->d_model, n, rays, nullptr, visible, h->d_work, h->d_counters);
-    if (int st = ws_launch_check("k_ws_march")) return st;
+        k_ws_march<false><<<grid, 64, 0, s>>>(h->d_model.p, n, rays, nullptr, visible, h->d_work.p, h->d_counters.p);
+    if (int st = launch_check("k_ws_march")) return st;
     return ws_check_overflow(h, s);
 }
 
+// the host-pointer form: results are copied back also when the march refused them as GPIS_ERR_UNSUPPORTED (ws_check_overflow)
 int march_host(WsHandle *h, bool want_sample, size_t n, const gpis_ray_in *rays, void *out)
 {
     if (n == 0) return GPIS_OK;
-    WS_HIP_TRY(hipSetDevice(h->device));
-    const size_t rec = want_sample ? sizeof(gpis_seg_out) : 1;
-    if (int st = ws_stage(h, 0, n * sizeof(gpis_ray_in))) return st;
-    if (int st = ws_stage(h, 1, n * rec)) return st;
-    WS_HIP_TRY(hipMemcpy(h->stage[0], rays, n * sizeof(gpis_ray_in), hipMemcpyHostToDevice));
-    const int st = march(h, want_sample, n, (const gpis_ray_in *)h->stage[0], want_sample ? (gpis_seg_out *)h->stage[1] : nullptr,
-                         want_sample ? nullptr : (uint8_t *)h->stage[1], nullptr);
-    if (st && st != GPIS_ERR_UNSUPPORTED) return st;
-    WS_HIP_TRY(hipMemcpy(out, h->stage[1], n * rec, hipMemcpyDeviceToHost));
-    return st;
+    return host_round_trip(h->mu, h->device, h->stage, GrowStage{h->stage}, {{rays, nullptr, n * sizeof(gpis_ray_in), 0}, {nullptr, out, n * (want_sample ? sizeof(gpis_seg_out) : 1), 1}},
+                           [&] { return march(h, want_sample, n, (const gpis_ray_in *)h->stage[0].p, want_sample ? (gpis_seg_out *)h->stage[1].p : nullptr,
+                                              want_sample ? nullptr : (uint8_t *)h->stage[1].p, nullptr); },
+                           kTripNoSync | kTripKeepUnsupported);
 }
 
 }   // namespace
@@ -89,13 +84,6 @@ int ws_destroy(gpis_medium *m)
     if (!h) return GPIS_OK;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    if (h->d_model) (void)hipFree(h->d_model);
-    if (h->d_counters) (void)hipFree(h->d_counters);
-    if (h->d_basis) (void)hipFree(h->d_basis);
-    if (h->d_work) (void)hipFree(h->d_work);
-    if (h->d_scene_next) (void)hipFree(h->d_scene_next);
-    for (int k = 0; k < 3; ++k)
-        if (h->stage[k]) (void)hipFree(h->stage[k]);
     h->tag = 0;
     delete h;
     return GPIS_OK;
@@ -113,21 +101,21 @@ extern "C" void gpis_ws_default_params(gpis_ws_params *p)
 
 extern "C" int gpis_ws_create(const gpis_params *params, const gpis_ws_params *ws, int device, gpis_medium **out)
 {
-    if (!params || !ws || !out) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: null argument");
+    if (!params || !ws || !out) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: null argument");
     *out = nullptr;
     if (int st = ws_validate(*params, *ws)) return st;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return ws_err(GPIS_ERR_NO_DEVICE, "gpis_ws_create: no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= count) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: device %d of %d", device, count);
-    WS_HIP_TRY(hipSetDevice(device));
+        return set_err(GPIS_ERR_NO_DEVICE, "gpis_ws_create: no HIP device visible (this library has no CPU fallback)");
+    if (device < 0 || device >= count) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_create: device %d of %d", device, count);
+    HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
-    WS_HIP_TRY(hipGetDeviceProperties(&prop, device));
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (!strstr(prop.gcnArchName, "gfx950"))
-        return ws_err(GPIS_ERR_NO_DEVICE, "gpis_ws_create: device %d is %s, this library is built for gfx950 only", device, prop.gcnArchName);
+        return set_err(GPIS_ERR_NO_DEVICE, "gpis_ws_create: device %d is %s, this library is built for gfx950 only", device, prop.gcnArchName);
 
     WsHandle *h = new (std::nothrow) WsHandle();
-    if (!h) return ws_err(GPIS_ERR_DEVICE, "out of host memory");
+    if (!h) return set_err(GPIS_ERR_DEVICE, "out of host memory");
     h->device = device;
     h->params = *params;
     h->wsp = *ws;
@@ -145,21 +133,23 @@ extern "C" int gpis_ws_create(const gpis_params *params, const gpis_ws_params *w
     W.sqrt2n = W.n > 0 ? std::sqrt(2. / W.n) : 0.;
     W.basis = nullptr;
     int st = GPIS_OK;
-    auto fail = [&](int code) { gpis::ws_destroy(reinterpret_cast<gpis_medium *>(h)); return code; };
-    if (hipMalloc(&h->d_model, sizeof(WsModel)) != hipSuccess || hipMalloc(&h->d_counters, sizeof(WsCounters)) != hipSuccess ||
-        hipMemset(h->d_counters, 0, sizeof(WsCounters)) != hipSuccess)
-        return fail(ws_err(GPIS_ERR_DEVICE, "gpis_ws_create: device allocation failed"));
+    // after the error text is set.  Nothing of this handle can still run on the device: its one launch (k_ws_basis) either failed
+    // to launch or was waited for by the hipDeviceSynchronize whose failure brings us here, and hipFree waits in any case
+    auto fail = [&](int code) { delete h; return code; };
+    if (h->d_model.grow(sizeof(WsModel)) != hipSuccess || h->d_counters.grow(sizeof(WsCounters)) != hipSuccess ||
+        hipMemset(h->d_counters.p, 0, sizeof(WsCounters)) != hipSuccess)
+        return fail(set_err(GPIS_ERR_DEVICE, "gpis_ws_create: device allocation failed"));
     if (W.single && W.n > 0) {
-        if (hipMalloc(&h->d_basis, 6 * (size_t)W.n * sizeof(double)) != hipSuccess)
-            return fail(ws_err(GPIS_ERR_DEVICE, "gpis_ws_create: device allocation failed"));
-        W.basis = h->d_basis;
+        if (h->d_basis.grow(6 * (size_t)W.n * sizeof(double)) != hipSuccess)
+            return fail(set_err(GPIS_ERR_DEVICE, "gpis_ws_create: device allocation failed"));
+        W.basis = h->d_basis.p;
     }
-    if (hipMemcpy(h->d_model, &W, sizeof W, hipMemcpyHostToDevice) != hipSuccess)
-        return fail(ws_err(GPIS_ERR_DEVICE, "gpis_ws_create: upload failed"));
+    if (hipMemcpy(h->d_model.p, &W, sizeof W, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(set_err(GPIS_ERR_DEVICE, "gpis_ws_create: upload failed"));
     if (W.single && W.n > 0) {
-        k_ws_basis<0><<<(W.n + 255) / 256, 256>>>(h->d_model, 1, nullptr, h->d_basis, 0);     // pss (0,0,0,0)
-        if ((st = ws_launch_check("k_ws_basis"))) return fail(st);
-        if (hipDeviceSynchronize() != hipSuccess) return fail(ws_err(GPIS_ERR_DEVICE, "gpis_ws_create: basis build failed"));
+        k_ws_basis<0><<<(W.n + 255) / 256, 256>>>(h->d_model.p, 1, nullptr, h->d_basis.p, 0);     // pss (0,0,0,0)
+        if ((st = launch_check("k_ws_basis"))) return fail(st);
+        if (hipDeviceSynchronize() != hipSuccess) return fail(set_err(GPIS_ERR_DEVICE, "gpis_ws_create: basis build failed"));
     }
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ws_march<true>, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 8;
@@ -171,63 +161,61 @@ extern "C" int gpis_ws_create(const gpis_params *params, const gpis_ws_params *w
 extern "C" int gpis_ws_sample_distance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out, void *stream)
 {
     WS_HANDLE(m);
-    if (n && (!rays || !out)) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_sample_distance_batch: null pointer");
+    if (n && (!rays || !out)) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_sample_distance_batch: null pointer");
     std::lock_guard<std::mutex> lock(h->mu);
     return march(h, true, n, rays, out, nullptr, (hipStream_t)stream);
 }
 extern "C" int gpis_ws_transmittance_batch(gpis_medium *m, size_t n, const gpis_ray_in *rays, uint8_t *visible, void *stream)
 {
     WS_HANDLE(m);
-    if (n && (!rays || !visible)) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_transmittance_batch: null pointer");
+    if (n && (!rays || !visible)) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_transmittance_batch: null pointer");
     std::lock_guard<std::mutex> lock(h->mu);
     return march(h, false, n, rays, nullptr, visible, (hipStream_t)stream);
 }
 extern "C" int gpis_ws_sample_distance_host(gpis_medium *m, size_t n, const gpis_ray_in *rays, gpis_seg_out *out)
 {
     WS_HANDLE(m);
-    if (n && (!rays || !out)) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_sample_distance_host: null pointer");
-    std::lock_guard<std::mutex> lock(h->mu);
+    if (n && (!rays || !out)) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_sample_distance_host: null pointer");
     return march_host(h, true, n, rays, out);
 }
 extern "C" int gpis_ws_transmittance_host(gpis_medium *m, size_t n, const gpis_ray_in *rays, uint8_t *visible)
 {
     WS_HANDLE(m);
-    if (n && (!rays || !visible)) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_transmittance_host: null pointer");
-    std::lock_guard<std::mutex> lock(h->mu);
+    if (n && (!rays || !visible)) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_transmittance_host: null pointer");
     return march_host(h, false, n, rays, visible);
 }
 extern "C" int gpis_ws_eval_batch(gpis_medium *m, size_t n, const gpis_ws_query *q, double *value, double *grad3, int32_t *gp_id, void *stream)
 {
     WS_HANDLE(m);
-    if (n && !q) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_eval_batch: null pointer");
+    if (n && !q) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_eval_batch: null pointer");
     if (n == 0) return GPIS_OK;
     std::lock_guard<std::mutex> lock(h->mu);
-    WS_HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipSetDevice(h->device));
     const unsigned grid = (unsigned)(n < h->grid_cap ? n : h->grid_cap);
     if (int st = ws_ensure_work(h, grid)) return st;
-    k_ws_eval<0><<<grid, 64, 0, (hipStream_t)stream>>>(h->d_model, n, q, value, grad3, gp_id, h->d_work, h->d_counters);
-    if (int st = ws_launch_check("k_ws_eval")) return st;
+    k_ws_eval<0><<<grid, 64, 0, (hipStream_t)stream>>>(h->d_model.p, n, q, value, grad3, gp_id, h->d_work.p, h->d_counters.p);
+    if (int st = launch_check("k_ws_eval")) return st;
     return ws_check_overflow(h, (hipStream_t)stream);
 }
 extern "C" int gpis_ws_basis_batch(gpis_medium *m, size_t n, const uint32_t *pss4, double *out, void *stream)
 {
     WS_HANDLE(m);
-    if (n && (!pss4 || !out)) return ws_err(GPIS_ERR_INVALID_ARG, "gpis_ws_basis_batch: null pointer");
+    if (n && (!pss4 || !out)) return set_err(GPIS_ERR_INVALID_ARG, "gpis_ws_basis_batch: null pointer");
     const size_t total = n * (size_t)h->host.n;
     if (total == 0) return GPIS_OK;
-    WS_HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipSetDevice(h->device));
     const size_t blocks = (total + 255) / 256;
-    k_ws_basis<0><<<(unsigned)(blocks < 65536 ? blocks : 65536), 256, 0, (hipStream_t)stream>>>(h->d_model, n, pss4, out, 1);
-    return ws_launch_check("k_ws_basis");
+    k_ws_basis<0><<<(unsigned)(blocks < 65536 ? blocks : 65536), 256, 0, (hipStream_t)stream>>>(h->d_model.p, n, pss4, out, 1);
+    return launch_check("k_ws_basis");
 }
 extern "C" int gpis_ws_get_counters(gpis_medium *m, uint64_t *n_eval, uint64_t *n_spec, uint64_t *n_seg)
 {
     WS_HANDLE(m);
     std::lock_guard<std::mutex> lock(h->mu);
-    WS_HIP_TRY(hipSetDevice(h->device));
-    WS_HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());
     WsCounters c;
-    WS_HIP_TRY(hipMemcpy(&c, h->d_counters, sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&c, h->d_counters.p, sizeof c, hipMemcpyDeviceToHost));
     if (n_eval) *n_eval = c.n_eval;
     if (n_spec) *n_spec = c.n_spec;
     if (n_seg) *n_seg = c.n_seg;
@@ -237,8 +225,8 @@ extern "C" int gpis_ws_reset_counters(gpis_medium *m)
 {
     WS_HANDLE(m);
     std::lock_guard<std::mutex> lock(h->mu);
-    WS_HIP_TRY(hipSetDevice(h->device));
-    WS_HIP_TRY(hipDeviceSynchronize());
-    WS_HIP_TRY(hipMemset(h->d_counters, 0, sizeof(WsCounters)));
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(h->d_counters.p, 0, sizeof(WsCounters)));
     return GPIS_OK;
 }

@@ -68,7 +68,7 @@ def main():
     d_in = torch.from_numpy(rays_all.view(np.uint8).reshape(-1).copy()).cuda()
     d_out = torch.zeros(nmax * pkg.SEG_OUT.itemsize, dtype=torch.uint8, device="cuda")
     res = {"config": args.config, "guide": args.guide, "unit": "segments/s (sampleDistance)", "rows": []}
-    sizes = [1, 16, 64, 1024, 16384, 65536, 1 << 18, nmax]
+    sizes = [1, 16, 64, 1024, 4096, 16384, 65536, 1 << 18, nmax]
     for n in [s for s in sizes if s <= nmax]:
         reps = max(2, min(200, (1 << 18) // n))
         row = {"n": n}
