@@ -1000,6 +1000,45 @@ int gpis_ws_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radianc
 int gpis_ws_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo,
                                  float *radiance_sum, void *stream);
 
+/* gpis_ws_render_scene_s and gpis_ws_render_scene_s_paths — the same estimators, sample for sample — under the sample schedule of
+ * gpis_render_scene_s_adaptive.  Weight-space handles only; s->spp_count is the AVERAGE number of samples per pixel, S.
+ * Pass loop, records, RNG: exactly those of gpis_render_scene_s_adaptive — the plan step gpis_adaptive_plan_host, the start state
+ * gpis_adaptive_rng_init_host, records zeroed at the start, record (x/4) + (y/4) * ceil(W/4), whole frames on one GPU.
+ * Sample identity: sample i of a record in a pass is the sample (x, y, k = s->spp_begin + sample_index + i) of
+ * gpis_ws_render_scene_s / gpis_ws_render_scene_s_paths: the same PCG32 seed, the same draws, the same pixelSampleSegment words
+ * (hence the same realizations and the same realization reuse inside a sample) and the same marches; the DIFFERENCE from the
+ * reference's `_currentSpp + i` is the one stated at gpis_render_scene_s_adaptive.
+ * Sample value v.  Lambert frame: v = lit ? clamp(cv * light_radiance) : 0, where cv = cos(normal, light) * (visible ? 1 : 0) and
+ * lit (a shadow segment was marched) are what gpis_ws_render_scene_s sums; the hit is ok && !exited of the primary segment.  Path
+ * driver: v = clamp(emission), the sample's sum of NEE contributions.  clamp: NaN, +-infinite and > 65536 count as 0
+ * (PathTraceIntegrator.cpp:149-156), in the image and in the statistics.
+ * Statistics: SampleRecord::addSample(float) on v over the tile's pixels row-major, clipped at the image edge, then i.  The path
+ * driver is a mono estimator: its statistic is the scalar v itself, as for the Lambert entry — NOT the luminance of a grey Vec3f
+ * (0.2126f v + 0.7152f v + 0.0722f v rounds differently).
+ * Image: per pixel and pass v is summed in i order from zero; that sum is ACCUMULATED once into radiance_sum[y*width+x], the count
+ * into sample_count and the hits into hit_count (device pointers, height*width entries; hit_count may be NULL).  While nothing is
+ * clamped a pixel equals bit for bit the sequence of uniform-driver calls over its (spp_begin, spp_count) ranges.
+ * records (device pointer, may be NULL) and info (host pointer, may be NULL) are filled as by gpis_render_scene_s_adaptive,
+ * including the closing sample_index += next_sample_count.
+ * chunk_log2: a pass runs in chunks of 2^chunk_log2 samples, one fused launch each; 0 means 2^22 (the chunk of the uniform
+ * drivers), else 8 .. 28.  Cuts fall between records, and a record larger than the chunk is a chunk of its own.  It is an
+ * argument because weight-space handles have no gpis_set_option.  No result depends on it.
+ * gpis_ws_get_counters: n_eval, n_spec and n_seg advance by exactly what the same samples cost through the uniform entries.
+ * The cos / sin argument rule above is read at each pass's synchronisation; on a hit the entry returns GPIS_ERR_UNSUPPORTED at
+ * once (what was written must not be used).
+ * GPIS_ERR_INVALID_ARG, nothing written: a handle that is not weight-space, rows other than the whole image or shard_count > 1,
+ * spp_step == 0, threshold < 2, spp_count == 0, a NULL s / a / radiance_sum / sample_count, chunk_log2 outside {0, 8 .. 28},
+ * max_path_bounces < 1.  GPIS_ERR_UNSUPPORTED: a plan that gives a record 0 or more than 2^28 / 16 samples per pixel in a pass; a
+ * chunk whose samples plus the resident grid reach 2^32 (the work counter).
+ * The entries SYNCHRONISE `stream` once per pass and return with the stream idle. */
+extern int gpis_ws_render_scene_s_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a, int chunk_log2,
+                                           float *radiance_sum, uint32_t *sample_count, uint32_t *hit_count,
+                                           gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
+extern int gpis_ws_render_scene_s_paths_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a, int chunk_log2,
+                                                 int max_path_bounces, float albedo,
+                                                 float *radiance_sum, uint32_t *sample_count,
+                                                 gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
+
 /* gpis_render_scene_s over the function-space medium: the frame of gpis_ws_render_scene_s (above) with this medium's sampler and
  * state.  Covers the rows [y_begin, y_begin+y_count), the tile-row shard (shard_index / shard_count) and the samples
  * [spp_begin, spp_begin+spp_count) that `s` selects.  Per sample (x, y, k): ONE PCG32 stream, set_state(xxhash32(x, y, k,

@@ -444,6 +444,7 @@ class GpisLib:
         "gpis_fs_render_scene_s", "gpis_fs_render_scene_s_paths",
         "gpis_default_adaptive_s", "gpis_render_scene_s_adaptive", "gpis_adaptive_plan_host", "gpis_adaptive_rng_init_host", "gpis_adaptive_record_add_host",
         "gpis_render_scene_s_paths_rgb_adaptive", "gpis_adaptive_rgb_value_host",
+        "gpis_ws_render_scene_s_adaptive", "gpis_ws_render_scene_s_paths_adaptive",
         "gpis_network_mean_host", "gpis_network_mean_batch", "gpis_bake_mean_network",
     ]
 
@@ -541,6 +542,8 @@ class GpisLib:
         L.gpis_render_scene_s_paths_rgb_adaptive.argtypes = [vp, vp, vp, i32] + [vp] * 7
         L.gpis_adaptive_rgb_value_host.argtypes = [sz, vp, vp, vp]
         L.gpis_adaptive_rgb_value_host.restype = None
+        L.gpis_ws_render_scene_s_adaptive.argtypes = [vp, vp, vp, i32] + [vp] * 6
+        L.gpis_ws_render_scene_s_paths_adaptive.argtypes = [vp, vp, vp, i32, i32, ctypes.c_float] + [vp] * 5
         L.gpis_ws_default_params.argtypes = [vp]
         L.gpis_ws_default_params.restype = None
         L.gpis_ws_create.argtypes = [vp, vp, i32, ctypes.POINTER(vp)]
@@ -1132,6 +1135,46 @@ class WeightSpaceMedium:
                                                              ctypes.c_void_p(d_rad.data_ptr()), None), "gpis_ws_render_scene_s_paths")
         torch.cuda.synchronize(dev)
         return d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy()
+
+    def _adaptive_frame(self, entry, scene, adaptive, args, want_hits, want_records, chunk_log2):
+        """the two adaptive entries into zeroed device buffers, with the return convention of Medium.render_scene_s_adaptive"""
+        import torch
+        scene = np.array(scene, dtype=SCENE_S).reshape(())
+        adaptive = np.array(default_adaptive_s() if adaptive is None else adaptive, dtype=ADAPTIVE_S).reshape(())
+        hgt, wid = int(scene["height"]), int(scene["width"])
+        vh, vw = (hgt + 3) // 4, (wid + 3) // 4
+        dev = torch.device("cuda", self.device)
+        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
+        d_cnt = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev)
+        d_hit = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_hits else None
+        d_rec = torch.zeros(max(vh * vw, 1) * ADAPTIVE_RECORD.itemsize, dtype=torch.uint8, device=dev) if want_records else None
+        info = np.zeros((), dtype=ADAPTIVE_INFO)
+        bufs = [ctypes.c_void_p(d_rad.data_ptr()), ctypes.c_void_p(d_cnt.data_ptr())]
+        if entry == "gpis_ws_render_scene_s_adaptive":
+            bufs.append(ctypes.c_void_p(d_hit.data_ptr()) if want_hits else None)
+        torch.cuda.synchronize(dev)
+        self.L.check(getattr(self.L.lib, entry)(self.h, _ptr(scene), _ptr(adaptive), int(chunk_log2), *args, *bufs,
+                                                ctypes.c_void_p(d_rec.data_ptr()) if want_records else None, _ptr(info), None), entry)
+        torch.cuda.synchronize(dev)
+        out = [d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy(), d_cnt.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()]
+        if want_hits:
+            out.append(d_hit.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy())
+        if want_records:
+            out.append(d_rec.cpu().numpy()[:vh * vw * ADAPTIVE_RECORD.itemsize].view(ADAPTIVE_RECORD).reshape(vh, vw).copy())
+        out.append(info)
+        return tuple(out)
+
+    def render_scene_s_adaptive(self, scene, adaptive=None, want_hits=False, want_records=False, chunk_log2=0):
+        """One frame of the scene-S frame driver under the reference's adaptive sample schedule (gpis_ws_render_scene_s_adaptive):
+        (radiance_sum, sample_count[, hit_count][, records], info) as Medium.render_scene_s_adaptive returns them.
+        scene["spp_count"] is the average number of samples per pixel; chunk_log2 (0: 2^22, else 8 .. 28) changes no result."""
+        return self._adaptive_frame("gpis_ws_render_scene_s_adaptive", scene, adaptive, (), want_hits, want_records, chunk_log2)
+
+    def render_scene_s_paths_adaptive(self, scene, max_bounces, albedo, adaptive=None, want_records=False, chunk_log2=0):
+        """One frame of the multi-bounce path driver under the adaptive sample schedule (gpis_ws_render_scene_s_paths_adaptive):
+        (radiance_sum, sample_count[, records], info)."""
+        return self._adaptive_frame("gpis_ws_render_scene_s_paths_adaptive", scene, adaptive, (int(max_bounces), ctypes.c_float(albedo)), False,
+                                    want_records, chunk_log2)
 
     def counters(self):
         e, s, g = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()

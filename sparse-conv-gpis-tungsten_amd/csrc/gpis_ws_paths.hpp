@@ -25,7 +25,10 @@
 // The camera step and the hit normal are gpis_scene.hpp's helpers, the counter flush is gpis_ws.hpp's.  The shade step (Duff
 // frame, wi / wo, next-event estimation, disk rejection, next-ray fill) is stated here in full, as in k_paths_shade and
 // k_fs_paths: shared as functions around the marches it made this kernel slower (gpis_scene.hpp).
+// k_ws_paths_adaptive is the same body on the variable-count sample layout of an adaptive pass (gpis_adaptive.hpp: scene_sample of an
+// AdaptiveChunk); gpis_ws_adaptive.hpp sums and accounts its records.
 #pragma once
+#include "gpis_adaptive.hpp"
 #include "gpis_scene.hpp"
 #include "gpis_ws.hpp"
 
@@ -36,10 +39,15 @@ namespace gpis {
 // one sample's emission: the sum of its NEE contributions in bounce order (0 for a sample that misses the bound)
 struct WsPathsRec { float emission; };
 
-GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_paths(const WsModel *__restrict__ Wp, SceneConst sc, size_t first_pixel, uint32_t n_samples,
-                                                                int max_bounces, float albedo, uint32_t *__restrict__ next_sample,
-                                                                WsPathsRec *__restrict__ recs, double *__restrict__ workspace,
-                                                                WsCounters *__restrict__ counters)
+// The body of the fused kernel, a template on the sample step `where` (scene_sample's second argument): size_t, the first pixel of
+// a chunk with spp_count samples per pixel (k_ws_paths), or AdaptiveChunk, the records of an adaptive pass (k_ws_paths_adaptive;
+// gpis_adaptive.hpp).  Sample i of the chunk leaves recs[i] either way; nothing else depends on the layout.  The arguments are the
+// kernels' own, by value and without a second __restrict__ (the kernels' parameters carry it): restated here it changed the register
+// allocation of k_ws_paths, which is pinned.  The one WsLds of a kernel is the body's.
+template <typename Where>
+GPIS_DEV void ws_paths_samples(const WsModel *Wp, SceneConst sc, Where where, uint32_t n_samples,
+                               int max_bounces, float albedo, uint32_t *next_sample, WsPathsRec *recs,
+                               double *workspace, WsCounters *counters)
 {
     __shared__ WsLds L;
     const WsModel &W = *Wp;
@@ -60,7 +68,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_paths(const WsModel *_
         if (i >= n_samples) break;
         // ---- k_paths_begin
         uint32_t x, y, spp;
-        Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
+        Pcg32 g = scene_sample(sc, where, i, x, y, spp);
         const float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
         const float u0 = normalized_uint(g.next_i());
         float emission = 0.f;
@@ -149,6 +157,23 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_paths(const WsModel *_
         if (lane == 0) recs[i] = WsPathsRec{emission};
     }
     ws_flush_counters(counters, tally, segs, overflow, lane);
+}
+
+GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_paths(const WsModel *__restrict__ Wp, SceneConst sc, size_t first_pixel, uint32_t n_samples,
+                                                                int max_bounces, float albedo, uint32_t *__restrict__ next_sample,
+                                                                WsPathsRec *__restrict__ recs, double *__restrict__ workspace,
+                                                                WsCounters *__restrict__ counters)
+{
+    ws_paths_samples(Wp, sc, first_pixel, n_samples, max_bounces, albedo, next_sample, recs, workspace, counters);
+}
+
+// the same samples under the adaptive schedule (gpis_ws_render_scene_s_paths_adaptive): sample i of the chunk `ch` of records
+GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_paths_adaptive(const WsModel *__restrict__ Wp, SceneConst sc, AdaptiveChunk ch, uint32_t n_samples,
+                                                                         int max_bounces, float albedo, uint32_t *__restrict__ next_sample,
+                                                                         WsPathsRec *__restrict__ recs, double *__restrict__ workspace,
+                                                                         WsCounters *__restrict__ counters)
+{
+    ws_paths_samples(Wp, sc, ch, n_samples, max_bounces, albedo, next_sample, recs, workspace, counters);
 }
 
 // one lane per pixel: sequential sum over its samples' emissions, in sample order (k_paths_accumulate's sum)

@@ -14,7 +14,10 @@
 //   dynamic work fetch — a sample costs nothing (a miss), a few batches (a hit near the chord's start) or the whole chord and
 //       a shadow march; waves take the next sample index from a global counter (one atomic per wave per sample) instead of
 //       k_ws_march's static stride, so no wave idles behind a neighbour's long samples at the end of a launch.
+// k_ws_scene_adaptive is the same body on the variable-count sample layout of an adaptive pass (gpis_adaptive.hpp: scene_sample of an
+// AdaptiveChunk); gpis_ws_adaptive.hpp sums and accounts its records.
 #pragma once
+#include "gpis_adaptive.hpp"
 #include "gpis_scene.hpp"
 #include "gpis_ws.hpp"
 
@@ -26,9 +29,15 @@ namespace gpis {
 // bit 1 = lit (a shadow segment was marched; cv takes part in the pixel's sum)
 struct WsSceneRec { float cv; uint32_t flags; };
 
-GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_scene(const WsModel *__restrict__ Wp, SceneConst sc, size_t first_pixel, uint32_t n_samples,
-                                                                uint32_t *__restrict__ next, WsSceneRec *__restrict__ recs,
-                                                                double *__restrict__ workspace, WsCounters *__restrict__ counters)
+// The body of the fused kernel, a template on the sample step `where` (scene_sample's second argument): size_t, the first pixel of
+// a chunk with spp_count samples per pixel (k_ws_scene), or AdaptiveChunk, the records of an adaptive pass (k_ws_scene_adaptive;
+// gpis_adaptive.hpp).  Sample i of the chunk leaves recs[i] either way; nothing else depends on the layout.  The arguments are the
+// kernels' own, by value and without a second __restrict__ (the kernels' parameters carry it): restated here it changed the register
+// allocation of k_ws_scene, which is pinned.  The one WsLds of a kernel is the body's.
+template <typename Where>
+GPIS_DEV void ws_scene_samples(const WsModel *Wp, SceneConst sc, Where where, uint32_t n_samples,
+                               uint32_t *next, WsSceneRec *recs, double *workspace,
+                               WsCounters *counters)
 {
     __shared__ WsLds L;
     const WsModel &W = *Wp;
@@ -47,7 +56,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_scene(const WsModel *_
         if (i >= n_samples) break;
         // ---- k_scene_primary
         uint32_t x, y, spp;
-        Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
+        Pcg32 g = scene_sample(sc, where, i, x, y, spp);
         const float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
         const float u0 = normalized_uint(g.next_i()), u1 = normalized_uint(g.next_i());
         WsSceneRec rec{0.f, 0u};
@@ -93,6 +102,21 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_scene(const WsModel *_
         if (lane == 0) recs[i] = rec;
     }
     ws_flush_counters(counters, tally, segs, overflow, lane);
+}
+
+GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_scene(const WsModel *__restrict__ Wp, SceneConst sc, size_t first_pixel, uint32_t n_samples,
+                                                                uint32_t *__restrict__ next, WsSceneRec *__restrict__ recs,
+                                                                double *__restrict__ workspace, WsCounters *__restrict__ counters)
+{
+    ws_scene_samples(Wp, sc, first_pixel, n_samples, next, recs, workspace, counters);
+}
+
+// the same samples under the adaptive schedule (gpis_ws_render_scene_s_adaptive): sample i of the chunk `ch` of records
+GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_scene_adaptive(const WsModel *__restrict__ Wp, SceneConst sc, AdaptiveChunk ch, uint32_t n_samples,
+                                                                         uint32_t *__restrict__ next, WsSceneRec *__restrict__ recs,
+                                                                         double *__restrict__ workspace, WsCounters *__restrict__ counters)
+{
+    ws_scene_samples(Wp, sc, ch, n_samples, next, recs, workspace, counters);
 }
 
 // one lane per pixel: sequential sum over its samples, in sample order (k_scene_accumulate's sum)
