@@ -150,7 +150,7 @@ typedef struct gpis_mean {
  * field says.  The "quadratic" sampler is refused; sparse VDB files are read by the loader, which hands over a dense array.
  *
  * Where such media run: either type, in either slot of the CSG pair, is served by the sparse-convolution medium (gpis_create) on
- * the lane-per-ray all-features path instance — all gpis_render_scene_s* frame drivers, both adaptive entries, the batch entry
+ * the lane-per-ray all-features path instance — all gpis_render_scene_s* frame drivers, their adaptive entries, the batch entry
  * points.  GPIS_OPT_PERSISTENT has no effect on them; there is no fast table, no wavefront and no persistent form, and
  * gpis_build_guide refuses them (GPIS_ERR_UNSUPPORTED).  The function-space entries (gpis_fs_*) refuse them with
  * GPIS_ERR_UNSUPPORTED and gpis_ws_create (the weight-space medium) with GPIS_ERR_INVALID_ARG, each with a message that names the
@@ -890,6 +890,47 @@ extern int gpis_render_scene_s_paths_rgb_adaptive(gpis_medium *m, const gpis_sce
 /* host only, test surface: the Vec3f clamp and the luminance of gpis_render_scene_s_paths_rgb_adaptive on rgb_in[3*n] — the
  * clamped values into rgb_out[3*n] and their luminances into luminance[n] (each may be NULL), by the functions the kernels call. */
 extern void gpis_adaptive_rgb_value_host(size_t n, const float *rgb_in, float *rgb_out, float *luminance);
+
+/* gpis_render_scene_s_paths and gpis_render_scene_s_nee_paths — the mono Lambert path estimator and the conductor NEE / MIS path
+ * estimator, sample for sample — under the sample schedule of gpis_render_scene_s_adaptive (PathTraceIntegrator.cpp:43-163,
+ * SampleRecord.hpp:44-65).  Sparse-convolution handles; s->spp_count is the AVERAGE number of samples per pixel, S; whole frames
+ * on one GPU.
+ * Pass loop, records, RNG: exactly those of gpis_render_scene_s_adaptive — the plan step gpis_adaptive_plan_host, the start state
+ * gpis_adaptive_rng_init_host, records zeroed at the start, record (x/4) + (y/4) * ceil(W/4); sample i of a record in a pass is
+ * k = s->spp_begin + sample_index + i, with the DIFFERENCE from the reference's `_currentSpp + i` stated there.
+ * A sample: (x, y, k) is the sample (x, y, k) of the uniform entry — its seed, draws, segment words, marches and arithmetic, see
+ * gpis_render_scene_s_paths / gpis_render_scene_s_nee_paths; its value is the scalar E that entry adds for it.
+ * Clamp (PathTraceIntegrator.cpp:149-156): an E that is NaN, +-infinite or > 65536 counts as 0, in the image and in the
+ * statistics.  The sample's segments still count in seg_count: they were marched.
+ * Statistics: SampleRecord::addSample(float) on the clamped E, in the order of gpis_render_scene_s_adaptive: the tile's pixels
+ * row-major, clipped at the image edge, then i.
+ * Image: per pixel and pass the clamped E are summed in i order from zero; that sum is ACCUMULATED once into
+ * radiance_sum[y*width+x], the count into sample_count[y*width+x] and, for the NEE entry, the segments marched (path, light shadow
+ * and phase shadow segments) into seg_count[y*width+x] (device pointers, height*width entries; seg_count may be NULL).
+ * records (device pointer, may be NULL) and info (host pointer, may be NULL) are filled as by gpis_render_scene_s_adaptive,
+ * including the closing sample_index += next_sample_count.
+ * Image, counts, records and info depend neither on how a pass is cut into chunks (GPIS_OPT_CHUNK_LOG2, default the uniform
+ * entry's: 2^25 samples for the Lambert driver, 2^27 for the NEE driver; cuts fall between records, and a record larger than a
+ * chunk is a chunk of its own) nor on any tuning option: GPIS_OPT_PATHS_SORT / PATHS_PRESORT / MARCH_FORM / PERSISTENT for the
+ * Lambert entry, MARCH_FORM / PERSISTENT for the NEE entry.
+ * GPIS_ERR_INVALID_ARG, nothing written: everything the uniform entry refuses (max_path_bounces < 1, a weight-space handle, for
+ * the NEE entry a NULL surf or cap_cos outside (-1, 1)), a NULL a / radiance_sum / sample_count, rows other than the whole image,
+ * shard_count > 1, spp_step == 0, threshold < 2, spp_count == 0.  GPIS_ERR_UNSUPPORTED: a plan that gives a record 0 or more than
+ * 2^28 samples in a pass.  GPIS_ERR_DEVICE: the device cannot hold the workspace of the smallest chunk.
+ * Consequences: with threshold >= S the schedule is uniform, and while nothing is clamped the image equals bit for bit the
+ * uniform entry called once per pass with that pass's (spp_begin, spp_count), accumulated into one buffer; at
+ * max_path_bounces = 2 on a medium whose weight[0] is exactly 1 the NEE entry under that condition equals
+ * gpis_render_scene_s_nee called the same way; max_path_bounces = 1 makes every sample zero: the first pass is rendered, then
+ * the plan step ends the frame (passes_rendered = 1, stopped_early = 1, seg_count all zero).
+ * Each entry SYNCHRONISES `stream` once per pass and returns with the stream idle. */
+extern int gpis_render_scene_s_paths_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a,
+                                              int max_path_bounces, float albedo,
+                                              float *radiance_sum, uint32_t *sample_count,
+                                              gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
+extern int gpis_render_scene_s_nee_paths_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a,
+                                                  const gpis_surface_s *surf, int max_path_bounces,
+                                                  float *radiance_sum, uint32_t *sample_count, uint32_t *seg_count,
+                                                  gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
 
 /* ---- weight-space GP medium (WeightSpaceGaussianProcessMedium.cpp, WeightSpaceGaussianProcess.cpp) --------------------
  * The field of one realization is  f(p) = sqrt(cov(p,p)) * (sqrt(2/N) * sum_i w_i cos((d_i . p) * omega_i + phi_i)) + mean(p)

@@ -445,6 +445,7 @@ class GpisLib:
         "gpis_default_adaptive_s", "gpis_render_scene_s_adaptive", "gpis_adaptive_plan_host", "gpis_adaptive_rng_init_host", "gpis_adaptive_record_add_host",
         "gpis_render_scene_s_paths_rgb_adaptive", "gpis_adaptive_rgb_value_host",
         "gpis_ws_render_scene_s_adaptive", "gpis_ws_render_scene_s_paths_adaptive",
+        "gpis_render_scene_s_paths_adaptive", "gpis_render_scene_s_nee_paths_adaptive",
         "gpis_network_mean_host", "gpis_network_mean_batch", "gpis_bake_mean_network",
     ]
 
@@ -543,6 +544,8 @@ class GpisLib:
         L.gpis_adaptive_rgb_value_host.argtypes = [sz, vp, vp, vp]
         L.gpis_adaptive_rgb_value_host.restype = None
         L.gpis_ws_render_scene_s_adaptive.argtypes = [vp, vp, vp, i32] + [vp] * 6
+        L.gpis_render_scene_s_paths_adaptive.argtypes = [vp, vp, vp, i32, ctypes.c_float] + [vp] * 5
+        L.gpis_render_scene_s_nee_paths_adaptive.argtypes = [vp, vp, vp, vp, i32] + [vp] * 6
         L.gpis_ws_render_scene_s_paths_adaptive.argtypes = [vp, vp, vp, i32, i32, ctypes.c_float] + [vp] * 5
         L.gpis_ws_default_params.argtypes = [vp]
         L.gpis_ws_default_params.restype = None
@@ -845,6 +848,51 @@ class Medium:
             out.append(d_rec.cpu().numpy()[:vh * vw * ADAPTIVE_RECORD.itemsize].view(ADAPTIVE_RECORD).reshape(vh, vw).copy())
         out.append(info)
         return tuple(out)
+
+    def _paths_adaptive_frame(self, entry, scene, adaptive, args, want_segs, want_records):
+        """the two mono path entries under the adaptive schedule into zeroed device buffers, with the return convention of
+        render_scene_s_paths_rgb_adaptive"""
+        import torch
+        scene = np.array(scene, dtype=SCENE_S).reshape(())
+        adaptive = np.array(default_adaptive_s() if adaptive is None else adaptive, dtype=ADAPTIVE_S).reshape(())
+        hgt, wid = int(scene["height"]), int(scene["width"])
+        vh, vw = (hgt + 3) // 4, (wid + 3) // 4
+        dev = torch.device("cuda", self.device)
+        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
+        d_cnt = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev)
+        d_seg = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_segs else None
+        d_rec = torch.zeros(max(vh * vw, 1) * ADAPTIVE_RECORD.itemsize, dtype=torch.uint8, device=dev) if want_records else None
+        info = np.zeros((), dtype=ADAPTIVE_INFO)
+        bufs = [ctypes.c_void_p(d_rad.data_ptr()), ctypes.c_void_p(d_cnt.data_ptr())]
+        if entry == "gpis_render_scene_s_nee_paths_adaptive":
+            bufs.append(ctypes.c_void_p(d_seg.data_ptr()) if want_segs else None)
+        torch.cuda.synchronize(dev)
+        self.L.check(getattr(self.L.lib, entry)(self.h, _ptr(scene), _ptr(adaptive), *args, *bufs,
+                                                ctypes.c_void_p(d_rec.data_ptr()) if want_records else None, _ptr(info), None), entry)
+        torch.cuda.synchronize(dev)
+        out = [d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy(), d_cnt.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()]
+        if want_segs:
+            out.append(d_seg.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy())
+        if want_records:
+            out.append(d_rec.cpu().numpy()[:vh * vw * ADAPTIVE_RECORD.itemsize].view(ADAPTIVE_RECORD).reshape(vh, vw).copy())
+        out.append(info)
+        return tuple(out)
+
+    def render_scene_s_paths_adaptive(self, scene, max_bounces, albedo, adaptive=None, want_records=False):
+        """One frame of the mono Lambert path driver under the reference's adaptive sample schedule
+        (gpis_render_scene_s_paths_adaptive) into zeroed device buffers: (radiance_sum, sample_count[, records], info) — the float32
+        sum-of-radiance image and the uint32 samples per pixel to divide it by (height, width), the ADAPTIVE_RECORD array
+        (ceil(height/4), ceil(width/4)) when asked, and the ADAPTIVE_INFO record.  scene["spp_count"] is the average number of
+        samples per pixel."""
+        return self._paths_adaptive_frame("gpis_render_scene_s_paths_adaptive", scene, adaptive, (int(max_bounces), ctypes.c_float(albedo)), False, want_records)
+
+    def render_scene_s_nee_paths_adaptive(self, scene, surface, max_bounces, adaptive=None, want_segs=False, want_records=False):
+        """One frame of the conductor NEE / MIS path driver under the reference's adaptive sample schedule
+        (gpis_render_scene_s_nee_paths_adaptive) into zeroed device buffers: (radiance_sum, sample_count[, seg_count][, records],
+        info) as render_scene_s_paths_rgb_adaptive returns them, the image (height, width); seg_count: per pixel the segments
+        marched (path, light shadow and phase shadow segments)."""
+        surface = np.array(surface, dtype=SURFACE_S).reshape(())
+        return self._paths_adaptive_frame("gpis_render_scene_s_nee_paths_adaptive", scene, adaptive, (_ptr(surface), int(max_bounces)), want_segs, want_records)
 
     def mean_color_emission(self, points):
         """(color, emission) of the mean at double-precision points (n, 3)"""

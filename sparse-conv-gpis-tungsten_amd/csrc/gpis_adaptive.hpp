@@ -1,5 +1,6 @@
 // gpis_adaptive.hpp — the variable-count sample layout and the tile statistics of the adaptive frame drivers
-// (gpis_render_scene_s_adaptive and gpis_render_scene_s_paths_rgb_adaptive in tu_scene.hip, which instantiates the kernels below;
+// (gpis_render_scene_s_adaptive, gpis_render_scene_s_paths_rgb_adaptive, gpis_render_scene_s_paths_adaptive and
+// gpis_render_scene_s_nee_paths_adaptive in tu_scene.hip, which instantiates the kernels below;
 // gpis_ws_render_scene_s_adaptive and gpis_ws_render_scene_s_paths_adaptive in tu_ws_adaptive.hip;
 // the host plan step in tu_adaptive.hip; include/gpis.h states the contract and cites the reference).
 //   host + device: SampleRecord::addSample / errorEstimate (adaptive_add_sample, adaptive_error_estimate), the sample clamp of
@@ -7,8 +8,9 @@
 //       variance tile of a record clipped at the image edge (adaptive_tile);
 //   device: scene_sample of an AdaptiveChunk — the camera step of gpis_scene.hpp's scene_sample for a pass whose records carry
 //       different sample counts.  A driver whose camera kernel is a template on that argument renders under the adaptive schedule;
-//       nothing else of its kernels changes.  Behind the bounce loops: the per-pixel sums and the tile statistics of the two
-//       adaptive drivers (the Lambert frame's on AdaptiveLambert, the RGB path driver's on its emission planes).
+//       nothing else of its kernels changes.  Behind the bounce loops: the per-pixel sums and the tile statistics of the staged
+//       adaptive drivers (the Lambert frame's on AdaptiveLambert, the RGB path driver's on its emission planes, the mono path
+//       drivers' — Lambert and conductor NEE — on their per-sample E).
 //       The fused weight-space kernels take the same step inside their work loop (k_ws_scene_adaptive, k_ws_paths_adaptive); their sums
 //       and statistics are gpis_ws_adaptive.hpp's.  The pass loop of all four drivers is gpis_adaptive_host.hpp's.
 // Layout of a pass: records in index order; record r owns the samples [offset[r], offset[r+1]) = its pixels row-major x its
@@ -203,6 +205,50 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_rgb_adaptive_accumulate(
         radiance_sum3[3 * pix + c] += acc[c];
     sample_count[pix] += rec.count;
     if (seg_count) seg_count[pix] += marched;
+}
+
+// ---- the mono path drivers (gpis_render_scene_s_paths_adaptive, gpis_render_scene_s_nee_paths_adaptive), after the bounce loop of a
+// chunk of records; `emission`: E of every sample, `segs`: the segments marched for it (NULL where the driver counts none)
+
+// one lane per pixel slot (16 per record, those past a clipped tile idle): the sequential sum over the pixel's clamped E, in sample
+// order, and the segments marched for them — a clamped sample's too
+GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_adaptive_sum(SceneConst sc, AdaptiveChunk ch, const float *__restrict__ emission,
+                                                                           const uint32_t *__restrict__ segs, float *__restrict__ radiance_sum,
+                                                                           uint32_t *__restrict__ sample_count, uint32_t *__restrict__ seg_count)
+{
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (size_t)ch.nrec * (kVarianceTile * kVarianceTile)) return;
+    const uint32_t r = ch.r0 + (uint32_t)(j / (kVarianceTile * kVarianceTile)), p = (uint32_t)(j % (kVarianceTile * kVarianceTile));
+    const AdaptiveTile t = adaptive_tile(sc.s.width, sc.s.height, r);
+    if (p >= t.w * t.h) return;
+    const AdaptivePlanRec rec = ch.plan[r];
+    const size_t first = (size_t)(rec.offset - ch.plan[ch.r0].offset) + (size_t)p * rec.count;
+    float acc = 0.f;
+    uint32_t marched = 0;
+    for (uint32_t k = 0; k < rec.count; ++k) {
+        acc += adaptive_clamp(emission[first + k]);
+        if (segs) marched += segs[first + k];
+    }
+    const size_t pix = (size_t)(t.y0 + p / t.w) * sc.s.width + (t.x0 + p % t.w);
+    radiance_sum[pix] += acc;
+    sample_count[pix] += rec.count;
+    if (segs) seg_count[pix] += marched;
+}
+
+// one lane per record: SampleRecord::addSample over the record's clamped E in the order the layout stores them (k_adaptive_stats)
+GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_adaptive_tile_stats(AdaptiveChunk ch, const float *__restrict__ emission,
+                                                                                  gpis_adaptive_record *__restrict__ records)
+{
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ch.nrec) return;
+    const uint32_t r = ch.r0 + (uint32_t)j;
+    const size_t first = (size_t)(ch.plan[r].offset - ch.plan[ch.r0].offset), n = (size_t)(ch.plan[r + 1].offset - ch.plan[r].offset);
+    gpis_adaptive_record rec = records[r];
+    for (size_t q = 0; q < n; ++q)
+        adaptive_add_sample(rec, adaptive_clamp(emission[first + q]));
+    records[r].sample_count = rec.sample_count;
+    records[r].mean = rec.mean;
+    records[r].running_variance = rec.running_variance;
 }
 
 }   // namespace gpis

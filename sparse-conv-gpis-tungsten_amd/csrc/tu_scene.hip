@@ -3,8 +3,9 @@
 // through small one-thread-per-sample kernels — defined here, in gpis_paths_rgb.hpp and in gpis_adaptive.hpp, and launched
 // directly — between the medium's march launches (gpis_launch.hpp):
 //   the Lambert frame               gpis_render_scene_s, gpis_render_scene_s_adaptive, gpis_reserve_scene_workspace
-//   the Lambert multi-bounce paths  gpis_render_scene_s_paths, gpis_render_scene_s_paths_rgb, gpis_render_scene_s_paths_rgb_adaptive
-//   the conductor NEE / MIS frames  gpis_render_scene_s_nee, gpis_render_scene_s_nee_paths
+//   the Lambert multi-bounce paths  gpis_render_scene_s_paths, gpis_render_scene_s_paths_adaptive, gpis_render_scene_s_paths_rgb,
+//                                   gpis_render_scene_s_paths_rgb_adaptive
+//   the conductor NEE / MIS frames  gpis_render_scene_s_nee, gpis_render_scene_s_nee_paths, gpis_render_scene_s_nee_paths_adaptive
 //   the function-space frames       gpis_fs_render_scene_s, gpis_fs_render_scene_s_paths (fused kernels: tu_fs_scene.hip, tu_fs_paths.hip)
 #include <hip/hip_runtime.h>
 
@@ -187,12 +188,13 @@ struct PathArrays {
     uint8_t *alive, *nee, *vis;
 };
 
-__global__ void __launch_bounds__(256) k_paths_begin(SceneConst sc, size_t first_pixel, size_t n_samples, PathArrays a)
+// The camera step: the path state of slot i.  `where` is the sample layout scene_sample takes: size_t, the first pixel of a chunk
+// with spp_count samples per pixel (k_paths_begin), or AdaptiveChunk (k_paths_adaptive_begin).
+template <typename Where>
+__device__ __forceinline__ void paths_begin_sample(const SceneConst &sc, const Where &where, size_t i, const PathArrays &a)
 {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_samples) return;
     uint32_t x, y, spp;
-    Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
+    Pcg32 g = scene_sample(sc, where, i, x, y, spp);
     float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
     float u0 = normalized_uint(g.next_i());
     gpis_ray_in r;
@@ -203,6 +205,19 @@ __global__ void __launch_bounds__(256) k_paths_begin(SceneConst sc, size_t first
     a.throughput[i] = 1.f;
     a.emission[i] = 0.f;
     a.alive[i] = hit ? 1 : 0;
+}
+__global__ void __launch_bounds__(256) k_paths_begin(SceneConst sc, size_t first_pixel, size_t n_samples, PathArrays a)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_samples) return;
+    paths_begin_sample(sc, first_pixel, i, a);
+}
+// the same step for the records of an adaptive pass (the mono path drivers under the adaptive schedule)
+__global__ void __launch_bounds__(256) k_paths_adaptive_begin(SceneConst sc, AdaptiveChunk ch, size_t n_samples, PathArrays a)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_samples) return;
+    paths_begin_sample(sc, ch, i, a);
 }
 
 // Regrouping of a bounce's segments (k_paths_keys → radix sort → k_paths_gather).  Key = Morton code of
@@ -1121,25 +1136,38 @@ static int lambert_paths_frames(gpis_medium *m, const gpis_scene_s *s, int n_mar
     return ws_release(m, 0, st);
 }
 
+namespace {
+struct PathsMonoState {                // the path state of the mono Lambert path drivers inside the frame's workspace
+    size_t o_rng = 0, o_thr = 0, o_em = 0, o_con = 0;
+    PathArrays a;
+    template <typename Carve>
+    void carve(Carve &carve, size_t ns_max)
+    {
+        o_rng = carve(ns_max * 8); o_thr = carve(ns_max * 4); o_em = carve(ns_max * 4); o_con = carve(ns_max * 4);
+    }
+    void bind(const PathsFrame &f)
+    {
+        a.rays = f.rays; a.seg = f.seg; a.shadow = f.shadow;
+        a.rng = (uint64_t *)(f.ws + o_rng);
+        a.throughput = (float *)(f.ws + o_thr); a.emission = (float *)(f.ws + o_em); a.contrib = (float *)(f.ws + o_con);
+        a.alive = f.alive; a.nee = f.nee; a.vis = f.vis;
+    }
+};
+}
 extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo, float *radiance_sum, void *stream)
 {
     CHECK_ARGS(std_handle(m) && s && radiance_sum && max_path_bounces >= 1);
     CHECK_ARGS(scene_args_ok(s));
     hipStream_t st = (hipStream_t)stream;
     const SceneConst sc = make_scene_const(s);
-    size_t o_rng = 0, o_thr = 0, o_em = 0, o_con = 0;
-    PathArrays a;
+    PathsMonoState state;
+    const PathArrays &a = state.a;
     // the segment of bounce max-1 cannot contribute (no NEE there, TraceBase.cpp:546, and the
     // light is a Dirac delta), so it is not traced
     return lambert_paths_frames(
         m, s, max_path_bounces - 1, max_path_bounces - 1, st,
-        [&](auto &carve, size_t ns_max) { o_rng = carve(ns_max * 8); o_thr = carve(ns_max * 4); o_em = carve(ns_max * 4); o_con = carve(ns_max * 4); },
-        [&](const PathsFrame &f) {
-            a.rays = f.rays; a.seg = f.seg; a.shadow = f.shadow;
-            a.rng = (uint64_t *)(f.ws + o_rng);
-            a.throughput = (float *)(f.ws + o_thr); a.emission = (float *)(f.ws + o_em); a.contrib = (float *)(f.ws + o_con);
-            a.alive = f.alive; a.nee = f.nee; a.vis = f.vis;
-        },
+        [&](auto &carve, size_t ns_max) { state.carve(carve, ns_max); },
+        [&](const PathsFrame &f) { state.bind(f); },
         [&](size_t p0, size_t ns) {
             k_paths_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, p0, ns, a);
             return launch_check("k_paths_begin");
@@ -1155,6 +1183,67 @@ extern "C" int gpis_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, 
         [&](size_t p0, size_t np) {
             k_paths_accumulate<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, a.emission, radiance_sum);
             return launch_check("k_paths_accumulate");
+        });
+}
+
+// The end of a chunk of records of the mono path drivers under the adaptive schedule: per pixel the sum of the clamped E (and of
+// `segs`, where the driver counts segments and the caller wants them), per record the tile statistics.
+static int paths_adaptive_finish(const SceneConst &sc, const AdaptiveChunk &ch, hipStream_t st, const float *emission, const uint32_t *segs, float *radiance_sum,
+                                 uint32_t *sample_count, uint32_t *seg_count, gpis_adaptive_record *d_records)
+{
+    k_paths_adaptive_sum<0><<<grid_of((size_t)ch.nrec * (kVarianceTile * kVarianceTile), 256), 256, 0, st>>>(sc, ch, emission, seg_count ? segs : nullptr, radiance_sum,
+                                                                                                          sample_count, seg_count);
+    if (int rc = launch_check("k_paths_adaptive_sum")) return rc;
+    k_paths_adaptive_tile_stats<0><<<grid_of(ch.nrec, 256), 256, 0, st>>>(ch, emission, d_records);
+    return launch_check("k_paths_adaptive_tile_stats");
+}
+
+// gpis_render_scene_s_paths under the adaptive sample schedule: the pass loop of gpis_render_scene_s_adaptive around the chunk body
+// of the Lambert path drivers, as gpis_render_scene_s_paths_rgb_adaptive below.  A chunk of records is seeded through scene_sample of
+// its AdaptiveChunk, runs the bounce loop of gpis_render_scene_s_paths, and ends with the pixel sums and the tile statistics on the
+// clamped E of every sample.
+extern "C" int gpis_render_scene_s_paths_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a, int max_path_bounces, float albedo,
+                                                  float *radiance_sum, uint32_t *sample_count, gpis_adaptive_record *records, gpis_adaptive_info *info,
+                                                  void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && a && radiance_sum && sample_count && max_path_bounces >= 1);
+    CHECK_ARGS(scene_args_ok(s));
+    hipStream_t st = (hipStream_t)stream;
+    const SceneConst sc = make_scene_const(s);
+    const int n_marched = max_path_bounces - 1;
+    PathsMonoState state;
+    const PathArrays &arr = state.a;
+    PathsWs W;
+    PathsFrame f;
+    return adaptive_passes(
+        MediumPasses{m, 25}, s, a, __func__, st, records, info,
+        [&](size_t n, bool &fits) {
+            const int rc = lambert_paths_carve(m, n_marched, n, st, [&](auto &carve, size_t ns_max) { state.carve(carve, ns_max); }, W);
+            if (rc) return rc;
+            fits = try_stage(m, 3, W.bytes);
+            return (int)GPIS_OK;
+        },
+        [&]() {
+            f = lambert_paths_bind(m, W);
+            state.bind(f);
+            return (int)GPIS_OK;
+        },
+        [&](const AdaptiveChunk &ch, size_t ns, gpis_adaptive_record *d_records) {
+            return lambert_paths_chunk(
+                m, W, f, ns, n_marched, n_marched, st,
+                [&] {
+                    k_paths_adaptive_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, ch, ns, arr);
+                    return launch_check("k_paths_adaptive_begin");
+                },
+                [&](int bounce, size_t n, const uint32_t *order, const gpis_ray_in *rays_in, const uint8_t *live) {
+                    k_paths_shade<<<grid_of(n, 256), 256, 0, st>>>(sc, n, bounce, max_path_bounces, albedo, arr, order, rays_in, live);
+                    return launch_check("k_paths_shade");
+                },
+                [&](size_t n, const uint32_t *order, const uint32_t *order2, const uint8_t *live2) {
+                    k_paths_nee_add<<<grid_of(n, 256), 256, 0, st>>>(n, arr, order, order2, live2, arr.vis);
+                    return launch_check("k_paths_nee_add");
+                },
+                [&] { return paths_adaptive_finish(sc, ch, st, arr.emission, nullptr, radiance_sum, sample_count, nullptr, d_records); });
         });
 }
 
@@ -1284,8 +1373,107 @@ extern "C" int gpis_render_scene_s_paths_rgb_adaptive(gpis_medium *m, const gpis
         });
 }
 
-// The frames of the two conductor NEE / MIS drivers.  max_path_bounces == 0: the single-interaction estimator of
-// gpis_render_scene_s_nee; otherwise the bounce loop of gpis_render_scene_s_nee_paths over the same stages.
+// The two conductor NEE / MIS drivers and the path driver's adaptive form.  max_path_bounces == 0: the single-interaction estimator
+// of gpis_render_scene_s_nee; otherwise the bounce loop of gpis_render_scene_s_nee_paths over the same stages.  The workspace layout
+// (nee_carve, nee_bind) and the body of one chunk (nee_chunk) are functions of their own, as the Lambert path drivers': the frame
+// loop of the uniform entries (nee_frames) and the pass loop of gpis_render_scene_s_nee_paths_adaptive run the same code.
+// ≈ 800 B per sample (rays, results, the two query records, two shadow rays, masks; the path driver adds 8 B).
+struct NeeWs {
+    size_t bytes;                      // of stage[3]
+    size_t o_rays, o_seg, o_rng, o_thr, o_em, o_alive, o_coeff, o_qh, o_qn, o_aux, o_shl, o_shp;
+    size_t o_ph, o_gh, o_pn, o_cl, o_cp, o_f[7], o_th, o_segs;
+    PathArrays a;
+    NeeArrays b;
+    NeePathArrays c;
+};
+// the layout of stage[3] for chunks of up to ns_max samples
+static void nee_carve(NeeWs &W, size_t ns_max, bool paths)
+{
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { return ws_carve(off, bytes); };
+    W.o_rays = carve(ns_max * sizeof(gpis_ray_in)); W.o_seg = carve(ns_max * sizeof(gpis_seg_out));
+    W.o_rng = carve(ns_max * 8); W.o_thr = carve(ns_max * 4); W.o_em = carve(ns_max * 4); W.o_alive = carve(ns_max);
+    W.o_coeff = carve(ns_max * sizeof(gpis_cond_coeff)); W.o_qh = carve(ns_max * sizeof(gpis_nee_query)); W.o_qn = carve(ns_max * sizeof(gpis_nee_query));
+    W.o_aux = carve(ns_max * sizeof(NeeAux)); W.o_shl = carve(ns_max * sizeof(gpis_ray_in)); W.o_shp = carve(ns_max * sizeof(gpis_ray_in));
+    W.o_ph = carve(ns_max * 4); W.o_gh = carve(ns_max * 12); W.o_pn = carve(ns_max * 4); W.o_cl = carve(ns_max * 4); W.o_cp = carve(ns_max * 4);
+    for (int k = 0; k < 7; ++k) W.o_f[k] = carve(ns_max);
+    W.o_th = W.o_segs = 0;
+    if (paths) { W.o_th = carve(ns_max * 4); W.o_segs = carve(ns_max * 4); }
+    W.bytes = off;
+}
+// the arrays in stage[3], which holds W.bytes
+static void nee_bind(gpis_medium *m, NeeWs &W)
+{
+    char *ws = (char *)m->stage[3].p;
+    PathArrays &a = W.a;
+    NeeArrays &b = W.b;
+    NeePathArrays &c = W.c;
+    a.rays = (gpis_ray_in *)(ws + W.o_rays); a.seg = (gpis_seg_out *)(ws + W.o_seg); a.shadow = nullptr;
+    a.rng = (uint64_t *)(ws + W.o_rng); a.throughput = (float *)(ws + W.o_thr); a.emission = (float *)(ws + W.o_em); a.contrib = nullptr;
+    a.alive = (uint8_t *)(ws + W.o_alive); a.nee = nullptr; a.vis = nullptr;
+    b.coeff = (gpis_cond_coeff *)(ws + W.o_coeff); b.q_half = (gpis_nee_query *)(ws + W.o_qh); b.q_normal = (gpis_nee_query *)(ws + W.o_qn);
+    b.aux = (NeeAux *)(ws + W.o_aux); b.shadow_light = (gpis_ray_in *)(ws + W.o_shl); b.shadow_phase = (gpis_ray_in *)(ws + W.o_shp);
+    b.pdf_half = (float *)(ws + W.o_ph); b.grad_half = (float *)(ws + W.o_gh); b.pdf_normal = (float *)(ws + W.o_pn);
+    b.contrib_light = (float *)(ws + W.o_cl); b.contrib_phase = (float *)(ws + W.o_cp);
+    b.want_light = (uint8_t *)(ws + W.o_f[0]); b.want_phase = (uint8_t *)(ws + W.o_f[1]); b.want_pdf_normal = (uint8_t *)(ws + W.o_f[2]);
+    b.go_light = (uint8_t *)(ws + W.o_f[3]); b.go_phase = (uint8_t *)(ws + W.o_f[4]); b.vis_light = (uint8_t *)(ws + W.o_f[5]); b.vis_phase = (uint8_t *)(ws + W.o_f[6]);
+    c.thr_hit = (float *)(ws + W.o_th); c.segs = (uint32_t *)(ws + W.o_segs);
+}
+// One chunk of ns samples: `begin` (the driver's camera step), the estimator of one hit or the bounce loop, `finish` (its sums).
+// Each callback launches and returns its launch_check.
+template <typename Begin, typename Finish>
+static int nee_chunk(gpis_medium *m, const SceneConst &sc, const gpis_surface_s *surf, const NeeWs &W, size_t ns, int max_path_bounces, hipStream_t st,
+                     Begin begin, Finish finish)
+{
+    const bool paths = max_path_bounces > 0;
+    const PathArrays &a = W.a;
+    const NeeArrays &b = W.b;
+    const NeePathArrays &c = W.c;
+    int rc = GPIS_OK;
+    // the light and the phase estimator of the hits of one march: neePDF / neeGrad between set-up and shade, then the shadow marches
+    auto nee_queries = [&]() -> int {
+        ProfScope prof(m, 2, st);
+        launch::nee(nee_instance(m->host_model), m->d_model.p, ns, b.q_half, b.pdf_half, b.grad_half, m->d_counters.p, b.want_light, st);
+        if (int r = launch_check("k_nee")) return r;
+        launch::nee(nee_instance(m->host_model), m->d_model.p, ns, b.q_normal, b.pdf_normal, nullptr, m->d_counters.p, b.want_pdf_normal, st);
+        return launch_check("k_nee");
+    };
+    auto shadow_marches = [&](int hint) -> int {
+        if (int r = transmittance_impl(m, ns, b.shadow_light, b.vis_light, b.go_light, st, hint)) return r;
+        return transmittance_impl(m, ns, b.shadow_phase, b.vis_phase, b.go_phase, st, hint);
+    };
+    if ((rc = begin())) return rc;
+    if (!paths) {
+        if ((rc = sample_distance_impl(m, ns, a.rays, a.seg, b.coeff, a.alive, st))) return rc;
+        k_nee_setup<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b);
+        if ((rc = launch_check("k_nee_setup"))) return rc;
+        if ((rc = nee_queries())) return rc;
+        k_nee_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b);
+        if ((rc = launch_check("k_nee_shade"))) return rc;
+        if ((rc = shadow_marches(MARCH_COHERENT))) return rc;
+        k_nee_gather<<<grid_of(ns, 256), 256, 0, st>>>(surf->cap_radiance, ns, a, b);
+        if ((rc = launch_check("k_nee_gather"))) return rc;
+    } else {
+        HIP_TRY(hipMemsetAsync(c.segs, 0, ns * sizeof(uint32_t), st));
+        // the segment of bounce max-1 cannot contribute (no direct lighting there, TraceBase.cpp:546, and the light seen directly is
+        // never added), so it is not marched.  Dead paths stay masked in sample order; the segments after the first are scattered.
+        for (int bounce = 0; bounce + 1 < max_path_bounces; ++bounce) {
+            const int hint = bounce > 0 ? MARCH_SCATTERED : MARCH_COHERENT;
+            if ((rc = sample_distance_impl(m, ns, a.rays, a.seg, b.coeff, a.alive, st, hint))) return rc;
+            k_nee_paths_setup<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b, c);
+            if ((rc = launch_check("k_nee_paths_setup"))) return rc;
+            if ((rc = nee_queries())) return rc;
+            k_nee_paths_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, bounce, max_path_bounces, a, b, c);
+            if ((rc = launch_check("k_nee_paths_shade"))) return rc;
+            if ((rc = shadow_marches(hint))) return rc;
+            k_nee_paths_gather<<<grid_of(ns, 256), 256, 0, st>>>(surf->cap_radiance, ns, a, b, c);
+            if ((rc = launch_check("k_nee_paths_gather"))) return rc;
+        }
+    }
+    return finish();
+}
+// The frames of the two uniform entries: the largest chunk the device can hold, starting from the whole frame (2^27 samples ≈ 106 GB
+// for C2's 1920x1080x64) — every launch ends in a tail of half-empty waves.
 static int nee_frames(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_s *surf, int max_path_bounces, float *radiance_sum, uint32_t *seg_count,
                       hipStream_t st)
 {
@@ -1294,94 +1482,36 @@ static int nee_frames(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_
     HIP_TRY(hipSetDevice(m->device));
     SceneConst sc = make_scene_const(s);
     const size_t total_pixels = scene_rows(*s) * s->width;
-    // ≈ 800 B per sample (rays, results, the two query records, two shadow rays, masks; the path driver adds 8 B): the largest chunk
-    // the device can hold, starting from the whole frame (2^27 samples ≈ 106 GB for C2's 1920x1080x64) — every launch ends in a tail
-    // of half-empty waves
-    PathArrays a;
-    NeeArrays b;
-    NeePathArrays c;
-    size_t chunk_pixels = 0, ns_max = 0, off = 0;
-    size_t o_rays = 0, o_seg = 0, o_rng = 0, o_thr = 0, o_em = 0, o_alive = 0, o_coeff = 0, o_qh = 0, o_qn = 0, o_aux = 0, o_shl = 0, o_shp = 0;
-    size_t o_ph = 0, o_gh = 0, o_pn = 0, o_cl = 0, o_cp = 0, o_f[7] = {0}, o_th = 0, o_segs = 0;
+    NeeWs W;
+    size_t chunk_pixels = 0;
     int rc = GPIS_OK;
     for (int l = chunk_log2(m, 27);; --l) {
         chunk_pixels = chunk_pixels_of(l, s->spp_count, total_pixels);
-        ns_max = chunk_pixels * s->spp_count;
-        off = 0;
-        auto carve = [&](size_t bytes) { return ws_carve(off, bytes); };
-        o_rays = carve(ns_max * sizeof(gpis_ray_in)); o_seg = carve(ns_max * sizeof(gpis_seg_out));
-        o_rng = carve(ns_max * 8); o_thr = carve(ns_max * 4); o_em = carve(ns_max * 4); o_alive = carve(ns_max);
-        o_coeff = carve(ns_max * sizeof(gpis_cond_coeff)); o_qh = carve(ns_max * sizeof(gpis_nee_query)); o_qn = carve(ns_max * sizeof(gpis_nee_query));
-        o_aux = carve(ns_max * sizeof(NeeAux)); o_shl = carve(ns_max * sizeof(gpis_ray_in)); o_shp = carve(ns_max * sizeof(gpis_ray_in));
-        o_ph = carve(ns_max * 4); o_gh = carve(ns_max * 12); o_pn = carve(ns_max * 4); o_cl = carve(ns_max * 4); o_cp = carve(ns_max * 4);
-        for (int k = 0; k < 7; ++k) o_f[k] = carve(ns_max);
-        if (paths) { o_th = carve(ns_max * 4); o_segs = carve(ns_max * 4); }
-        if (try_stage(m, 3, off))
+        nee_carve(W, chunk_pixels * s->spp_count, paths);
+        if (try_stage(m, 3, W.bytes))
             break;
         if (l <= 20) return set_err(GPIS_ERR_DEVICE, "NEE driver: no memory for a 1 Mi-sample workspace");
     }
     if ((rc = ws_acquire(m, 0, st))) return rc;
-    char *ws = (char *)m->stage[3].p;
-    a.rays = (gpis_ray_in *)(ws + o_rays); a.seg = (gpis_seg_out *)(ws + o_seg); a.shadow = nullptr;
-    a.rng = (uint64_t *)(ws + o_rng); a.throughput = (float *)(ws + o_thr); a.emission = (float *)(ws + o_em); a.contrib = nullptr;
-    a.alive = (uint8_t *)(ws + o_alive); a.nee = nullptr; a.vis = nullptr;
-    b.coeff = (gpis_cond_coeff *)(ws + o_coeff); b.q_half = (gpis_nee_query *)(ws + o_qh); b.q_normal = (gpis_nee_query *)(ws + o_qn);
-    b.aux = (NeeAux *)(ws + o_aux); b.shadow_light = (gpis_ray_in *)(ws + o_shl); b.shadow_phase = (gpis_ray_in *)(ws + o_shp);
-    b.pdf_half = (float *)(ws + o_ph); b.grad_half = (float *)(ws + o_gh); b.pdf_normal = (float *)(ws + o_pn);
-    b.contrib_light = (float *)(ws + o_cl); b.contrib_phase = (float *)(ws + o_cp);
-    b.want_light = (uint8_t *)(ws + o_f[0]); b.want_phase = (uint8_t *)(ws + o_f[1]); b.want_pdf_normal = (uint8_t *)(ws + o_f[2]);
-    b.go_light = (uint8_t *)(ws + o_f[3]); b.go_phase = (uint8_t *)(ws + o_f[4]); b.vis_light = (uint8_t *)(ws + o_f[5]); b.vis_phase = (uint8_t *)(ws + o_f[6]);
-    c.thr_hit = (float *)(ws + o_th); c.segs = (uint32_t *)(ws + o_segs);
-    // the light and the phase estimator of the hits of one march: neePDF / neeGrad between set-up and shade, then the shadow marches
-    auto nee_queries = [&](size_t ns) -> int {
-        ProfScope prof(m, 2, st);
-        launch::nee(nee_instance(m->host_model), m->d_model.p, ns, b.q_half, b.pdf_half, b.grad_half, m->d_counters.p, b.want_light, st);
-        if (int r = launch_check("k_nee")) return r;
-        launch::nee(nee_instance(m->host_model), m->d_model.p, ns, b.q_normal, b.pdf_normal, nullptr, m->d_counters.p, b.want_pdf_normal, st);
-        return launch_check("k_nee");
-    };
-    auto shadow_marches = [&](size_t ns, int hint) -> int {
-        if (int r = transmittance_impl(m, ns, b.shadow_light, b.vis_light, b.go_light, st, hint)) return r;
-        return transmittance_impl(m, ns, b.shadow_phase, b.vis_phase, b.go_phase, st, hint);
-    };
+    nee_bind(m, W);
     for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
         size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
         size_t ns = np * s->spp_count;
-        k_paths_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, p0, ns, a);
-        if ((rc = launch_check("k_paths_begin"))) return rc;
-        if (!paths) {
-            if ((rc = sample_distance_impl(m, ns, a.rays, a.seg, b.coeff, a.alive, st))) return rc;
-            k_nee_setup<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b);
-            if ((rc = launch_check("k_nee_setup"))) return rc;
-            if ((rc = nee_queries(ns))) return rc;
-            k_nee_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b);
-            if ((rc = launch_check("k_nee_shade"))) return rc;
-            if ((rc = shadow_marches(ns, MARCH_COHERENT))) return rc;
-            k_nee_gather<<<grid_of(ns, 256), 256, 0, st>>>(surf->cap_radiance, ns, a, b);
-            if ((rc = launch_check("k_nee_gather"))) return rc;
-        } else {
-            HIP_TRY(hipMemsetAsync(c.segs, 0, ns * sizeof(uint32_t), st));
-            // the segment of bounce max-1 cannot contribute (no direct lighting there, TraceBase.cpp:546, and the light seen directly is
-            // never added), so it is not marched.  Dead paths stay masked in sample order; the segments after the first are scattered.
-            for (int bounce = 0; bounce + 1 < max_path_bounces; ++bounce) {
-                const int hint = bounce > 0 ? MARCH_SCATTERED : MARCH_COHERENT;
-                if ((rc = sample_distance_impl(m, ns, a.rays, a.seg, b.coeff, a.alive, st, hint))) return rc;
-                k_nee_paths_setup<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b, c);
-                if ((rc = launch_check("k_nee_paths_setup"))) return rc;
-                if ((rc = nee_queries(ns))) return rc;
-                k_nee_paths_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, bounce, max_path_bounces, a, b, c);
-                if ((rc = launch_check("k_nee_paths_shade"))) return rc;
-                if ((rc = shadow_marches(ns, hint))) return rc;
-                k_nee_paths_gather<<<grid_of(ns, 256), 256, 0, st>>>(surf->cap_radiance, ns, a, b, c);
-                if ((rc = launch_check("k_nee_paths_gather"))) return rc;
-            }
-            if (seg_count) {
-                k_scene_sum_u32<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, c.segs, seg_count);
-                if ((rc = launch_check("k_scene_sum_u32"))) return rc;
-            }
-        }
-        k_paths_accumulate<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, a.emission, radiance_sum);
-        if ((rc = launch_check("k_paths_accumulate"))) return rc;
+        rc = nee_chunk(
+            m, sc, surf, W, ns, max_path_bounces, st,
+            [&] {
+                k_paths_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, p0, ns, W.a);
+                return launch_check("k_paths_begin");
+            },
+            [&] {
+                if (paths && seg_count) {
+                    k_scene_sum_u32<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, W.c.segs, seg_count);
+                    if (int r = launch_check("k_scene_sum_u32")) return r;
+                }
+                k_paths_accumulate<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, W.a.emission, radiance_sum);
+                return launch_check("k_paths_accumulate");
+            });
+        if (rc) return rc;
     }
     return ws_release(m, 0, st);
 }
@@ -1401,4 +1531,39 @@ extern "C" int gpis_render_scene_s_nee_paths(gpis_medium *m, const gpis_scene_s 
     CHECK_ARGS(scene_args_ok(s));
     CHECK_ARGS(surf->cap_cos < 1.0f && surf->cap_cos > -1.0f);
     return nee_frames(m, s, surf, max_path_bounces, radiance_sum, seg_count, (hipStream_t)stream);
+}
+
+// gpis_render_scene_s_nee_paths under the adaptive sample schedule: the pass loop of gpis_render_scene_s_adaptive around nee_chunk.
+// A chunk of records is seeded through scene_sample of its AdaptiveChunk, runs the bounce loop of gpis_render_scene_s_nee_paths, and
+// ends with the pixel sums and the tile statistics on the clamped E of every sample.
+extern "C" int gpis_render_scene_s_nee_paths_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a, const gpis_surface_s *surf,
+                                                      int max_path_bounces, float *radiance_sum, uint32_t *sample_count, uint32_t *seg_count,
+                                                      gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && a && surf && radiance_sum && sample_count && max_path_bounces >= 1);
+    CHECK_ARGS(scene_args_ok(s));
+    CHECK_ARGS(surf->cap_cos < 1.0f && surf->cap_cos > -1.0f);
+    hipStream_t st = (hipStream_t)stream;
+    const SceneConst sc = make_scene_const(s);
+    NeeWs W;
+    return adaptive_passes(
+        MediumPasses{m, 27}, s, a, __func__, st, records, info,
+        [&](size_t n, bool &fits) {
+            nee_carve(W, n, true);
+            fits = try_stage(m, 3, W.bytes);
+            return (int)GPIS_OK;
+        },
+        [&]() {
+            nee_bind(m, W);
+            return (int)GPIS_OK;
+        },
+        [&](const AdaptiveChunk &ch, size_t ns, gpis_adaptive_record *d_records) {
+            return nee_chunk(
+                m, sc, surf, W, ns, max_path_bounces, st,
+                [&] {
+                    k_paths_adaptive_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, ch, ns, W.a);
+                    return launch_check("k_paths_adaptive_begin");
+                },
+                [&] { return paths_adaptive_finish(sc, ch, st, W.a.emission, W.c.segs, radiance_sum, sample_count, seg_count, d_records); });
+        });
 }
