@@ -536,7 +536,7 @@ typedef enum gpis_option {
     GPIS_OPT_WAVE_TAIL = 1,      /* wavefront march: below this many active rays one wave finishes one ray (default 262144; 0 = never) */
     GPIS_OPT_PATHS_SORT = 2,     /* gpis_render_scene_s_paths: regroup secondary segments by lattice cell (default 1) */
     GPIS_OPT_PATHS_PRESORT = 3,  /* ... also when the wavefront march (which regroups the exact work itself) runs (default 1) */
-    GPIS_OPT_CHUNK_LOG2 = 4,     /* log2 of the tile drivers' samples per chunk (16..28; 0 = as large as the device holds) */
+    GPIS_OPT_CHUNK_LOG2 = 4,     /* log2 of the tile drivers' samples per chunk (8..28; 0 = as large as the device holds) */
     GPIS_OPT_PERSISTENT = 5,     /* per-path media: 1 (default) = persistent refilling march kernels, 0 = one ray per lane per launch */
     GPIS_OPT_SOLO_MAX = 6,       // persistent march: evaluate sideways (lane = impulse) while at most this many lanes of a wave have a
                                  //   pending evaluation; -1 (default) = derived from impulse_density
@@ -1137,6 +1137,48 @@ int gpis_fs_render_scene_s(gpis_medium *m, const gpis_scene_s *s, float *radianc
  * between them). */
 int gpis_fs_render_scene_s_paths(gpis_medium *m, const gpis_scene_s *s, int max_path_bounces, float albedo,
                                  float *radiance_sum, uint32_t *seg_count, void *stream);
+
+/* gpis_fs_render_scene_s and gpis_fs_render_scene_s_paths — the same estimators, sample for sample — under the sample schedule of
+ * gpis_render_scene_s_adaptive.  Handles as the two uniform entries; s->spp_count is the AVERAGE number of samples per pixel, S.
+ * Pass loop, records, RNG: exactly those of gpis_render_scene_s_adaptive — the plan step gpis_adaptive_plan_host, the start state
+ * gpis_adaptive_rng_init_host, records zeroed at the start, record (x/4) + (y/4) * ceil(W/4), whole frames on one GPU.
+ * Sample identity: sample i of a record in a pass is the sample (x, y, k = s->spp_begin + sample_index + i) of
+ * gpis_fs_render_scene_s / gpis_fs_render_scene_s_paths: the same single PCG32 stream set_state(xxhash32(x, y, k, scene_seed) + 1),
+ * jx, jy first and every later draw the medium's or the bounce's in program order, the same segment words and the same handling of
+ * the state — in the frame driver the shadow segment runs in place on the sample's one state, in the path driver every shadow
+ * segment runs on a copy of the path's state and the sampler is not copied.  The DIFFERENCE from the reference's
+ * `_currentSpp + i` is the one stated at gpis_render_scene_s_adaptive.
+ * Sample value v.  Lambert frame: v = lit ? clamp(cv * light_radiance) : 0, where cv = cos(normal, light) * (visible ? 1 : 0) and
+ * lit (a shadow segment was marched) are what gpis_fs_render_scene_s sums; the hit is ok && !exited of the primary segment.  Path
+ * driver: v = clamp(emission), the sample's sum of NEE contributions — the scalar, not a luminance.  clamp: NaN, +-infinite and
+ * > 65536 count as 0 (PathTraceIntegrator.cpp:149-156), in the image and in the statistics; the segments of a clamped path sample
+ * still count.
+ * Statistics: SampleRecord::addSample(float) on v over the tile's pixels row-major, clipped at the image edge, then i.
+ * Image: per pixel and pass v is summed in i order from zero; that sum is ACCUMULATED once into radiance_sum[y*width+x], the count
+ * into sample_count and the hits into hit_count / the segments marched, path plus shadow, into seg_count (device pointers,
+ * height*width entries; hit_count / seg_count may be NULL).  While nothing is clamped a pixel equals bit for bit the sequence of
+ * uniform-driver calls over its (spp_begin, spp_count) ranges.  Nothing is added atomically into the image, and no result depends
+ * on the order in which workgroups finish.
+ * max_path_bounces = 1: every sample is zero, so the first pass is rendered and the plan step ends the frame (passes_rendered = 1,
+ * stopped_early = 1); seg_count is NOT zero, since the path driver marches and counts the segment of the last bounce.
+ * records (device pointer, may be NULL) and info (host pointer, may be NULL) are filled as by gpis_render_scene_s_adaptive,
+ * including the closing sample_index += next_sample_count.
+ * A pass runs in chunks of 2^GPIS_OPT_CHUNK_LOG2 samples, one fused launch each (0 = 2^22, as the uniform entries).  Cuts fall
+ * between records, and a record larger than the chunk is a chunk of its own.  No result depends on it.
+ * GPIS_ERR_INVALID_ARG, nothing written: everything the uniform entry refuses (a weight-space handle, parameters outside the
+ * function-space scope, max_path_bounces < 1), a NULL s / a / radiance_sum / sample_count, rows other than the whole image or
+ * shard_count > 1, spp_step == 0, threshold < 2, spp_count == 0.  GPIS_ERR_UNSUPPORTED: a plan that gives a record 0 or more than
+ * 2^28 / 16 samples per pixel in a pass; a chunk whose samples plus the resident grid reach 2^32 (the work counter).
+ * The entries SYNCHRONISE `stream` once per pass and return with the stream idle.  They share the handle's function-space
+ * workspace, state slots and work counter with the uniform entries and the gpis_fs_* batch entries: launches of the SAME handle
+ * must be ordered; two adaptive calls on one handle run one after the other. */
+extern int gpis_fs_render_scene_s_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a,
+                                           float *radiance_sum, uint32_t *sample_count, uint32_t *hit_count,
+                                           gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
+extern int gpis_fs_render_scene_s_paths_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a,
+                                                 int max_path_bounces, float albedo,
+                                                 float *radiance_sum, uint32_t *sample_count, uint32_t *seg_count,
+                                                 gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
 
 #ifdef __cplusplus
 }

@@ -446,6 +446,7 @@ class GpisLib:
         "gpis_render_scene_s_paths_rgb_adaptive", "gpis_adaptive_rgb_value_host",
         "gpis_ws_render_scene_s_adaptive", "gpis_ws_render_scene_s_paths_adaptive",
         "gpis_render_scene_s_paths_adaptive", "gpis_render_scene_s_nee_paths_adaptive",
+        "gpis_fs_render_scene_s_adaptive", "gpis_fs_render_scene_s_paths_adaptive",
         "gpis_network_mean_host", "gpis_network_mean_batch", "gpis_bake_mean_network",
     ]
 
@@ -547,6 +548,8 @@ class GpisLib:
         L.gpis_render_scene_s_paths_adaptive.argtypes = [vp, vp, vp, i32, ctypes.c_float] + [vp] * 5
         L.gpis_render_scene_s_nee_paths_adaptive.argtypes = [vp, vp, vp, vp, i32] + [vp] * 6
         L.gpis_ws_render_scene_s_paths_adaptive.argtypes = [vp, vp, vp, i32, i32, ctypes.c_float] + [vp] * 5
+        L.gpis_fs_render_scene_s_adaptive.argtypes = [vp] * 9
+        L.gpis_fs_render_scene_s_paths_adaptive.argtypes = [vp, vp, vp, i32, ctypes.c_float] + [vp] * 6
         L.gpis_ws_default_params.argtypes = [vp]
         L.gpis_ws_default_params.restype = None
         L.gpis_ws_create.argtypes = [vp, vp, i32, ctypes.POINTER(vp)]
@@ -850,8 +853,8 @@ class Medium:
         return tuple(out)
 
     def _paths_adaptive_frame(self, entry, scene, adaptive, args, want_segs, want_records):
-        """the two mono path entries under the adaptive schedule into zeroed device buffers, with the return convention of
-        render_scene_s_paths_rgb_adaptive"""
+        """the mono path entries under the adaptive schedule (and the function-space frame entry, whose per-pixel count is hits)
+        into zeroed device buffers, with the return convention of render_scene_s_paths_rgb_adaptive"""
         import torch
         scene = np.array(scene, dtype=SCENE_S).reshape(())
         adaptive = np.array(default_adaptive_s() if adaptive is None else adaptive, dtype=ADAPTIVE_S).reshape(())
@@ -864,7 +867,7 @@ class Medium:
         d_rec = torch.zeros(max(vh * vw, 1) * ADAPTIVE_RECORD.itemsize, dtype=torch.uint8, device=dev) if want_records else None
         info = np.zeros((), dtype=ADAPTIVE_INFO)
         bufs = [ctypes.c_void_p(d_rad.data_ptr()), ctypes.c_void_p(d_cnt.data_ptr())]
-        if entry == "gpis_render_scene_s_nee_paths_adaptive":
+        if entry != "gpis_render_scene_s_paths_adaptive":        # the one entry without a per-pixel count beside sample_count
             bufs.append(ctypes.c_void_p(d_seg.data_ptr()) if want_segs else None)
         torch.cuda.synchronize(dev)
         self.L.check(getattr(self.L.lib, entry)(self.h, _ptr(scene), _ptr(adaptive), *args, *bufs,
@@ -893,6 +896,19 @@ class Medium:
         marched (path, light shadow and phase shadow segments)."""
         surface = np.array(surface, dtype=SURFACE_S).reshape(())
         return self._paths_adaptive_frame("gpis_render_scene_s_nee_paths_adaptive", scene, adaptive, (_ptr(surface), int(max_bounces)), want_segs, want_records)
+
+    def fs_render_scene_s_adaptive(self, scene, adaptive=None, want_hits=False, want_records=False):
+        """One frame of the function-space scene-S frame driver under the reference's adaptive sample schedule
+        (gpis_fs_render_scene_s_adaptive) into zeroed device buffers: (radiance_sum, sample_count[, hit_count][, records], info) as
+        render_scene_s_adaptive returns them."""
+        return self._paths_adaptive_frame("gpis_fs_render_scene_s_adaptive", scene, adaptive, (), want_hits, want_records)
+
+    def fs_render_scene_s_paths_adaptive(self, scene, max_bounces, albedo, adaptive=None, want_segs=False, want_records=False):
+        """One frame of the function-space multi-bounce path driver under the adaptive sample schedule
+        (gpis_fs_render_scene_s_paths_adaptive) into zeroed device buffers: (radiance_sum, sample_count[, seg_count][, records],
+        info) as render_scene_s_nee_paths_adaptive returns them; seg_count: per pixel the segments marched (path plus shadow)."""
+        return self._paths_adaptive_frame("gpis_fs_render_scene_s_paths_adaptive", scene, adaptive, (int(max_bounces), ctypes.c_float(albedo)), want_segs,
+                                          want_records)
 
     def mean_color_emission(self, points):
         """(color, emission) of the mean at double-precision points (n, 3)"""

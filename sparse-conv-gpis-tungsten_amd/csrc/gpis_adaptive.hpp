@@ -2,6 +2,7 @@
 // (gpis_render_scene_s_adaptive, gpis_render_scene_s_paths_rgb_adaptive, gpis_render_scene_s_paths_adaptive and
 // gpis_render_scene_s_nee_paths_adaptive in tu_scene.hip, which instantiates the kernels below;
 // gpis_ws_render_scene_s_adaptive and gpis_ws_render_scene_s_paths_adaptive in tu_ws_adaptive.hip;
+// gpis_fs_render_scene_s_adaptive and gpis_fs_render_scene_s_paths_adaptive in tu_fs_adaptive.hip;
 // the host plan step in tu_adaptive.hip; include/gpis.h states the contract and cites the reference).
 //   host + device: SampleRecord::addSample / errorEstimate (adaptive_add_sample, adaptive_error_estimate), the sample clamp of
 //       renderTile on a float and on a Vec3f (adaptive_clamp, adaptive_rgb_clamped), Vec3f::luminance (adaptive_luminance), the 4x4
@@ -11,8 +12,9 @@
 //       nothing else of its kernels changes.  Behind the bounce loops: the per-pixel sums and the tile statistics of the staged
 //       adaptive drivers (the Lambert frame's on AdaptiveLambert, the RGB path driver's on its emission planes, the mono path
 //       drivers' — Lambert and conductor NEE — on their per-sample E).
-//       The fused weight-space kernels take the same step inside their work loop (k_ws_scene_adaptive, k_ws_paths_adaptive); their sums
-//       and statistics are gpis_ws_adaptive.hpp's.  The pass loop of all four drivers is gpis_adaptive_host.hpp's.
+//       The fused weight-space and function-space kernels take the same step inside their work loop (k_ws_scene_adaptive,
+//       k_ws_paths_adaptive, k_fs_scene_adaptive, k_fs_paths_adaptive); their sums and statistics are gpis_adaptive_sum.hpp's on the
+//       accessors of gpis_ws_adaptive.hpp / gpis_fs_adaptive.hpp.  The pass loop of all drivers is gpis_adaptive_host.hpp's.
 // Layout of a pass: records in index order; record r owns the samples [offset[r], offset[r+1]) = its pixels row-major x its
 // next_sample_count samples, so a pixel's samples stay contiguous (what the cooperative guided evaluator lives on).
 #pragma once

@@ -2,6 +2,8 @@
 // (include/gpis.h at gpis_render_scene_s_adaptive; gpis_adaptive.hpp: the sample layout; tu_adaptive.hip: the plan step).
 // tu_scene.hip runs it on a sparse-convolution handle (gpis_render_scene_s_adaptive, gpis_render_scene_s_paths_rgb_adaptive),
 // tu_ws_adaptive.hip on a weight-space one (gpis_ws_render_scene_s_adaptive, gpis_ws_render_scene_s_paths_adaptive).
+// tu_fs_adaptive.hip runs it on the function-space side of a gpis_create handle (gpis_fs_render_scene_s_adaptive,
+// gpis_fs_render_scene_s_paths_adaptive).
 //
 // Per pass: the plan step on the host, its (offset, sample_index, count) table to the device, then chunks of whole records through
 // the driver's own stages, which end with its tile statistics into the device records; the records come back for the next plan

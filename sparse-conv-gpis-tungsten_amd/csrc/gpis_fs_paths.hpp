@@ -37,6 +37,7 @@
 // in full, the shade step as in k_ws_paths and k_paths_shade: as functions around the marches they made this kernel slower
 // (gpis_scene.hpp).  The tests pin all three against the same C (tests/native/ws_paths_shade.c, tests/native/fs_paths_shade.c).
 #pragma once
+#include "gpis_adaptive.hpp"
 #include "gpis_fs.hpp"
 #include "gpis_scene.hpp"
 
@@ -52,10 +53,15 @@ static_assert(sizeof(gpis_fs_state) % sizeof(unsigned long long) == 0 && alignof
 
 // grid = the resident set of the function-space workspace: workspace[blockIdx.x], path_slots[blockIdx.x] and
 // shadow_slots[blockIdx.x] are this workgroup's for the whole launch.
-GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_paths(const DevModel *__restrict__ Mp, SceneConst sc, size_t first_pixel, uint32_t n_samples,
-                                                                int max_bounces, float albedo, uint32_t *__restrict__ next, FsPathsRec *__restrict__ recs,
-                                                                FsGlob *__restrict__ workspace, gpis_fs_state *__restrict__ path_slots,
-                                                                gpis_fs_state *__restrict__ shadow_slots)
+// The body of the fused kernel, a template on the sample step `where` (scene_sample's second argument), as ws_paths_samples is
+// (gpis_ws_paths.hpp): size_t, the first pixel of a chunk with spp_count samples per pixel, for k_fs_paths; AdaptiveChunk, the
+// records of an adaptive pass (gpis_adaptive.hpp), for k_fs_paths_adaptive.  Sample i of the chunk leaves recs[i] either way.  The
+// arguments are the kernels' own, by value and without a second __restrict__ (the kernels' parameters carry it): k_fs_paths's
+// registers are pinned.  (k_fs_scene shares its body as included text instead, gpis_fs_scene_body.inc: the template form cost it
+// frame time, this kernel none; as included text this kernel would lose five of its accumulation registers against the pin.)
+template <typename Where>
+GPIS_DEV void fs_paths_samples(const DevModel *Mp, SceneConst sc, Where where, uint32_t n_samples, int max_bounces, float albedo, uint32_t *next,
+                               FsPathsRec *recs, FsGlob *workspace, gpis_fs_state *path_slots, gpis_fs_state *shadow_slots)
 {
     __shared__ FsLds L;
     FsGlob &G = workspace[blockIdx.x];
@@ -72,7 +78,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_paths(const DevModel *
         if (i >= n_samples) break;
         // ---- the camera step of k_fs_scene: the path's sampler gives jx, jy and is then the medium's and the bounce's
         uint32_t x, y, spp;
-        Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
+        Pcg32 g = scene_sample(sc, where, i, x, y, spp);
         const float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
         const V3 local = normalized(v3(-1.0f + ((float)x + jx) * 2.0f * sc.psx, sc.ratio - ((float)y + jy) * 2.0f * sc.psx, sc.plane_dist));
         const V3 d0 = v3(local.x, local.y, -local.z);
@@ -162,6 +168,23 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_paths(const DevModel *
         }
         if (lane == 0) recs[i] = rec;
     }
+}
+
+GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_paths(const DevModel *__restrict__ Mp, SceneConst sc, size_t first_pixel, uint32_t n_samples,
+                                                                int max_bounces, float albedo, uint32_t *__restrict__ next, FsPathsRec *__restrict__ recs,
+                                                                FsGlob *__restrict__ workspace, gpis_fs_state *__restrict__ path_slots,
+                                                                gpis_fs_state *__restrict__ shadow_slots)
+{
+    fs_paths_samples(Mp, sc, first_pixel, n_samples, max_bounces, albedo, next, recs, workspace, path_slots, shadow_slots);
+}
+
+// the same samples under the adaptive schedule (gpis_fs_render_scene_s_paths_adaptive): sample i of the chunk `ch` of records
+GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_paths_adaptive(const DevModel *__restrict__ Mp, SceneConst sc, AdaptiveChunk ch, uint32_t n_samples,
+                                                                         int max_bounces, float albedo, uint32_t *__restrict__ next,
+                                                                         FsPathsRec *__restrict__ recs, FsGlob *__restrict__ workspace,
+                                                                         gpis_fs_state *__restrict__ path_slots, gpis_fs_state *__restrict__ shadow_slots)
+{
+    fs_paths_samples(Mp, sc, ch, n_samples, max_bounces, albedo, next, recs, workspace, path_slots, shadow_slots);
 }
 
 // one lane per pixel: sequential sum over its samples' emissions, in sample order (k_paths_accumulate's sum, as k_fs_scene_sum)

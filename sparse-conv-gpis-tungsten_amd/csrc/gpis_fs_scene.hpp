@@ -18,7 +18,10 @@
 //       with fs_step_size > 0 and its shadow segment); workgroups take the next sample index from a global counter (one atomic
 //       per workgroup per sample) instead of k_fs_march's static stride.
 // The march itself is k_fs_march's: fs_sample_distance_one / fs_transmittance_one (gpis_fs.hpp), the same code for both kernels.
+// k_fs_scene_adaptive is the same body (gpis_fs_scene_body.inc) on the variable-count sample layout of an adaptive pass
+// (gpis_adaptive.hpp: scene_sample of an AdaptiveChunk); gpis_fs_adaptive.hpp sums and accounts its records.
 #pragma once
+#include "gpis_adaptive.hpp"
 #include "gpis_fs.hpp"
 #include "gpis_scene.hpp"
 
@@ -32,54 +35,26 @@ struct FsSceneRec { float cv; uint32_t flags; };
 
 // grid = the resident set of the function-space workspace (four one-wave workgroups per CU): workspace[blockIdx.x] and
 // slots[blockIdx.x] are this workgroup's for the whole launch.  Every value that steers control flow is computed identically by
-// all 64 lanes (the sample index is broadcast from lane 0), so every branch around an FS_SYNC is wave-uniform.
+// all 64 lanes (the sample index is broadcast from lane 0), so every branch around an FS_SYNC is wave-uniform.  The body is
+// gpis_fs_scene_body.inc, shared with k_fs_scene_adaptive.
 GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_scene(const DevModel *__restrict__ Mp, SceneConst sc, size_t first_pixel, uint32_t n_samples,
                                                                 uint32_t *__restrict__ next, FsSceneRec *__restrict__ recs,
                                                                 FsGlob *__restrict__ workspace, gpis_fs_state *__restrict__ slots)
 {
-    __shared__ FsLds L;
-    FsGlob &G = workspace[blockIdx.x];
-    gpis_fs_state *st = slots + blockIdx.x;
-    const DevModel &M = *Mp;
-    const gpis_scene_s &s = sc.s;
-    const int lane = (int)threadIdx.x;
-    const V3 l = v3(sc.light[0], sc.light[1], sc.light[2]);
-    for (;;) {
-        uint32_t i = 0;
-        if (lane == 0) i = atomicAdd(next, 1u);
-        i = __builtin_amdgcn_readfirstlane(i);
-        if (i >= n_samples) break;
-        // ---- k_scene_primary, with the path's sampler in place of the four per-sample draws
-        uint32_t x, y, spp;
-        Pcg32 g = scene_sample(sc, first_pixel, i, x, y, spp);
-        const float jx = normalized_uint(g.next_i()), jy = normalized_uint(g.next_i());
-        FsSceneRec rec{0.f, 0u};
-        gpis_ray_in ray;
-        if (scene_camera_ray(sc, x, y, spp, jx, jy, ray)) {
-            fs_reset_state(st, lane);            // the slot still holds the previous sample's context
-            FsState state = fs_state_of(ray);
-            FS_SYNC();
-            const gpis_seg_out r = fs_sample_distance_one(M, L, G, g, &ray, st, state, lane);
-            // ---- k_scene_shade
-            if (r.ok && !r.exited) {
-                rec.flags = 1u;
-                const float c = dot(hit_normal(r), l);
-                float s0, s1;
-                if (c > 0.f && sphere_chord(v3(r.p[0], r.p[1], r.p[2]), l, s.bound_radius, s0, s1)) {
-                    gpis_ray_in sh = scene_next_ray(ray, r);
-                    sh.dir[0] = l.x; sh.dir[1] = l.y; sh.dir[2] = l.z;
-                    sh.far_t = s1;
-                    // the shadow segment: in place on the state (context and sampler) the primary segment left
-                    FsState shadow = fs_state_of(sh);
-                    FS_SYNC();
-                    const bool vis = fs_transmittance_one(M, L, G, g, &sh, st, shadow, lane);
-                    rec.cv = c * (vis ? 1.f : 0.f);
-                    rec.flags = 3u;
-                }
-            }
-        }
-        if (lane == 0) recs[i] = rec;
-    }
+#define GPIS_FS_SAMPLE_WHERE first_pixel
+#include "gpis_fs_scene_body.inc"
+#undef GPIS_FS_SAMPLE_WHERE
+}
+
+// the same samples under the adaptive schedule (gpis_fs_render_scene_s_adaptive): sample i of the chunk `ch` of records.  The sample
+// index is wave-uniform, so the search of the chunk's offset table is scalar work.
+GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_scene_adaptive(const DevModel *__restrict__ Mp, SceneConst sc, AdaptiveChunk ch, uint32_t n_samples,
+                                                                         uint32_t *__restrict__ next, FsSceneRec *__restrict__ recs,
+                                                                         FsGlob *__restrict__ workspace, gpis_fs_state *__restrict__ slots)
+{
+#define GPIS_FS_SAMPLE_WHERE ch
+#include "gpis_fs_scene_body.inc"
+#undef GPIS_FS_SAMPLE_WHERE
 }
 
 // one lane per pixel: sequential sum over its samples, in sample order (k_scene_accumulate's sum, as k_ws_scene_sum)

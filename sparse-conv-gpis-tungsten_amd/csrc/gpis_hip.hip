@@ -877,7 +877,7 @@ extern "C" int gpis_set_option(gpis_medium *m, int option, long long value)
     case GPIS_OPT_MARCH_FORM: CHECK_ARGS(value >= GPIS_MARCH_FORM_AUTO && value <= GPIS_MARCH_FORM_WAVE); break;
     case GPIS_OPT_WAVE_TAIL: CHECK_ARGS(value >= 0); break;
     case GPIS_OPT_PATHS_SORT: case GPIS_OPT_PATHS_PRESORT: case GPIS_OPT_PERSISTENT: case GPIS_OPT_DEFER_GRAD: case GPIS_OPT_SCENE_EXIT_STATE: case GPIS_OPT_SCENE_COMPACT: case GPIS_OPT_SHADOW_LEAN: CHECK_ARGS(value == 0 || value == 1); break;
-    case GPIS_OPT_CHUNK_LOG2: CHECK_ARGS(value == 0 || (value >= 16 && value <= 28)); break;
+    case GPIS_OPT_CHUNK_LOG2: CHECK_ARGS(value == 0 || (value >= 8 && value <= 28)); break;    // below 16: chunks smaller than a record of a pass
     case GPIS_OPT_SOLO_MAX: CHECK_ARGS(value >= -1 && value <= 64); break;
     case GPIS_OPT_RANGE_LEN: CHECK_ARGS(value >= 0 && value <= (1 << 24) && value % 64 == 0); break;
     default: break;

@@ -50,7 +50,8 @@ struct gpis_medium {
     gpis::DevBuf<> stage[kStageSlots];
     std::mutex stage_mu[kStageSlots];   // guards the growth of one slot (the reserve entry does not take `mu`)
     std::mutex mu;
-    std::mutex fs_host_mu;   // serialises the function-space host entries, which own fs_stage[] end to end
+    std::mutex fs_host_mu;   // serialises the function-space host entries, which own fs_stage[] end to end, and the function-space
+                             // adaptive frame entries (tu_fs_adaptive.hip), which hold it over their passes and take `mu` inside
     gpis::DevBuf<> fs_stage[3];
     int batch_hint = GPIS_ORDER_COHERENT;   // gpis_set_batch_order: which form of the guided march the *_batch / *_host entries use
     // tuning options (gpis_set_option; defaults from the GPIS_* environment variables read ONCE in gpis_create)

@@ -18,6 +18,7 @@
 
 namespace gpis {
 struct SceneConst;
+struct AdaptiveChunk;
 struct SceneRay;
 struct SceneHit;
 
@@ -111,12 +112,17 @@ size_t fs_scene_rec_bytes();
 void fs_scene(unsigned grid, const DevModel *d_model, const SceneConst &sc, size_t first_pixel, uint32_t n_samples, uint32_t *next, void *recs,
               void *workspace, gpis_fs_state *slots, hipStream_t s);
 void fs_scene_sum(const SceneConst &sc, size_t first_pixel, size_t n_pixels, const void *recs, float *radiance_sum, uint32_t *hit_count, hipStream_t s);
+// the same fused kernel on the records of an adaptive pass (gpis_adaptive.hpp): sample i of the chunk leaves recs[i]
+void fs_scene_adaptive(unsigned grid, const DevModel *d_model, const SceneConst &sc, const AdaptiveChunk &ch, uint32_t n_samples, uint32_t *next, void *recs,
+                       void *workspace, gpis_fs_state *slots, hipStream_t s);
 // ---- multi-bounce path frame of the function-space medium (tu_fs_paths.hip): as fs_scene, with a second bank of state slots (one
 // per block) for the shadow segments' copies of the path state
 size_t fs_paths_rec_bytes();
 void fs_paths(unsigned grid, const DevModel *d_model, const SceneConst &sc, size_t first_pixel, uint32_t n_samples, int max_bounces, float albedo,
               uint32_t *next, void *recs, void *workspace, gpis_fs_state *path_slots, gpis_fs_state *shadow_slots, hipStream_t s);
 void fs_paths_sum(const SceneConst &sc, size_t first_pixel, size_t n_pixels, const void *recs, float *radiance_sum, uint32_t *seg_count, hipStream_t s);
+void fs_paths_adaptive(unsigned grid, const DevModel *d_model, const SceneConst &sc, const AdaptiveChunk &ch, uint32_t n_samples, int max_bounces, float albedo,
+                       uint32_t *next, void *recs, void *workspace, gpis_fs_state *path_slots, gpis_fs_state *shadow_slots, hipStream_t s);
 inline unsigned grid_of(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 }   // namespace launch
