@@ -622,6 +622,56 @@ def sort_pairs_u32(keys, vals, device=0, lib=None):
     return ko.cpu().numpy().view(np.uint32), vo.cpu().numpy().view(np.uint32)
 
 
+def _adaptive_s(adaptive):
+    return np.array(default_adaptive_s() if adaptive is None else adaptive, dtype=ADAPTIVE_S).reshape(())
+
+
+def _scene_frame(L, h, device, entry, scene, lead=(), channels=1, has_count=False, want_count=False, adaptive=None, want_records=False):
+    """One call of a scene-S frame entry of the C ABI into zeroed device buffers, between two synchronisations, and the results
+    copied back: the procedure of every render_scene_s* method of Medium and WeightSpaceMedium.
+    entry(h, scene[, adaptive], *lead, radiance_sum[, sample_count][, count][, records, info], stream): `lead` are the entry's own
+    arguments; `channels` is 1 or 3 (the image is (height, width) or (height, width, 3)); `has_count` says whether the entry takes a
+    per-pixel count pointer beside the image (hits or segments) and `want_count` whether the caller wants it (a null pointer where
+    not); `adaptive` is the ADAPTIVE_S record of an entry under the adaptive schedule, None for a uniform entry.
+    A uniform entry returns rad or (rad, count); an adaptive one (rad, sample_count[, count][, records], info), the ADAPTIVE_RECORD
+    array being (ceil(height/4), ceil(width/4))."""
+    import torch
+    scene = np.array(scene, dtype=SCENE_S).reshape(())
+    hgt, wid = int(scene["height"]), int(scene["width"])
+    vh, vw = (hgt + 3) // 4, (wid + 3) // 4
+    dev = torch.device("cuda", device)
+
+    def zeros(n, dtype):
+        return torch.zeros(max(n, 1), dtype=dtype, device=dev)
+
+    def per_pixel(t):
+        return t.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
+
+    d_rad = zeros(channels * hgt * wid, torch.float32)
+    d_cnt = zeros(hgt * wid, torch.int32) if adaptive is not None else None
+    want_count = bool(has_count and want_count)
+    d_aux = zeros(hgt * wid, torch.int32) if want_count else None
+    d_rec = zeros(vh * vw * ADAPTIVE_RECORD.itemsize, torch.uint8) if want_records else None
+    info = np.zeros((), dtype=ADAPTIVE_INFO)
+    args = [h, _ptr(scene)] + ([_ptr(adaptive)] if adaptive is not None else []) + list(lead) + [_ptr(d_rad.data_ptr())]
+    if adaptive is not None:
+        args.append(_ptr(d_cnt.data_ptr()))
+    if has_count:
+        args.append(_ptr(d_aux.data_ptr()) if want_count else None)
+    if adaptive is not None:
+        args += [_ptr(d_rec.data_ptr()) if want_records else None, _ptr(info)]
+    torch.cuda.synchronize(dev)
+    L.check(getattr(L.lib, entry)(*args, None), entry)
+    torch.cuda.synchronize(dev)
+    rad = d_rad.cpu().numpy()[:channels * hgt * wid].reshape((hgt, wid) if channels == 1 else (hgt, wid, channels)).copy()
+    out = [rad] + ([per_pixel(d_cnt)] if adaptive is not None else []) + ([per_pixel(d_aux)] if want_count else [])
+    if adaptive is None:
+        return tuple(out) if want_count else rad
+    if want_records:
+        out.append(d_rec.cpu().numpy()[:vh * vw * ADAPTIVE_RECORD.itemsize].view(ADAPTIVE_RECORD).reshape(vh, vw).copy())
+    return tuple(out + [info])
+
+
 class Medium:
     """gpis_medium handle + the host-pointer convenience calls (numpy in / numpy out)."""
 
@@ -711,113 +761,43 @@ class Medium:
     def fs_transmittance(self, rays, states):
         return self._fs_call("gpis_fs_transmittance_batch", rays, states, False)
 
+    # ---- the scene-S frame drivers: argument marshalling around _scene_frame, which makes the zeroed device buffers and the call
     def fs_render_scene_s(self, scene, want_hits=False):
         """One call of the function-space scene-S frame driver (gpis_fs_render_scene_s) into zeroed device buffers: the float32
         sum-of-radiance image (height, width) of the rows, shard and samples `scene` selects, and the per-pixel hit counts when
         asked."""
-        import torch
-        scene = np.array(scene, dtype=SCENE_S).reshape(())
-        hgt, wid = int(scene["height"]), int(scene["width"])
-        dev = torch.device("cuda", self.device)
-        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
-        d_hit = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_hits else None
-        torch.cuda.synchronize(dev)
-        self.L.check(self.L.lib.gpis_fs_render_scene_s(self.h, _ptr(scene), ctypes.c_void_p(d_rad.data_ptr()),
-                                                       ctypes.c_void_p(d_hit.data_ptr()) if want_hits else None, None), "gpis_fs_render_scene_s")
-        torch.cuda.synchronize(dev)
-        rad = d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy()
-        if not want_hits:
-            return rad
-        return rad, d_hit.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
+        return _scene_frame(self.L, self.h, self.device, "gpis_fs_render_scene_s", scene, has_count=True, want_count=want_hits)
 
     def fs_render_scene_s_paths(self, scene, max_bounces, albedo, want_segs=False):
         """One call of the function-space multi-bounce path driver (gpis_fs_render_scene_s_paths) into zeroed device buffers: the
         float32 sum-of-radiance image (height, width) of the rows, shard and samples `scene` selects, and per pixel the segments
         marched (path plus shadow) when asked."""
-        import torch
-        scene = np.array(scene, dtype=SCENE_S).reshape(())
-        hgt, wid = int(scene["height"]), int(scene["width"])
-        dev = torch.device("cuda", self.device)
-        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
-        d_seg = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_segs else None
-        torch.cuda.synchronize(dev)
-        self.L.check(self.L.lib.gpis_fs_render_scene_s_paths(self.h, _ptr(scene), int(max_bounces), ctypes.c_float(albedo), ctypes.c_void_p(d_rad.data_ptr()),
-                                                             ctypes.c_void_p(d_seg.data_ptr()) if want_segs else None, None), "gpis_fs_render_scene_s_paths")
-        torch.cuda.synchronize(dev)
-        rad = d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy()
-        if not want_segs:
-            return rad
-        return rad, d_seg.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
+        return _scene_frame(self.L, self.h, self.device, "gpis_fs_render_scene_s_paths", scene, (int(max_bounces), ctypes.c_float(albedo)),
+                            has_count=True, want_count=want_segs)
 
     def render_scene_s_nee_paths(self, scene, surface, max_bounces, want_segs=False):
         """One call of the multi-bounce conductor NEE / MIS path driver (gpis_render_scene_s_nee_paths) into zeroed device buffers:
         the float32 sum-of-radiance image (height, width) of the rows, shard and samples `scene` selects, and per pixel the
         segments marched (path plus light and phase shadow segments) when asked."""
-        import torch
-        scene = np.array(scene, dtype=SCENE_S).reshape(())
         surface = np.array(surface, dtype=SURFACE_S).reshape(())
-        hgt, wid = int(scene["height"]), int(scene["width"])
-        dev = torch.device("cuda", self.device)
-        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
-        d_seg = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_segs else None
-        torch.cuda.synchronize(dev)
-        self.L.check(self.L.lib.gpis_render_scene_s_nee_paths(self.h, _ptr(scene), _ptr(surface), int(max_bounces), ctypes.c_void_p(d_rad.data_ptr()),
-                                                              ctypes.c_void_p(d_seg.data_ptr()) if want_segs else None, None), "gpis_render_scene_s_nee_paths")
-        torch.cuda.synchronize(dev)
-        rad = d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy()
-        if not want_segs:
-            return rad
-        return rad, d_seg.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
+        return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_nee_paths", scene, (_ptr(surface), int(max_bounces)), has_count=True,
+                            want_count=want_segs)
 
     def render_scene_s_paths_rgb(self, scene, max_bounces, albedo, want_segs=False):
         """One call of the RGB multi-bounce path driver with the medium's emission (gpis_render_scene_s_paths_rgb) into zeroed
         device buffers: the float32 sum-of-radiance image (height, width, 3) of the rows, shard and samples `scene` selects, and
         per pixel the segments marched (path plus shadow) when asked.  A scalar `albedo` is broadcast to the three channels."""
-        import torch
-        scene = np.array(scene, dtype=SCENE_S).reshape(())
         alb = np.ascontiguousarray(np.broadcast_to(np.asarray(albedo, dtype=np.float32), (3,)))
-        hgt, wid = int(scene["height"]), int(scene["width"])
-        dev = torch.device("cuda", self.device)
-        d_rad = torch.zeros(max(3 * hgt * wid, 1), dtype=torch.float32, device=dev)
-        d_seg = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_segs else None
-        torch.cuda.synchronize(dev)
-        self.L.check(self.L.lib.gpis_render_scene_s_paths_rgb(self.h, _ptr(scene), int(max_bounces), _ptr(alb), ctypes.c_void_p(d_rad.data_ptr()),
-                                                              ctypes.c_void_p(d_seg.data_ptr()) if want_segs else None, None), "gpis_render_scene_s_paths_rgb")
-        torch.cuda.synchronize(dev)
-        rad = d_rad.cpu().numpy()[:3 * hgt * wid].reshape(hgt, wid, 3).copy()
-        if not want_segs:
-            return rad
-        return rad, d_seg.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
+        return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_paths_rgb", scene, (int(max_bounces), _ptr(alb)), channels=3,
+                            has_count=True, want_count=want_segs)
 
     def render_scene_s_adaptive(self, scene, adaptive=None, want_hits=False, want_records=False):
         """One frame of the Lambert driver under the reference's adaptive sample schedule (gpis_render_scene_s_adaptive) into zeroed
         device buffers: (radiance_sum, sample_count[, hit_count][, records], info) — the float32 sum-of-radiance image and the uint32
         samples per pixel to divide it by (height, width), the hits per pixel and the ADAPTIVE_RECORD array (ceil(height/4),
         ceil(width/4)) when asked, and the ADAPTIVE_INFO record.  scene["spp_count"] is the average number of samples per pixel."""
-        import torch
-        scene = np.array(scene, dtype=SCENE_S).reshape(())
-        adaptive = np.array(default_adaptive_s() if adaptive is None else adaptive, dtype=ADAPTIVE_S).reshape(())
-        hgt, wid = int(scene["height"]), int(scene["width"])
-        vh, vw = (hgt + 3) // 4, (wid + 3) // 4
-        dev = torch.device("cuda", self.device)
-        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
-        d_cnt = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev)
-        d_hit = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_hits else None
-        d_rec = torch.zeros(max(vh * vw, 1) * ADAPTIVE_RECORD.itemsize, dtype=torch.uint8, device=dev) if want_records else None
-        info = np.zeros((), dtype=ADAPTIVE_INFO)
-        torch.cuda.synchronize(dev)
-        self.L.check(self.L.lib.gpis_render_scene_s_adaptive(self.h, _ptr(scene), _ptr(adaptive), ctypes.c_void_p(d_rad.data_ptr()),
-                                                             ctypes.c_void_p(d_cnt.data_ptr()), ctypes.c_void_p(d_hit.data_ptr()) if want_hits else None,
-                                                             ctypes.c_void_p(d_rec.data_ptr()) if want_records else None, _ptr(info), None),
-                     "gpis_render_scene_s_adaptive")
-        torch.cuda.synchronize(dev)
-        out = [d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy(), d_cnt.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()]
-        if want_hits:
-            out.append(d_hit.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy())
-        if want_records:
-            out.append(d_rec.cpu().numpy()[:vh * vw * ADAPTIVE_RECORD.itemsize].view(ADAPTIVE_RECORD).reshape(vh, vw).copy())
-        out.append(info)
-        return tuple(out)
+        return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_adaptive", scene, has_count=True, want_count=want_hits,
+                            adaptive=_adaptive_s(adaptive), want_records=want_records)
 
     def render_scene_s_paths_rgb_adaptive(self, scene, max_bounces, albedo, adaptive=None, want_segs=False, want_records=False):
         """One frame of the RGB path driver under the reference's adaptive sample schedule (gpis_render_scene_s_paths_rgb_adaptive)
@@ -825,61 +805,9 @@ class Medium:
         (height, width, 3) and the uint32 samples per pixel to divide it by (height, width), the segments marched per pixel and the
         ADAPTIVE_RECORD array (ceil(height/4), ceil(width/4)) when asked, and the ADAPTIVE_INFO record.  scene["spp_count"] is the
         average number of samples per pixel.  A scalar `albedo` is broadcast to the three channels."""
-        import torch
-        scene = np.array(scene, dtype=SCENE_S).reshape(())
-        adaptive = np.array(default_adaptive_s() if adaptive is None else adaptive, dtype=ADAPTIVE_S).reshape(())
         alb = np.ascontiguousarray(np.broadcast_to(np.asarray(albedo, dtype=np.float32), (3,)))
-        hgt, wid = int(scene["height"]), int(scene["width"])
-        vh, vw = (hgt + 3) // 4, (wid + 3) // 4
-        dev = torch.device("cuda", self.device)
-        d_rad = torch.zeros(max(3 * hgt * wid, 1), dtype=torch.float32, device=dev)
-        d_cnt = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev)
-        d_seg = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_segs else None
-        d_rec = torch.zeros(max(vh * vw, 1) * ADAPTIVE_RECORD.itemsize, dtype=torch.uint8, device=dev) if want_records else None
-        info = np.zeros((), dtype=ADAPTIVE_INFO)
-        torch.cuda.synchronize(dev)
-        self.L.check(self.L.lib.gpis_render_scene_s_paths_rgb_adaptive(self.h, _ptr(scene), _ptr(adaptive), int(max_bounces), _ptr(alb),
-                                                                       ctypes.c_void_p(d_rad.data_ptr()), ctypes.c_void_p(d_cnt.data_ptr()),
-                                                                       ctypes.c_void_p(d_seg.data_ptr()) if want_segs else None,
-                                                                       ctypes.c_void_p(d_rec.data_ptr()) if want_records else None, _ptr(info), None),
-                     "gpis_render_scene_s_paths_rgb_adaptive")
-        torch.cuda.synchronize(dev)
-        out = [d_rad.cpu().numpy()[:3 * hgt * wid].reshape(hgt, wid, 3).copy(), d_cnt.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()]
-        if want_segs:
-            out.append(d_seg.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy())
-        if want_records:
-            out.append(d_rec.cpu().numpy()[:vh * vw * ADAPTIVE_RECORD.itemsize].view(ADAPTIVE_RECORD).reshape(vh, vw).copy())
-        out.append(info)
-        return tuple(out)
-
-    def _paths_adaptive_frame(self, entry, scene, adaptive, args, want_segs, want_records):
-        """the mono path entries under the adaptive schedule (and the function-space frame entry, whose per-pixel count is hits)
-        into zeroed device buffers, with the return convention of render_scene_s_paths_rgb_adaptive"""
-        import torch
-        scene = np.array(scene, dtype=SCENE_S).reshape(())
-        adaptive = np.array(default_adaptive_s() if adaptive is None else adaptive, dtype=ADAPTIVE_S).reshape(())
-        hgt, wid = int(scene["height"]), int(scene["width"])
-        vh, vw = (hgt + 3) // 4, (wid + 3) // 4
-        dev = torch.device("cuda", self.device)
-        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
-        d_cnt = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev)
-        d_seg = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_segs else None
-        d_rec = torch.zeros(max(vh * vw, 1) * ADAPTIVE_RECORD.itemsize, dtype=torch.uint8, device=dev) if want_records else None
-        info = np.zeros((), dtype=ADAPTIVE_INFO)
-        bufs = [ctypes.c_void_p(d_rad.data_ptr()), ctypes.c_void_p(d_cnt.data_ptr())]
-        if entry != "gpis_render_scene_s_paths_adaptive":        # the one entry without a per-pixel count beside sample_count
-            bufs.append(ctypes.c_void_p(d_seg.data_ptr()) if want_segs else None)
-        torch.cuda.synchronize(dev)
-        self.L.check(getattr(self.L.lib, entry)(self.h, _ptr(scene), _ptr(adaptive), *args, *bufs,
-                                                ctypes.c_void_p(d_rec.data_ptr()) if want_records else None, _ptr(info), None), entry)
-        torch.cuda.synchronize(dev)
-        out = [d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy(), d_cnt.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()]
-        if want_segs:
-            out.append(d_seg.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy())
-        if want_records:
-            out.append(d_rec.cpu().numpy()[:vh * vw * ADAPTIVE_RECORD.itemsize].view(ADAPTIVE_RECORD).reshape(vh, vw).copy())
-        out.append(info)
-        return tuple(out)
+        return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_paths_rgb_adaptive", scene, (int(max_bounces), _ptr(alb)), channels=3,
+                            has_count=True, want_count=want_segs, adaptive=_adaptive_s(adaptive), want_records=want_records)
 
     def render_scene_s_paths_adaptive(self, scene, max_bounces, albedo, adaptive=None, want_records=False):
         """One frame of the mono Lambert path driver under the reference's adaptive sample schedule
@@ -887,7 +815,8 @@ class Medium:
         sum-of-radiance image and the uint32 samples per pixel to divide it by (height, width), the ADAPTIVE_RECORD array
         (ceil(height/4), ceil(width/4)) when asked, and the ADAPTIVE_INFO record.  scene["spp_count"] is the average number of
         samples per pixel."""
-        return self._paths_adaptive_frame("gpis_render_scene_s_paths_adaptive", scene, adaptive, (int(max_bounces), ctypes.c_float(albedo)), False, want_records)
+        return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_paths_adaptive", scene, (int(max_bounces), ctypes.c_float(albedo)),
+                            adaptive=_adaptive_s(adaptive), want_records=want_records)
 
     def render_scene_s_nee_paths_adaptive(self, scene, surface, max_bounces, adaptive=None, want_segs=False, want_records=False):
         """One frame of the conductor NEE / MIS path driver under the reference's adaptive sample schedule
@@ -895,20 +824,22 @@ class Medium:
         info) as render_scene_s_paths_rgb_adaptive returns them, the image (height, width); seg_count: per pixel the segments
         marched (path, light shadow and phase shadow segments)."""
         surface = np.array(surface, dtype=SURFACE_S).reshape(())
-        return self._paths_adaptive_frame("gpis_render_scene_s_nee_paths_adaptive", scene, adaptive, (_ptr(surface), int(max_bounces)), want_segs, want_records)
+        return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_nee_paths_adaptive", scene, (_ptr(surface), int(max_bounces)),
+                            has_count=True, want_count=want_segs, adaptive=_adaptive_s(adaptive), want_records=want_records)
 
     def fs_render_scene_s_adaptive(self, scene, adaptive=None, want_hits=False, want_records=False):
         """One frame of the function-space scene-S frame driver under the reference's adaptive sample schedule
         (gpis_fs_render_scene_s_adaptive) into zeroed device buffers: (radiance_sum, sample_count[, hit_count][, records], info) as
         render_scene_s_adaptive returns them."""
-        return self._paths_adaptive_frame("gpis_fs_render_scene_s_adaptive", scene, adaptive, (), want_hits, want_records)
+        return _scene_frame(self.L, self.h, self.device, "gpis_fs_render_scene_s_adaptive", scene, has_count=True, want_count=want_hits,
+                            adaptive=_adaptive_s(adaptive), want_records=want_records)
 
     def fs_render_scene_s_paths_adaptive(self, scene, max_bounces, albedo, adaptive=None, want_segs=False, want_records=False):
         """One frame of the function-space multi-bounce path driver under the adaptive sample schedule
         (gpis_fs_render_scene_s_paths_adaptive) into zeroed device buffers: (radiance_sum, sample_count[, seg_count][, records],
         info) as render_scene_s_nee_paths_adaptive returns them; seg_count: per pixel the segments marched (path plus shadow)."""
-        return self._paths_adaptive_frame("gpis_fs_render_scene_s_paths_adaptive", scene, adaptive, (int(max_bounces), ctypes.c_float(albedo)), want_segs,
-                                          want_records)
+        return _scene_frame(self.L, self.h, self.device, "gpis_fs_render_scene_s_paths_adaptive", scene, (int(max_bounces), ctypes.c_float(albedo)),
+                            has_count=True, want_count=want_segs, adaptive=_adaptive_s(adaptive), want_records=want_records)
 
     def mean_color_emission(self, points):
         """(color, emission) of the mean at double-precision points (n, 3)"""
@@ -1168,77 +1099,29 @@ class WeightSpaceMedium:
         torch.cuda.synchronize(d_p.device)
         return d_out.cpu().numpy()[:n * N * 6].reshape(n, N, 6).copy()
 
+    # ---- the scene-S frame drivers: argument marshalling around _scene_frame, as Medium's
     def render_scene_s(self, scene, want_hits=False):
         """One call of the scene-S frame driver (gpis_ws_render_scene_s) into zeroed device buffers: the float32 sum-of-radiance
         image (height, width) of the rows, shard and samples `scene` selects, and the per-pixel hit counts when asked."""
-        import torch
-        scene = np.array(scene, dtype=SCENE_S).reshape(())
-        hgt, wid = int(scene["height"]), int(scene["width"])
-        dev = torch.device("cuda", self.device)
-        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
-        d_hit = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_hits else None
-        torch.cuda.synchronize(dev)
-        self.L.check(self.L.lib.gpis_ws_render_scene_s(self.h, _ptr(scene), ctypes.c_void_p(d_rad.data_ptr()),
-                                                       ctypes.c_void_p(d_hit.data_ptr()) if want_hits else None, None), "gpis_ws_render_scene_s")
-        torch.cuda.synchronize(dev)
-        rad = d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy()
-        if not want_hits:
-            return rad
-        return rad, d_hit.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()
+        return _scene_frame(self.L, self.h, self.device, "gpis_ws_render_scene_s", scene, has_count=True, want_count=want_hits)
 
     def render_scene_s_paths(self, scene, max_bounces, albedo):
         """One call of the multi-bounce path driver (gpis_ws_render_scene_s_paths) into a zeroed device buffer: the float32
         sum-of-radiance image (height, width) of the rows, shard and samples `scene` selects."""
-        import torch
-        scene = np.array(scene, dtype=SCENE_S).reshape(())
-        hgt, wid = int(scene["height"]), int(scene["width"])
-        dev = torch.device("cuda", self.device)
-        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-        self.L.check(self.L.lib.gpis_ws_render_scene_s_paths(self.h, _ptr(scene), int(max_bounces), ctypes.c_float(albedo),
-                                                             ctypes.c_void_p(d_rad.data_ptr()), None), "gpis_ws_render_scene_s_paths")
-        torch.cuda.synchronize(dev)
-        return d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy()
-
-    def _adaptive_frame(self, entry, scene, adaptive, args, want_hits, want_records, chunk_log2):
-        """the two adaptive entries into zeroed device buffers, with the return convention of Medium.render_scene_s_adaptive"""
-        import torch
-        scene = np.array(scene, dtype=SCENE_S).reshape(())
-        adaptive = np.array(default_adaptive_s() if adaptive is None else adaptive, dtype=ADAPTIVE_S).reshape(())
-        hgt, wid = int(scene["height"]), int(scene["width"])
-        vh, vw = (hgt + 3) // 4, (wid + 3) // 4
-        dev = torch.device("cuda", self.device)
-        d_rad = torch.zeros(max(hgt * wid, 1), dtype=torch.float32, device=dev)
-        d_cnt = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev)
-        d_hit = torch.zeros(max(hgt * wid, 1), dtype=torch.int32, device=dev) if want_hits else None
-        d_rec = torch.zeros(max(vh * vw, 1) * ADAPTIVE_RECORD.itemsize, dtype=torch.uint8, device=dev) if want_records else None
-        info = np.zeros((), dtype=ADAPTIVE_INFO)
-        bufs = [ctypes.c_void_p(d_rad.data_ptr()), ctypes.c_void_p(d_cnt.data_ptr())]
-        if entry == "gpis_ws_render_scene_s_adaptive":
-            bufs.append(ctypes.c_void_p(d_hit.data_ptr()) if want_hits else None)
-        torch.cuda.synchronize(dev)
-        self.L.check(getattr(self.L.lib, entry)(self.h, _ptr(scene), _ptr(adaptive), int(chunk_log2), *args, *bufs,
-                                                ctypes.c_void_p(d_rec.data_ptr()) if want_records else None, _ptr(info), None), entry)
-        torch.cuda.synchronize(dev)
-        out = [d_rad.cpu().numpy()[:hgt * wid].reshape(hgt, wid).copy(), d_cnt.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy()]
-        if want_hits:
-            out.append(d_hit.cpu().numpy()[:hgt * wid].view(np.uint32).reshape(hgt, wid).copy())
-        if want_records:
-            out.append(d_rec.cpu().numpy()[:vh * vw * ADAPTIVE_RECORD.itemsize].view(ADAPTIVE_RECORD).reshape(vh, vw).copy())
-        out.append(info)
-        return tuple(out)
+        return _scene_frame(self.L, self.h, self.device, "gpis_ws_render_scene_s_paths", scene, (int(max_bounces), ctypes.c_float(albedo)))
 
     def render_scene_s_adaptive(self, scene, adaptive=None, want_hits=False, want_records=False, chunk_log2=0):
         """One frame of the scene-S frame driver under the reference's adaptive sample schedule (gpis_ws_render_scene_s_adaptive):
         (radiance_sum, sample_count[, hit_count][, records], info) as Medium.render_scene_s_adaptive returns them.
         scene["spp_count"] is the average number of samples per pixel; chunk_log2 (0: 2^22, else 8 .. 28) changes no result."""
-        return self._adaptive_frame("gpis_ws_render_scene_s_adaptive", scene, adaptive, (), want_hits, want_records, chunk_log2)
+        return _scene_frame(self.L, self.h, self.device, "gpis_ws_render_scene_s_adaptive", scene, (int(chunk_log2),), has_count=True,
+                            want_count=want_hits, adaptive=_adaptive_s(adaptive), want_records=want_records)
 
     def render_scene_s_paths_adaptive(self, scene, max_bounces, albedo, adaptive=None, want_records=False, chunk_log2=0):
         """One frame of the multi-bounce path driver under the adaptive sample schedule (gpis_ws_render_scene_s_paths_adaptive):
         (radiance_sum, sample_count[, records], info)."""
-        return self._adaptive_frame("gpis_ws_render_scene_s_paths_adaptive", scene, adaptive, (int(max_bounces), ctypes.c_float(albedo)), False,
-                                    want_records, chunk_log2)
+        return _scene_frame(self.L, self.h, self.device, "gpis_ws_render_scene_s_paths_adaptive", scene,
+                            (int(chunk_log2), int(max_bounces), ctypes.c_float(albedo)), adaptive=_adaptive_s(adaptive), want_records=want_records)
 
     def counters(self):
         e, s, g = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()

@@ -1,20 +1,19 @@
 // gpis_adaptive.hpp — the variable-count sample layout and the tile statistics of the adaptive frame drivers
 // (gpis_render_scene_s_adaptive, gpis_render_scene_s_paths_rgb_adaptive, gpis_render_scene_s_paths_adaptive and
-// gpis_render_scene_s_nee_paths_adaptive in tu_scene.hip, which instantiates the kernels below;
-// gpis_ws_render_scene_s_adaptive and gpis_ws_render_scene_s_paths_adaptive in tu_ws_adaptive.hip;
-// gpis_fs_render_scene_s_adaptive and gpis_fs_render_scene_s_paths_adaptive in tu_fs_adaptive.hip;
+// gpis_render_scene_s_nee_paths_adaptive in tu_scene.hip; gpis_ws_render_scene_s_adaptive and gpis_ws_render_scene_s_paths_adaptive
+// in tu_ws_adaptive.hip; gpis_fs_render_scene_s_adaptive and gpis_fs_render_scene_s_paths_adaptive in tu_fs_adaptive.hip;
 // the host plan step in tu_adaptive.hip; include/gpis.h states the contract and cites the reference).
 //   host + device: SampleRecord::addSample / errorEstimate (adaptive_add_sample, adaptive_error_estimate), the sample clamp of
 //       renderTile on a float and on a Vec3f (adaptive_clamp, adaptive_rgb_clamped), Vec3f::luminance (adaptive_luminance), the 4x4
 //       variance tile of a record clipped at the image edge (adaptive_tile);
 //   device: scene_sample of an AdaptiveChunk — the camera step of gpis_scene.hpp's scene_sample for a pass whose records carry
 //       different sample counts.  A driver whose camera kernel is a template on that argument renders under the adaptive schedule;
-//       nothing else of its kernels changes.  Behind the bounce loops: the per-pixel sums and the tile statistics of the staged
-//       adaptive drivers (the Lambert frame's on AdaptiveLambert, the RGB path driver's on its emission planes, the mono path
-//       drivers' — Lambert and conductor NEE — on their per-sample E).
-//       The fused weight-space and function-space kernels take the same step inside their work loop (k_ws_scene_adaptive,
-//       k_ws_paths_adaptive, k_fs_scene_adaptive, k_fs_paths_adaptive); their sums and statistics are gpis_adaptive_sum.hpp's on the
-//       accessors of gpis_ws_adaptive.hpp / gpis_fs_adaptive.hpp.  The pass loop of all drivers is gpis_adaptive_host.hpp's.
+//       nothing else of its kernels changes.  The fused weight-space and function-space kernels take the same step inside their
+//       work loop (k_ws_scene_adaptive, k_ws_paths_adaptive, k_fs_scene_adaptive, k_fs_paths_adaptive).
+//       Behind a chunk, every driver's per-pixel sum and tile statistics are the bodies of gpis_frame_sum.hpp on the driver's
+//       accessor (SceneRecValues below for the {cv, flags} records of the two fused Lambert frames); what stays here of the
+//       three-channel RGB path driver is its clamp / luminance step and its three-channel sum.  The pass loop of all drivers is
+//       gpis_adaptive_host.hpp's.
 // Layout of a pass: records in index order; record r owns the samples [offset[r], offset[r+1]) = its pixels row-major x its
 // next_sample_count samples, so a pixel's samples stay contiguous (what the cooperative guided evaluator lives on).
 #pragma once
@@ -77,6 +76,22 @@ __host__ __device__ inline bool adaptive_rgb_clamped(float c0, float c1, float c
 // Vec3f::luminance, Vec.hpp:218-222: what SampleRecord::addSample(const Vec3f &) hands addSample(float), SampleRecord.hpp:52-55
 __host__ __device__ inline float adaptive_luminance(float c0, float c1, float c2) { return ((c0 * 0.2126f) + (c1 * 0.7152f)) + (c2 * 0.0722f); }
 
+// What a sample of a fused Lambert frame is worth, on its record {cv, flags} (WsSceneRec, FsSceneRec: bit 0 = the primary segment
+// hit, bit 1 = lit, cv takes part in the pixel's sum) — an accessor of gpis_frame_sum.hpp.  raw is what the uniform entry adds,
+// unclamped; value is raw after renderTile's clamp, what the adaptive entry adds and accounts.
+template <typename Rec>
+struct SceneRecValues {
+    const Rec *recs;
+    float light_radiance;
+    GPIS_DEV float raw(size_t i) const
+    {
+        const Rec r = recs[i];
+        return (r.flags & 2u) ? r.cv * light_radiance : 0.f;
+    }
+    GPIS_DEV float value(size_t i) const { return adaptive_clamp(raw(i)); }
+    GPIS_DEV uint32_t count(size_t i) const { return recs[i].flags & 1u; }
+};
+
 // Sample i of a chunk -> its record, then its pixel, its sample index k and the sample's PCG32 stream, seeded as scene_sample seeds
 // the sample (x, y, k).  The record is the last one of the chunk whose offset is <= the sample's position in the pass.
 GPIS_DEV Pcg32 scene_sample(const SceneConst &sc, const AdaptiveChunk &c, size_t i, uint32_t &x, uint32_t &y, uint32_t &spp)
@@ -99,56 +114,6 @@ GPIS_DEV Pcg32 scene_sample(const SceneConst &sc, const AdaptiveChunk &c, size_t
     return g;
 }
 
-// ---- the Lambert frame (gpis_render_scene_s_adaptive): what the shade step and the shadow march leave per sample of a chunk
-struct AdaptiveLambert {
-    const float *cosl;
-    const uint8_t *valid2, *vis, *hit;
-};
-// the value of sample i as k_scene_accumulate adds it, after renderTile's clamp
-GPIS_DEV float adaptive_sample_value(const AdaptiveLambert &a, size_t i, float light_radiance)
-{
-    return a.valid2[i] ? adaptive_clamp(a.cosl[i] * (a.vis[i] ? 1.f : 0.f) * light_radiance) : 0.f;
-}
-
-// one lane per pixel slot (16 per record, those past a clipped tile idle): sequential sum over the pixel's samples, in sample order
-GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_adaptive_accumulate(SceneConst sc, AdaptiveChunk ch, AdaptiveLambert a, float *__restrict__ radiance_sum,
-                                                                            uint32_t *__restrict__ sample_count, uint32_t *__restrict__ hit_count)
-{
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= (size_t)ch.nrec * (kVarianceTile * kVarianceTile)) return;
-    const uint32_t r = ch.r0 + (uint32_t)(j / (kVarianceTile * kVarianceTile)), p = (uint32_t)(j % (kVarianceTile * kVarianceTile));
-    const AdaptiveTile t = adaptive_tile(sc.s.width, sc.s.height, r);
-    if (p >= t.w * t.h) return;
-    const AdaptivePlanRec rec = ch.plan[r];
-    const size_t first = (size_t)(rec.offset - ch.plan[ch.r0].offset) + (size_t)p * rec.count;
-    float acc = 0.f;
-    uint32_t hits = 0;
-    for (uint32_t k = 0; k < rec.count; ++k) {
-        hits += a.hit[first + k];
-        acc += adaptive_sample_value(a, first + k, sc.s.light_radiance);
-    }
-    const size_t pix = (size_t)(t.y0 + p / t.w) * sc.s.width + (t.x0 + p % t.w);
-    radiance_sum[pix] += acc;
-    sample_count[pix] += rec.count;
-    if (hit_count) hit_count[pix] += hits;
-}
-
-// one lane per record: SampleRecord::addSample over the tile's pixels row-major, then the sample index — the record's samples in
-// the order the layout stores them
-GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_adaptive_stats(SceneConst sc, AdaptiveChunk ch, AdaptiveLambert a, gpis_adaptive_record *__restrict__ records)
-{
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= ch.nrec) return;
-    const uint32_t r = ch.r0 + (uint32_t)j;
-    const size_t first = (size_t)(ch.plan[r].offset - ch.plan[ch.r0].offset), n = (size_t)(ch.plan[r + 1].offset - ch.plan[r].offset);
-    gpis_adaptive_record rec = records[r];
-    for (size_t q = 0; q < n; ++q)
-        adaptive_add_sample(rec, adaptive_sample_value(a, first + q, sc.s.light_radiance));
-    records[r].sample_count = rec.sample_count;
-    records[r].mean = rec.mean;
-    records[r].running_variance = rec.running_variance;
-}
-
 // ---- the RGB path driver (gpis_render_scene_s_paths_rgb_adaptive), after the bounce loop of a chunk of records; `emission`: three
 // planes of `plane` floats (gpis_paths_rgb.hpp)
 
@@ -162,22 +127,6 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_rgb_adaptive_value(size_
     const bool z = adaptive_rgb_clamped(c0, c1, c2);
     luminance[i] = adaptive_luminance(z ? 0.f : c0, z ? 0.f : c1, z ? 0.f : c2);
     clamped[i] = z ? 1 : 0;
-}
-
-// one lane per record: SampleRecord::addSample over the record's luminances in the order the layout stores them (k_adaptive_stats)
-GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_rgb_adaptive_stats(AdaptiveChunk ch, const float *__restrict__ luminance,
-                                                                           gpis_adaptive_record *__restrict__ records)
-{
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= ch.nrec) return;
-    const uint32_t r = ch.r0 + (uint32_t)j;
-    const size_t first = (size_t)(ch.plan[r].offset - ch.plan[ch.r0].offset), n = (size_t)(ch.plan[r + 1].offset - ch.plan[r].offset);
-    gpis_adaptive_record rec = records[r];
-    for (size_t q = 0; q < n; ++q)
-        adaptive_add_sample(rec, luminance[first + q]);
-    records[r].sample_count = rec.sample_count;
-    records[r].mean = rec.mean;
-    records[r].running_variance = rec.running_variance;
 }
 
 // one lane per pixel slot (16 per record, those past a clipped tile idle): per channel the sequential sum over the pixel's clamped
@@ -207,50 +156,6 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_rgb_adaptive_accumulate(
         radiance_sum3[3 * pix + c] += acc[c];
     sample_count[pix] += rec.count;
     if (seg_count) seg_count[pix] += marched;
-}
-
-// ---- the mono path drivers (gpis_render_scene_s_paths_adaptive, gpis_render_scene_s_nee_paths_adaptive), after the bounce loop of a
-// chunk of records; `emission`: E of every sample, `segs`: the segments marched for it (NULL where the driver counts none)
-
-// one lane per pixel slot (16 per record, those past a clipped tile idle): the sequential sum over the pixel's clamped E, in sample
-// order, and the segments marched for them — a clamped sample's too
-GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_adaptive_sum(SceneConst sc, AdaptiveChunk ch, const float *__restrict__ emission,
-                                                                           const uint32_t *__restrict__ segs, float *__restrict__ radiance_sum,
-                                                                           uint32_t *__restrict__ sample_count, uint32_t *__restrict__ seg_count)
-{
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= (size_t)ch.nrec * (kVarianceTile * kVarianceTile)) return;
-    const uint32_t r = ch.r0 + (uint32_t)(j / (kVarianceTile * kVarianceTile)), p = (uint32_t)(j % (kVarianceTile * kVarianceTile));
-    const AdaptiveTile t = adaptive_tile(sc.s.width, sc.s.height, r);
-    if (p >= t.w * t.h) return;
-    const AdaptivePlanRec rec = ch.plan[r];
-    const size_t first = (size_t)(rec.offset - ch.plan[ch.r0].offset) + (size_t)p * rec.count;
-    float acc = 0.f;
-    uint32_t marched = 0;
-    for (uint32_t k = 0; k < rec.count; ++k) {
-        acc += adaptive_clamp(emission[first + k]);
-        if (segs) marched += segs[first + k];
-    }
-    const size_t pix = (size_t)(t.y0 + p / t.w) * sc.s.width + (t.x0 + p % t.w);
-    radiance_sum[pix] += acc;
-    sample_count[pix] += rec.count;
-    if (segs) seg_count[pix] += marched;
-}
-
-// one lane per record: SampleRecord::addSample over the record's clamped E in the order the layout stores them (k_adaptive_stats)
-GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_adaptive_tile_stats(AdaptiveChunk ch, const float *__restrict__ emission,
-                                                                                  gpis_adaptive_record *__restrict__ records)
-{
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= ch.nrec) return;
-    const uint32_t r = ch.r0 + (uint32_t)j;
-    const size_t first = (size_t)(ch.plan[r].offset - ch.plan[ch.r0].offset), n = (size_t)(ch.plan[r + 1].offset - ch.plan[r].offset);
-    gpis_adaptive_record rec = records[r];
-    for (size_t q = 0; q < n; ++q)
-        adaptive_add_sample(rec, adaptive_clamp(emission[first + q]));
-    records[r].sample_count = rec.sample_count;
-    records[r].mean = rec.mean;
-    records[r].running_variance = rec.running_variance;
 }
 
 }   // namespace gpis

@@ -37,7 +37,7 @@
 // in full, the shade step as in k_ws_paths and k_paths_shade: as functions around the marches they made this kernel slower
 // (gpis_scene.hpp).  The tests pin all three against the same C (tests/native/ws_paths_shade.c, tests/native/fs_paths_shade.c).
 #pragma once
-#include "gpis_adaptive.hpp"
+#include "gpis_frame_sum.hpp"
 #include "gpis_fs.hpp"
 #include "gpis_scene.hpp"
 
@@ -48,6 +48,15 @@ namespace gpis {
 // one sample: its emission (the sum of its NEE contributions in bounce order; 0 for a sample that misses the bound) and the
 // segments marched for it, path plus shadow
 struct FsPathsRec { float emission; uint32_t segs; };
+// what the sums and the tile statistics read of it (gpis_frame_sum.hpp): a mono estimator's scalar emission — raw as the uniform entry
+// adds it, value after renderTile's clamp as the adaptive entry adds and accounts it; the count is the sample's segments, path plus
+// shadow, whether or not the clamp took its value
+struct FsPathsValues {
+    const FsPathsRec *recs;
+    GPIS_DEV float raw(size_t i) const { return recs[i].emission; }
+    GPIS_DEV float value(size_t i) const { return adaptive_clamp(raw(i)); }
+    GPIS_DEV uint32_t count(size_t i) const { return recs[i].segs; }
+};
 
 static_assert(sizeof(gpis_fs_state) % sizeof(unsigned long long) == 0 && alignof(gpis_fs_state) == alignof(unsigned long long), "the state copies as whole 8-byte words");
 
@@ -191,19 +200,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_paths_adaptive(const D
 GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_fs_paths_sum(SceneConst sc, size_t first_pixel, size_t n_pixels, const FsPathsRec *__restrict__ recs,
                                                                      float *__restrict__ radiance_sum, uint32_t *__restrict__ seg_count)
 {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_pixels) return;
-    const uint32_t spp = sc.s.spp_count;
-    float acc = 0.f;
-    uint32_t segs = 0;
-    for (uint32_t k = 0; k < spp; ++k) {
-        const FsPathsRec r = recs[j * spp + k];
-        acc += r.emission;
-        segs += r.segs;
-    }
-    const size_t pix = scene_pixel(sc.s, first_pixel + j);
-    radiance_sum[pix] += acc;
-    if (seg_count) seg_count[pix] += segs;
+    frame_values_sum(sc, first_pixel, n_pixels, FsPathsValues{recs}, radiance_sum, seg_count);
 }
 
 }   // namespace gpis

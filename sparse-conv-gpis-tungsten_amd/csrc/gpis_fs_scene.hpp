@@ -21,7 +21,7 @@
 // k_fs_scene_adaptive is the same body (gpis_fs_scene_body.inc) on the variable-count sample layout of an adaptive pass
 // (gpis_adaptive.hpp: scene_sample of an AdaptiveChunk); gpis_fs_adaptive.hpp sums and accounts its records.
 #pragma once
-#include "gpis_adaptive.hpp"
+#include "gpis_frame_sum.hpp"
 #include "gpis_fs.hpp"
 #include "gpis_scene.hpp"
 
@@ -32,6 +32,8 @@ namespace gpis {
 // one sample's contribution: cos(normal, light) * visible, and bit 0 = the primary segment hit the surface (ok && !exited),
 // bit 1 = lit (a shadow segment was marched; cv takes part in the pixel's sum)
 struct FsSceneRec { float cv; uint32_t flags; };
+// what the sums and the tile statistics read of it (gpis_frame_sum.hpp); count: whether the primary segment hit
+struct FsSceneValues : SceneRecValues<FsSceneRec> {};
 
 // grid = the resident set of the function-space workspace (four one-wave workgroups per CU): workspace[blockIdx.x] and
 // slots[blockIdx.x] are this workgroup's for the whole launch.  Every value that steers control flow is computed identically by
@@ -61,20 +63,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_fs_scene_adaptive(const D
 GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_fs_scene_sum(SceneConst sc, size_t first_pixel, size_t n_pixels, const FsSceneRec *__restrict__ recs,
                                                                      float *__restrict__ radiance_sum, uint32_t *__restrict__ hit_count)
 {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_pixels) return;
-    const uint32_t spp = sc.s.spp_count;
-    float acc = 0.f;
-    uint32_t hits = 0;
-    for (uint32_t k = 0; k < spp; ++k) {
-        const FsSceneRec r = recs[j * spp + k];
-        hits += r.flags & 1u;
-        if (r.flags & 2u)
-            acc += r.cv * sc.s.light_radiance;
-    }
-    const size_t pix = scene_pixel(sc.s, first_pixel + j);
-    radiance_sum[pix] += acc;
-    if (hit_count) hit_count[pix] += hits;
+    frame_values_sum(sc, first_pixel, n_pixels, FsSceneValues{recs, sc.s.light_radiance}, radiance_sum, hit_count);
 }
 
 }   // namespace gpis

@@ -28,7 +28,7 @@
 // k_ws_paths_adaptive is the same body on the variable-count sample layout of an adaptive pass (gpis_adaptive.hpp: scene_sample of an
 // AdaptiveChunk); gpis_ws_adaptive.hpp sums and accounts its records.
 #pragma once
-#include "gpis_adaptive.hpp"
+#include "gpis_frame_sum.hpp"
 #include "gpis_scene.hpp"
 #include "gpis_ws.hpp"
 
@@ -38,6 +38,14 @@ namespace gpis {
 
 // one sample's emission: the sum of its NEE contributions in bounce order (0 for a sample that misses the bound)
 struct WsPathsRec { float emission; };
+// what the sums and the tile statistics read of it (gpis_frame_sum.hpp): a mono estimator's scalar emission — raw as the uniform entry
+// adds it, value after renderTile's clamp as the adaptive entry adds and accounts it; the driver counts nothing per pixel
+struct WsPathsValues {
+    const WsPathsRec *recs;
+    GPIS_DEV float raw(size_t i) const { return recs[i].emission; }
+    GPIS_DEV float value(size_t i) const { return adaptive_clamp(raw(i)); }
+    GPIS_DEV uint32_t count(size_t) const { return 0u; }
+};
 
 // The body of the fused kernel, a template on the sample step `where` (scene_sample's second argument): size_t, the first pixel of
 // a chunk with spp_count samples per pixel (k_ws_paths), or AdaptiveChunk, the records of an adaptive pass (k_ws_paths_adaptive;
@@ -180,13 +188,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_paths_adaptive(const W
 GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_ws_paths_sum(SceneConst sc, size_t first_pixel, size_t n_pixels, const WsPathsRec *__restrict__ recs,
                                                                      float *__restrict__ radiance_sum)
 {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_pixels) return;
-    const uint32_t spp = sc.s.spp_count;
-    float acc = 0.f;
-    for (uint32_t k = 0; k < spp; ++k)
-        acc += recs[j * spp + k].emission;
-    radiance_sum[scene_pixel(sc.s, first_pixel + j)] += acc;
+    frame_values_sum(sc, first_pixel, n_pixels, WsPathsValues{recs}, radiance_sum, nullptr);
 }
 
 }   // namespace gpis

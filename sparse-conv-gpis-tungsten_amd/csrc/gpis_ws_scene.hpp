@@ -17,7 +17,7 @@
 // k_ws_scene_adaptive is the same body on the variable-count sample layout of an adaptive pass (gpis_adaptive.hpp: scene_sample of an
 // AdaptiveChunk); gpis_ws_adaptive.hpp sums and accounts its records.
 #pragma once
-#include "gpis_adaptive.hpp"
+#include "gpis_frame_sum.hpp"
 #include "gpis_scene.hpp"
 #include "gpis_ws.hpp"
 
@@ -28,6 +28,8 @@ namespace gpis {
 // one sample's contribution: cos(normal, light) * visible, and bit 0 = the primary segment hit the surface,
 // bit 1 = lit (a shadow segment was marched; cv takes part in the pixel's sum)
 struct WsSceneRec { float cv; uint32_t flags; };
+// what the sums and the tile statistics read of it (gpis_frame_sum.hpp); count: whether the primary segment hit
+struct WsSceneValues : SceneRecValues<WsSceneRec> {};
 
 // The body of the fused kernel, a template on the sample step `where` (scene_sample's second argument): size_t, the first pixel of
 // a chunk with spp_count samples per pixel (k_ws_scene), or AdaptiveChunk, the records of an adaptive pass (k_ws_scene_adaptive;
@@ -123,20 +125,7 @@ GPIS_TU_KERNEL __global__ void __launch_bounds__(64) k_ws_scene_adaptive(const W
 GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_ws_scene_sum(SceneConst sc, size_t first_pixel, size_t n_pixels, const WsSceneRec *__restrict__ recs,
                                                                      float *__restrict__ radiance_sum, uint32_t *__restrict__ hit_count)
 {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_pixels) return;
-    const uint32_t spp = sc.s.spp_count;
-    float acc = 0.f;
-    uint32_t hits = 0;
-    for (uint32_t k = 0; k < spp; ++k) {
-        const WsSceneRec r = recs[j * spp + k];
-        hits += r.flags & 1u;
-        if (r.flags & 2u)
-            acc += r.cv * sc.s.light_radiance;
-    }
-    const size_t pix = scene_pixel(sc.s, first_pixel + j);
-    radiance_sum[pix] += acc;
-    if (hit_count) hit_count[pix] += hits;
+    frame_values_sum(sc, first_pixel, n_pixels, WsSceneValues{recs, sc.s.light_radiance}, radiance_sum, hit_count);
 }
 
 }   // namespace gpis

@@ -2,7 +2,7 @@
 // drivers of the function-space GP medium under the adaptive sample schedule.  The pass loop is the one of the other adaptive
 // drivers (gpis_adaptive_host.hpp); a chunk of records is one fused launch on the variable-count layout (k_fs_scene_adaptive,
 // k_fs_paths_adaptive: tu_fs_scene.hip, tu_fs_paths.hip through gpis_launch.hpp), the per-pixel sum of its sample records and the
-// tile statistics (gpis_fs_adaptive.hpp: the bodies of gpis_adaptive_sum.hpp on this medium's accessors).  Of fs_frame
+// tile statistics (gpis_fs_adaptive.hpp: the bodies of gpis_frame_sum.hpp on this medium's accessors).  Of fs_frame
 // (tu_scene.hip) a chunk keeps the reset of the work counter, fs_workspace for the records and the grid cap, and
 // grid = min(samples, cap).
 #include <hip/hip_runtime.h>

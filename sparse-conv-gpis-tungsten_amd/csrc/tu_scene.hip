@@ -18,7 +18,8 @@
 #include "gpis_host.hpp"
 #include "gpis_launch.hpp"
 #include "gpis_scene.hpp"       // SceneConst, scene_sample, scene_camera_ray, hit_normal, the compact records
-#include "gpis_adaptive.hpp"    // the variable-count sample layout: scene_sample of an AdaptiveChunk, the sums and the tile statistics
+#include "gpis_adaptive.hpp"    // the variable-count sample layout: scene_sample of an AdaptiveChunk, the tile statistics' arithmetic, the clamps
+#include "gpis_frame_sum.hpp"   // the per-pixel sums and the tile statistics behind a chunk, on the accessors below
 #include "gpis_adaptive_host.hpp"   // adaptive_passes: the pass loop of the adaptive drivers
 #include "gpis_paths_rgb.hpp"   // PathsRgbArrays and the kernels of the RGB path drivers
 
@@ -172,6 +173,35 @@ __global__ void __launch_bounds__(256) k_scene_accumulate(SceneConst sc, size_t 
     if (hit_count) hit_count[pix] += hits;
 }
 
+// What the shade step and the shadow march leave per sample of a chunk of the Lambert frame (lambert_chunk): the staged arrays, and
+// what a sample of them is worth under the adaptive schedule at the scene's light radiance — an accessor of gpis_frame_sum.hpp.
+// value: what k_scene_accumulate adds, after renderTile's clamp; count: whether the primary segment hit.  The kernels take the
+// arrays and build the accessor themselves, so their parameters stay the four pointers.  (No raw: k_scene_accumulate, the one
+// uniform sum of these arrays, stays its own kernel, scalar tail included.  The kernels of the adaptive schedule are templates in
+// namespace gpis, as the headers' kernels.)
+namespace gpis {
+struct AdaptiveLambert {
+    const float *cosl;
+    const uint8_t *valid2, *vis, *hit;
+};
+struct LambertValues {
+    AdaptiveLambert a;
+    float light_radiance;
+    GPIS_DEV float value(size_t i) const { return a.valid2[i] ? adaptive_clamp(a.cosl[i] * (a.vis[i] ? 1.f : 0.f) * light_radiance) : 0.f; }
+    GPIS_DEV uint32_t count(size_t i) const { return a.hit[i]; }
+};
+
+// gpis_render_scene_s_adaptive behind a chunk of records: the per-pixel sum of the variable-count layout and the tile statistics
+GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_adaptive_accumulate(SceneConst sc, AdaptiveChunk ch, AdaptiveLambert a, float *__restrict__ radiance_sum,
+                                                                            uint32_t *__restrict__ sample_count, uint32_t *__restrict__ hit_count)
+{
+    adaptive_values_sum(sc, ch, LambertValues{a, sc.s.light_radiance}, radiance_sum, sample_count, hit_count);
+}
+GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_adaptive_stats(SceneConst sc, AdaptiveChunk ch, AdaptiveLambert a, gpis_adaptive_record *__restrict__ records)
+{
+    adaptive_values_stats(ch, LambertValues{a, sc.s.light_radiance}, records);
+}
+}   // namespace gpis
 
 // --------------------------------------------------------------------------------------
 // multi-bounce wavefront driver (gpis_render_scene_s_paths): PathTracer.cpp:62-75,
@@ -367,17 +397,53 @@ __global__ void __launch_bounds__(256) k_paths_nee_add(size_t n_samples, PathArr
     a.emission[order ? (size_t)order[j] : j] += vis[k] ? a.contrib[j] : 0.f;
 }
 
+// What a sample of a mono path driver is worth (gpis_render_scene_s_paths, gpis_render_scene_s_nee[_paths], the per-sample E of the
+// RGB drivers where k_paths_accumulate runs on it, and their adaptive forms) — an accessor of gpis_frame_sum.hpp on the per-sample E
+// and the segments marched for the sample (NULL where the driver counts none or the caller wants none).  raw: E as the uniform
+// entries add it, unclamped; value: E after renderTile's clamp, as the adaptive entries add and account it; a clamped sample's
+// segments count too.
+struct PathValues {
+    const float *emission;
+    const uint32_t *segs;
+    GPIS_DEV float raw(size_t i) const { return emission[i]; }
+    GPIS_DEV float value(size_t i) const { return adaptive_clamp(raw(i)); }
+    GPIS_DEV uint32_t count(size_t i) const { return segs ? segs[i] : 0u; }
+};
+// The luminance plane k_rgb_adaptive_value leaves of a chunk of the RGB path driver: clamped there already, so value(i) is the
+// plane's float as it stands (clamping a luminance a second time can differ at 65536).  The statistics alone read it.
+struct LuminanceValues {
+    const float *luminance;
+    GPIS_DEV float value(size_t i) const { return luminance[i]; }
+};
+
+// one lane per pixel: sequential sum over its samples' E, in sample order
 __global__ void __launch_bounds__(256) k_paths_accumulate(SceneConst sc, size_t first_pixel, size_t n_pixels, const float *__restrict__ emission,
                                                           float *__restrict__ radiance_sum)
 {
-    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_pixels) return;
-    const uint32_t spp = sc.s.spp_count;
-    float acc = 0.f;
-    for (uint32_t k = 0; k < spp; ++k)
-        acc += emission[j * spp + k];
-    radiance_sum[scene_pixel(sc.s, first_pixel + j)] += acc;
+    frame_values_sum(sc, first_pixel, n_pixels, PathValues{emission, nullptr}, radiance_sum, nullptr);
 }
+
+// The mono path drivers and the RGB path driver under the adaptive schedule, behind the bounce loop of a chunk of records: the
+// per-pixel sum of the variable-count layout (the segments where `segs` is given; seg_count is then the caller's) and the tile
+// statistics.
+namespace gpis {
+GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_adaptive_sum(SceneConst sc, AdaptiveChunk ch, const float *__restrict__ emission,
+                                                                           const uint32_t *__restrict__ segs, float *__restrict__ radiance_sum,
+                                                                           uint32_t *__restrict__ sample_count, uint32_t *__restrict__ seg_count)
+{
+    adaptive_values_sum(sc, ch, PathValues{emission, segs}, radiance_sum, sample_count, seg_count);
+}
+GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_paths_adaptive_tile_stats(AdaptiveChunk ch, const float *__restrict__ emission,
+                                                                                  gpis_adaptive_record *__restrict__ records)
+{
+    adaptive_values_stats(ch, PathValues{emission, nullptr}, records);
+}
+GPIS_TU_KERNEL __global__ void __launch_bounds__(256) k_rgb_adaptive_stats(AdaptiveChunk ch, const float *__restrict__ luminance,
+                                                                           gpis_adaptive_record *__restrict__ records)
+{
+    adaptive_values_stats(ch, LuminanceValues{luminance}, records);
+}
+}   // namespace gpis
 
 // one lane per pixel: the sum of a per-sample count over its spp (the segments marched for a pixel's samples, path plus shadow: the
 // RGB path drivers and gpis_render_scene_s_nee_paths)

@@ -156,6 +156,30 @@ def check_uniform_schedule(pkg, med, drv, ob, uniform=None):
         assert info_tuple(got["info"]) == (passes, 0, W * H * S)
 
 
+def check_odd_spp_on_a_clipped_frame(pkg, med, drv, ob):
+    """9 x 6 from the default distance: 3 x 2 records, the last column and the last row of tiles clipped.  5 spp in steps of 2 under a
+    threshold no pass reaches are passes of 2, 2 and 1 samples: every record plans a single sample at last, and the uniform entry
+    runs odd counts beside it — per k for the composite, then the three passes' calls accumulated into one buffer."""
+    import torch
+    scene, settings = par.scene(ob, 5, 9, 6, cam_pos=(0.0, 0.0, 4.0)), ar.default_adaptive(spp_step=2, threshold=64)
+    want = composite(pkg, med, drv, scene, settings)
+    describe("9 x 6", want)
+    assert want["records"].shape == (2, 3) and [np.unique(c).tolist() for c in want["counts"]] == [[2], [2], [1]]
+    assert want["radiance_sum"].max() > 0
+    par.assert_no_clamp(want)
+    got = adaptive(pkg, med, drv, scene, settings)
+    equal(got, want, drv.keys)
+    assert info_tuple(got["info"]) == (3, 0, 9 * 6 * 5)
+    into = (torch.zeros(6 * 9, dtype=torch.float32, device="cuda"), torch.zeros(6 * 9, dtype=torch.int32, device="cuda"))
+    for k0, n in ((0, 2), (2, 2), (4, 1)):
+        part = scene.copy()
+        part["spp_begin"], part["spp_count"] = k0, n
+        img, segs = drv.uniform(pkg, med, part, into=into)
+    assert np.array_equal(got["radiance_sum"].view(np.uint32), img.view(np.uint32))
+    if segs is not None:
+        assert segs.max() > 0 and np.array_equal(got["seg_count"], segs)
+
+
 def check_one_bounce(pkg, med, drv, ob):
     """max_path_bounces = 1: nothing is marched and every sample is zero; the plan step ends the frame after the first pass"""
     assert drv.max_bounces == 1

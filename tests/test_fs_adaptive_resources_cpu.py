@@ -3,7 +3,7 @@ inside libgpis_hip.so (no GPU needed), in the pattern of tests/test_paths_adapti
 their bodies with k_fs_scene and k_fs_paths, which sit at the edge of their register budget: the new ones must not spill a VGPR and
 must keep the one FsLds that lets four one-wave workgroups share a CU, and the kernels of the commit before keep what they had —
 no scratch, 37 488 B of LDS, no VGPR spill and the same VGPR count.  The weight-space adaptive kernels, whose sum and statistics
-now share their bodies with this medium's (gpis_adaptive_sum.hpp), are still there once each."""
+now share their bodies with this medium's (gpis_frame_sum.hpp), are still there once each."""
 import os
 
 import pytest

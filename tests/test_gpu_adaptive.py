@@ -184,6 +184,30 @@ def test_threshold_at_or_above_the_spp_is_uniform(env):
         assert (got["records"]["sample_index"] == S).all() and int(got["info"]["samples"]) == W * H * S
 
 
+@pytest.mark.parametrize("name", ["c0_full_records", "c1_guided_compact"])
+def test_odd_spp_on_a_clipped_frame(env, name):
+    """9 x 6 from the default distance: 3 x 2 records, the last column and the last row of tiles clipped.  5 spp in steps of 2 under a
+    threshold no pass reaches are passes of 2, 2 and 1 samples: every record plans a single sample at last, and gpis_render_scene_s
+    runs odd counts beside it — per k for the composite, then the three passes' calls accumulated into one buffer."""
+    import torch
+    pkg, ob = env
+    med = CASES[name][0](pkg)
+    scene, settings = ob.default_scene_s(9, 6, 5), ar.default_adaptive(spp_step=2, threshold=64)
+    want = _composite(pkg, med, scene, settings)
+    print(name, want["info"], "largest value", want["largest_value"], "image max", float(want["radiance_sum"].max()))
+    assert want["records"].shape == (2, 3) and [np.unique(c).tolist() for c in want["counts"]] == [[2], [2], [1]]
+    assert 0 < want["largest_value"] <= 65536 and want["hit_count"].max() > 0
+    got = _adaptive(pkg, med, scene, settings)
+    _equal(got, want)
+    assert (int(got["info"]["passes_rendered"]), int(got["info"]["stopped_early"]), int(got["info"]["samples"])) == (3, 0, 9 * 6 * 5)
+    into = (torch.zeros(6 * 9, dtype=torch.float32, device="cuda"), torch.zeros(6 * 9, dtype=torch.int32, device="cuda"))
+    for k0, n in ((0, 2), (2, 2), (4, 1)):
+        part = scene.copy()
+        part["spp_begin"], part["spp_count"] = k0, n
+        passes = _uniform(pkg, med, part, into)
+    assert np.array_equal(got["radiance_sum"].view(np.uint32), passes[0].view(np.uint32)) and np.array_equal(got["hit_count"], passes[1])
+
+
 def test_zero_radiance_stops_after_the_first_pass(env):
     pkg, ob = env
     got = _adaptive(pkg, _c0(pkg), _scene(ob, 48, light_radiance=0.0))

@@ -197,6 +197,33 @@ def test_threshold_at_or_above_the_spp_is_uniform(env):
     med.close()
 
 
+@pytest.mark.parametrize("name", ["grey_guided", "ramp_emission"])
+def test_odd_spp_on_a_clipped_frame(env, name):
+    """9 x 6 from the default distance: 3 x 2 records, the last column and the last row of tiles clipped.  5 spp in steps of 2 under a
+    threshold no pass reaches are passes of 2, 2 and 1 samples: every record plans a single sample at last, and
+    gpis_render_scene_s_paths_rgb runs odd counts beside it — per k for the composite, then the three passes' calls accumulated
+    into one buffer."""
+    import torch
+    pkg, ob = env
+    case, guide, bounces, _, _ = CASES[name]
+    med, albedo = _medium(pkg, case, guide=guide)
+    scene, settings = ob.default_scene_s(9, 6, 5), ar.default_adaptive(spp_step=2, threshold=64)
+    want = _composite(pkg, med, scene, albedo, bounces, settings)
+    print(name, want["info"], "clamped samples", int(want["clamped"].sum()), "image max", float(want["radiance_sum"].max()))
+    assert want["records"].shape == (2, 3) and [np.unique(c).tolist() for c in want["counts"]] == [[2], [2], [1]]
+    assert want["radiance_sum"].max() > 0 and want["seg_count"].max() > 0 and not want["clamped"].any()
+    got = _adaptive(pkg, med, scene, albedo, bounces, settings)
+    _equal(got, want)
+    assert (int(got["info"]["passes_rendered"]), int(got["info"]["stopped_early"]), int(got["info"]["samples"])) == (3, 0, 9 * 6 * 5)
+    into = (torch.zeros(3 * 6 * 9, dtype=torch.float32, device="cuda"), torch.zeros(6 * 9, dtype=torch.int32, device="cuda"))
+    for k0, n in ((0, 2), (2, 2), (4, 1)):
+        part = scene.copy()
+        part["spp_begin"], part["spp_count"] = k0, n
+        passes = _uniform(pkg, med, part, albedo, bounces, into=into)
+    med.close()
+    assert np.array_equal(got["radiance_sum"].view(np.uint32), passes[0].view(np.uint32)) and np.array_equal(got["seg_count"], passes[1])
+
+
 def test_zero_radiance_stops_after_the_first_pass(env):
     """without emission and with max_path_bounces = 1 nothing is marched and every sample is zero"""
     pkg, ob = env

@@ -183,6 +183,31 @@ def test_threshold_at_or_above_the_spp_is_uniform(env, driver):
     med.close()
 
 
+@pytest.mark.parametrize("driver", ["lambert", "paths"])
+def test_odd_spp_on_a_clipped_frame(env, driver):
+    """9 x 6 from the default distance: 3 x 2 records, the last column and the last row of tiles clipped.  5 spp in steps of 2 under a
+    threshold no pass reaches are passes of 2, 2 and 1 samples: every record plans a single sample at last, and the uniform driver
+    runs odd counts beside it — per k for the composite, then the three passes' calls accumulated into one buffer."""
+    import torch
+    pkg, ob = env
+    med = pkg.Medium(fa.medium(pkg))
+    scene, settings = ob.default_scene_s(9, 6, 5), ar.default_adaptive(spp_step=2, threshold=64)
+    want = fa.frame(lambda one: _uniform(pkg, med, driver, one), scene, settings)
+    print(driver, want["info"], "largest value", want["largest_value"], "image max", float(want["radiance_sum"].max()))
+    assert want["records"].shape == (2, 3) and [np.unique(c).tolist() for c in want["counts"]] == [[2], [2], [1]]
+    assert 0 < want["largest_value"] <= 65536 and want["hit_count"].max() > 0
+    got = _adaptive(pkg, med, driver, scene, settings)
+    _equal(got, want)
+    assert (int(got["info"]["passes_rendered"]), int(got["info"]["stopped_early"]), int(got["info"]["samples"])) == (3, 0, 9 * 6 * 5)
+    into = (torch.zeros(6 * 9, dtype=torch.float32, device="cuda"), torch.zeros(6 * 9, dtype=torch.int32, device="cuda"))
+    for k0, n in ((0, 2), (2, 2), (4, 1)):
+        part = scene.copy()
+        part["spp_begin"], part["spp_count"] = k0, n
+        passes = _uniform(pkg, med, driver, part, into)
+    med.close()
+    assert np.array_equal(got["radiance_sum"].view(np.uint32), passes[0].view(np.uint32)) and np.array_equal(got["hit_count"], passes[1])
+
+
 @pytest.mark.parametrize("name", ["lambert_renewal", "paths_renewal"])
 def test_chunk_independence(env, name):
     """GPIS_OPT_CHUNK_LOG2 8: a full record of the first pass (16 pixels x 16 samples) is exactly one chunk and the clipped bottom-row

@@ -83,6 +83,14 @@ def test_smallest_frame(env):
     med.close()
 
 
+@pytest.mark.parametrize("case, bounces", [("mis", 3), ("uni", 2)])
+def test_odd_spp_on_a_clipped_frame(env, case, bounces):
+    pkg, ob = env
+    med, surf = _medium(pkg, case)
+    pag.check_odd_spp_on_a_clipped_frame(pkg, med, pag.Nee(surf, bounces), ob)
+    med.close()
+
+
 def test_fixture(env):
     pkg, ob = env
     g = np.load(par.GOLDEN_NEE)

@@ -72,6 +72,14 @@ def test_smallest_frame(env):
     med.close()
 
 
+@pytest.mark.parametrize("config, guide, bounces", [("C0", False, 4), ("C1", True, 3)])
+def test_odd_spp_on_a_clipped_frame(env, config, guide, bounces):
+    pkg, ob = env
+    med = _medium(pkg, config, guide)
+    pag.check_odd_spp_on_a_clipped_frame(pkg, med, pag.Lambert(bounces), ob)
+    med.close()
+
+
 def test_fixture(env):
     pkg, ob = env
     g = np.load(par.GOLDEN_LAMBERT)
