@@ -932,6 +932,72 @@ extern int gpis_render_scene_s_nee_paths_adaptive(gpis_medium *m, const gpis_sce
                                                   float *radiance_sum, uint32_t *sample_count, uint32_t *seg_count,
                                                   gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
 
+/* gpis_surface_s per channel: the coloured conductor (ConductorBsdf.cpp:24-28, Fresnel.hpp:136-143: one reflectance per channel)
+ * under a coloured cap light.  64 bytes. */
+typedef struct gpis_surface_rgb_s {
+    float eta[3], k[3];        /* ConductorBsdf "eta", "k" */
+    float albedo[3];
+    float cap_radiance[3];     /* InfiniteSphereCap emission */
+    float cap_cos;             /* as gpis_surface_s.cap_cos */
+    float _pad[3];
+} gpis_surface_rgb_s;
+/* the reference's default conductor, copper: eta = (0.200438, 0.924033, 1.10221), k = (3.91295, 2.45285, 2.14219); albedo 1,
+ * cap_radiance 1, cap_cos 0.9781476 (a 12-degree cap).  Materials by name (ComplexIorList) are the loader's to resolve. */
+void gpis_default_surface_rgb(gpis_surface_rgb_s *surf);
+
+/* gpis_render_scene_s_nee_paths carried in RGB, with the medium's emission: the conductor NEE / MIS path estimator as the
+ * reference's integrator runs it for a ConductorBsdf, whose Fresnel term, albedo and light are Vec3f, on a medium whose weight and
+ * emission are Vec3f.  Accepts and refuses what gpis_render_scene_s_nee_paths does (handles, rows, tile-row shards, spp ranges,
+ * chunking, stream; GPIS_ERR_INVALID_ARG, nothing written, for max_path_bounces < 1, a NULL surf or radiance_sum3, cap_cos outside
+ * (-1, 1), a row range outside the image, a bad shard, a weight-space handle).
+ * Per sample, operation for operation in float with contraction off.  The stream, the draws and their order, the rays, the
+ * masks, the queries and the segments are those of gpis_render_scene_s_nee_paths step for step: no direction, pdf, heuristic or
+ * draw depends on colour.  thr[c] = 1, em[c] = 0.  Let E = "mean_emission is enabled" and B = max_path_bounces.  For b = 0, 1, ...:
+ *   1. sampleDistance with segment word b.  The last segment marched is b = B-2 when !E and b = B-1 when E: that segment can only
+ *      add its hit's emission; no estimator and no bounce follow it.  !ok ends the path and adds nothing.
+ *   2. Emission and weight: steps 3 and 4 of gpis_render_scene_s_paths_rgb verbatim — on a hit when E, e = emission(ro + rd * t)
+ *      as gpis_mean_color_emission_* evaluates it, em[c] = em[c] + (thr[c] * e[c]) with thr BEFORE the weight; then
+ *      thr[c] = thr[c] * weight[c]; `exited` ends the path.  Within a bounce the emission term is added before the NEE terms.
+ *   3. F[c] = albedo[c] * conductorReflectance(eta[c], k[c], wi.z): the scalar function of gpis_render_scene_s_nee per channel,
+ *      its eta == 0 && k == 0 -> 1 case included.
+ *   4. Light sample (schemes NEE, MIS): f[c] = F[c] * neePDF(half vector).  The shadow segment is marched iff f is not zero in
+ *      every channel (Vec3f == 0.0f, Vec.hpp:452-458) and the chord exists.  lightF[c] = f[c] * cap_radiance[c] / pdf_l, times the
+ *      scalar power heuristic unless the scheme is NEE.
+ *   5. Phase sample (schemes UNI, MIS): phaseF[c] = cap_radiance[c] * F[c], times the scalar heuristic unless the scheme is UNI.
+ *   6. L[c] = the visible ones of lightF[c] and phaseF[c], the light's first; L = 0 for both iff cap_radiance is zero in every
+ *      channel (TraceBase.cpp:374, 410 on a Vec3f).  em[c] = em[c] + thr[c] * L[c] with the thr of step 2.
+ *   7. The bounce: thr[c] = thr[c] * F[c]; the path ends when max(thr[0..2]) == 0 (PathTracer.cpp:143; Vec::max: m = thr[0], then
+ *      each larger component); the rest is steps 3 and 4 of gpis_render_scene_s_nee_paths, the next ray (and its jitter) following
+ *      only if its segment b+1 is one of those step 1 marches.
+ * There is NO Russian roulette, as in gpis_render_scene_s_nee_paths.
+ * Each pixel's sum of em[c], taken per channel in sample order from zero, is ACCUMULATED into radiance_sum3[3*(y*width+x)+c]
+ * (device pointer, 3*height*width floats) once per chunk of samples, and per pixel the segments marched (path, light shadow and
+ * phase shadow segments) into seg_count[height*width] (device pointer; may be NULL).  Image and counts depend neither on how a
+ * frame is cut into calls (rows, shards, spp ranges) or chunks (GPIS_OPT_CHUNK_LOG2) nor on any tuning option.
+ * Consequences: with eta[c] = eta, k[c] = k, albedo[c] = albedo, cap_radiance[c] = cap_radiance on a medium without emission
+ * whose three weight channels are equal, every channel and seg_count equal gpis_render_scene_s_nee_paths bit for bit; on any
+ * medium without emission, channel c equals that entry given channel c's surface wherever weight[c] == weight[0], as long as
+ * the channels agree on which f and which throughputs are zero (a light segment or a path that one channel alone keeps alive is
+ * marched here and not by that channel's mono frame, which moves seg_count and the later draws); with E, max_path_bounces = 1
+ * renders first-hit emission (with !E it adds zeros and marches nothing).  Asynchronous on `stream`. */
+int gpis_render_scene_s_nee_paths_rgb(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_rgb_s *surf, int max_path_bounces,
+                                      float *radiance_sum3, uint32_t *seg_count, void *stream);
+
+/* gpis_render_scene_s_nee_paths_rgb — the same estimator, sample for sample — under the sample schedule of
+ * gpis_render_scene_s_adaptive.  Pass loop, records, RNG, sample numbering (k = s->spp_begin + sample_index + i), chunking and
+ * the synchronisation once per pass are those of gpis_render_scene_s_nee_paths_adaptive; the Vec3f clamp (any NaN, +-infinite or
+ * > 65536 component zeroes the sample; its segments still count), the statistics on the luminance of the clamped value and the
+ * image / sample_count / seg_count layout are those of gpis_render_scene_s_paths_rgb_adaptive.
+ * GPIS_ERR_INVALID_ARG, nothing written: everything gpis_render_scene_s_nee_paths_rgb refuses, a NULL a / sample_count, rows other
+ * than the whole image, shard_count > 1, spp_step == 0, threshold < 2, spp_count == 0.  GPIS_ERR_UNSUPPORTED and GPIS_ERR_DEVICE as
+ * gpis_render_scene_s_nee_paths_adaptive.
+ * Consequence: with threshold >= S and nothing clamped the image equals bit for bit gpis_render_scene_s_nee_paths_rgb called once
+ * per pass with that pass's (spp_begin, spp_count), accumulated into one buffer. */
+extern int gpis_render_scene_s_nee_paths_rgb_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a,
+                                                      const gpis_surface_rgb_s *surf, int max_path_bounces,
+                                                      float *radiance_sum3, uint32_t *sample_count, uint32_t *seg_count,
+                                                      gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
+
 /* ---- weight-space GP medium (WeightSpaceGaussianProcessMedium.cpp, WeightSpaceGaussianProcess.cpp) --------------------
  * The field of one realization is  f(p) = sqrt(cov(p,p)) * (sqrt(2/N) * sum_i w_i cos((d_i . p) * omega_i + phi_i)) + mean(p)
  * with N random Fourier features of the squared-exponential covariance (WSG:120-127, 160-240).  A realization is fixed by the

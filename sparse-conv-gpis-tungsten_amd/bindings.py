@@ -218,6 +218,9 @@ SCENE_S = np.dtype([
 SURFACE_S = np.dtype([
     ("eta", "<f4"), ("k", "<f4"), ("albedo", "<f4"), ("cap_cos", "<f4"), ("cap_radiance", "<f4"), ("_pad", "<f4", 3),
 ], align=True)
+SURFACE_RGB_S = np.dtype([
+    ("eta", "<f4", 3), ("k", "<f4", 3), ("albedo", "<f4", 3), ("cap_radiance", "<f4", 3), ("cap_cos", "<f4"), ("_pad", "<f4", 3),
+], align=True)
 
 # variance-driven adaptive sampling (gpis_render_scene_s_adaptive)
 ADAPTIVE_S = np.dtype([("spp_step", "<u4"), ("threshold", "<u4"), ("seed", "<u4"), ("_pad", "<u4")], align=True)
@@ -259,6 +262,15 @@ def default_surface_s():
     return s
 
 
+def default_surface_rgb():
+    """gpis_default_surface_rgb without loading the library: the reference's default conductor (copper, ConductorBsdf.cpp:24-28),
+    albedo 1, and the 12-degree cap of default_surface_s with radiance 1."""
+    s = np.zeros((), dtype=SURFACE_RGB_S)
+    s["eta"], s["k"] = (0.200438, 0.924033, 1.10221), (3.91295, 2.45285, 2.14219)
+    s["albedo"], s["cap_radiance"], s["cap_cos"] = 1.0, 1.0, 0.9781476
+    return s
+
+
 # ---- weight-space GP medium (include/gpis.h: gpis_ws_*) ----
 WS_MAX_BASIS = 1024
 
@@ -291,7 +303,7 @@ _EXPECTED_SIZES = {
     "gpis_params": PARAMS.itemsize, "gpis_mean": MEAN.itemsize, "gpis_ray_in": RAY_IN.itemsize,
     "gpis_seg_out": SEG_OUT.itemsize, "gpis_cond_coeff": COND_COEFF.itemsize, "gpis_query": QUERY.itemsize,
     "gpis_nee_query": NEE_QUERY.itemsize, "gpis_derived": DERIVED.itemsize, "gpis_scene_s": SCENE_S.itemsize,
-    "gpis_surface_s": SURFACE_S.itemsize, "gpis_ramp": RAMP.itemsize,
+    "gpis_surface_s": SURFACE_S.itemsize, "gpis_surface_rgb_s": SURFACE_RGB_S.itemsize, "gpis_ramp": RAMP.itemsize,
     "gpis_fs_state": FS_STATE.itemsize, "gpis_guide_info": GUIDE_INFO.itemsize,
     "gpis_ws_params": WS_PARAMS.itemsize, "gpis_ws_query": WS_QUERY.itemsize,
     "gpis_adaptive_s": ADAPTIVE_S.itemsize, "gpis_adaptive_record": ADAPTIVE_RECORD.itemsize, "gpis_adaptive_info": ADAPTIVE_INFO.itemsize,
@@ -446,6 +458,7 @@ class GpisLib:
         "gpis_render_scene_s_paths_rgb_adaptive", "gpis_adaptive_rgb_value_host",
         "gpis_ws_render_scene_s_adaptive", "gpis_ws_render_scene_s_paths_adaptive",
         "gpis_render_scene_s_paths_adaptive", "gpis_render_scene_s_nee_paths_adaptive",
+        "gpis_default_surface_rgb", "gpis_render_scene_s_nee_paths_rgb", "gpis_render_scene_s_nee_paths_rgb_adaptive",
         "gpis_fs_render_scene_s_adaptive", "gpis_fs_render_scene_s_paths_adaptive",
         "gpis_network_mean_host", "gpis_network_mean_batch", "gpis_bake_mean_network",
     ]
@@ -547,6 +560,10 @@ class GpisLib:
         L.gpis_ws_render_scene_s_adaptive.argtypes = [vp, vp, vp, i32] + [vp] * 6
         L.gpis_render_scene_s_paths_adaptive.argtypes = [vp, vp, vp, i32, ctypes.c_float] + [vp] * 5
         L.gpis_render_scene_s_nee_paths_adaptive.argtypes = [vp, vp, vp, vp, i32] + [vp] * 6
+        L.gpis_default_surface_rgb.argtypes = [vp]
+        L.gpis_default_surface_rgb.restype = None
+        L.gpis_render_scene_s_nee_paths_rgb.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+        L.gpis_render_scene_s_nee_paths_rgb_adaptive.argtypes = [vp, vp, vp, vp, i32] + [vp] * 6
         L.gpis_ws_render_scene_s_paths_adaptive.argtypes = [vp, vp, vp, i32, i32, ctypes.c_float] + [vp] * 5
         L.gpis_fs_render_scene_s_adaptive.argtypes = [vp] * 9
         L.gpis_fs_render_scene_s_paths_adaptive.argtypes = [vp, vp, vp, i32, ctypes.c_float] + [vp] * 6
@@ -826,6 +843,22 @@ class Medium:
         surface = np.array(surface, dtype=SURFACE_S).reshape(())
         return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_nee_paths_adaptive", scene, (_ptr(surface), int(max_bounces)),
                             has_count=True, want_count=want_segs, adaptive=_adaptive_s(adaptive), want_records=want_records)
+
+    def render_scene_s_nee_paths_rgb(self, scene, surface, max_bounces, want_segs=False):
+        """One call of the RGB conductor NEE / MIS path driver with the medium's emission (gpis_render_scene_s_nee_paths_rgb) into
+        zeroed device buffers: the float32 sum-of-radiance image (height, width, 3) of the rows, shard and samples `scene` selects,
+        and per pixel the segments marched (path plus light and phase shadow segments) when asked.  `surface`: SURFACE_RGB_S."""
+        surface = np.array(surface, dtype=SURFACE_RGB_S).reshape(())
+        return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_nee_paths_rgb", scene, (_ptr(surface), int(max_bounces)), channels=3,
+                            has_count=True, want_count=want_segs)
+
+    def render_scene_s_nee_paths_rgb_adaptive(self, scene, surface, max_bounces, adaptive=None, want_segs=False, want_records=False):
+        """One frame of the RGB conductor NEE / MIS path driver under the reference's adaptive sample schedule
+        (gpis_render_scene_s_nee_paths_rgb_adaptive) into zeroed device buffers: (radiance_sum, sample_count[, seg_count][, records],
+        info) as render_scene_s_paths_rgb_adaptive returns them."""
+        surface = np.array(surface, dtype=SURFACE_RGB_S).reshape(())
+        return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_nee_paths_rgb_adaptive", scene, (_ptr(surface), int(max_bounces)),
+                            channels=3, has_count=True, want_count=want_segs, adaptive=_adaptive_s(adaptive), want_records=want_records)
 
     def fs_render_scene_s_adaptive(self, scene, adaptive=None, want_hits=False, want_records=False):
         """One frame of the function-space scene-S frame driver under the reference's adaptive sample schedule

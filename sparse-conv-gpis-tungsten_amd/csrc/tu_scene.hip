@@ -5,7 +5,8 @@
 //   the Lambert frame               gpis_render_scene_s, gpis_render_scene_s_adaptive, gpis_reserve_scene_workspace
 //   the Lambert multi-bounce paths  gpis_render_scene_s_paths, gpis_render_scene_s_paths_adaptive, gpis_render_scene_s_paths_rgb,
 //                                   gpis_render_scene_s_paths_rgb_adaptive
-//   the conductor NEE / MIS frames  gpis_render_scene_s_nee, gpis_render_scene_s_nee_paths, gpis_render_scene_s_nee_paths_adaptive
+//   the conductor NEE / MIS frames  gpis_render_scene_s_nee, gpis_render_scene_s_nee_paths, gpis_render_scene_s_nee_paths_adaptive,
+//                                   gpis_render_scene_s_nee_paths_rgb, gpis_render_scene_s_nee_paths_rgb_adaptive (gpis_cond_rgb.hpp)
 //   the function-space frames       gpis_fs_render_scene_s, gpis_fs_render_scene_s_paths (fused kernels: tu_fs_scene.hip, tu_fs_paths.hip)
 #include <hip/hip_runtime.h>
 
@@ -483,13 +484,31 @@ __device__ __forceinline__ float conductor_reflectance(float eta, float k, float
 }
 __device__ __forceinline__ float power_heuristic(float pdf0, float pdf1) { return (pdf0 * pdf0) / (pdf0 * pdf0 + pdf1 * pdf1); }
 
-struct NeeAux {            // per sample, between the set-up and the shading kernel
+template <int N>           // channels: 1 (gpis_surface_s) or 3 (gpis_surface_rgb_s, gpis_cond_rgb.hpp)
+struct NeeAuxN {           // per sample, between the set-up and the shading kernel
     float d[3];            // sampled light direction
     float w[3];            // mirror direction of the phase sample
-    float F;               // albedo * conductorReflectance(wi.z)
+    float F[N];            // albedo * conductorReflectance(wi.z), per channel
     float v1, v2;          // the next two draws of the sample's stream (march jitters of the shadow segments)
     int32_t scheme;
 };
+using NeeAux = NeeAuxN<1>;
+// fn(c) for every channel, stated without a loop: the mono kernels compile to the code they had before the estimator had channels
+template <int N, typename Fn>
+__device__ __forceinline__ void for_channels(Fn fn)
+{
+    static_assert(N == 1 || N == 3, "one channel or RGB");
+    fn(0);
+    if constexpr (N == 3) { fn(1); fn(2); }
+}
+// channel c of a surface: the mono surface has one
+__device__ __forceinline__ float surface_F(const gpis_surface_s &sf, int, float cosThetaI) { return sf.albedo * conductor_reflectance(sf.eta, sf.k, cosThetaI); }
+__device__ __forceinline__ float surface_F(const gpis_surface_rgb_s &sf, int c, float cosThetaI)
+{
+    return sf.albedo[c] * conductor_reflectance(sf.eta[c], sf.k[c], cosThetaI);
+}
+__device__ __forceinline__ float surface_cap_radiance(const gpis_surface_s &sf, int) { return sf.cap_radiance; }
+__device__ __forceinline__ float surface_cap_radiance(const gpis_surface_rgb_s &sf, int c) { return sf.cap_radiance[c]; }
 struct NeeArrays {
     gpis_cond_coeff *coeff;
     gpis_nee_query *q_half, *q_normal;
@@ -507,8 +526,10 @@ struct NeeArrays {
 // inside the cap, drawn from g — z, then the disk pairs — for the schemes NEE and MIS) with its half-vector query, and the mirror
 // direction of ConductorBsdf::sample for EVERY scheme (the path driver bounces along it) with, for UNI and MIS, the test whether
 // it sees the cap and the query at the sampled normal.  Fills x but v1 / v2; writes b.q_half[i] / b.q_normal[i] where wanted.
-__device__ __forceinline__ void nee_setup_sample(const SceneConst &sc, const gpis_surface_s &sf, const gpis_ray_in &ray, const gpis_seg_out &o,
-                                                 Pcg32 &g, size_t i, const NeeArrays &b, NeeAux &x, uint8_t &wl, uint8_t &wp, uint8_t &wn)
+// Only F depends on the channel.
+template <int N, typename Surface>
+__device__ __forceinline__ void nee_setup_sample(const SceneConst &sc, const Surface &sf, const gpis_ray_in &ray, const gpis_seg_out &o,
+                                                 Pcg32 &g, size_t i, const NeeArrays &b, NeeAuxN<N> &x, uint8_t &wl, uint8_t &wp, uint8_t &wn)
 {
     x.scheme = o.scheme;
     const V3 capDir = v3(sc.light[0], sc.light[1], sc.light[2]);
@@ -516,7 +537,7 @@ __device__ __forceinline__ void nee_setup_sample(const SceneConst &sc, const gpi
     const Frame fr = frame_from_normal(n);
     const V3 dir = v3(ray.dir[0], ray.dir[1], ray.dir[2]);
     const V3 wi = normalized(to_local(fr, v3(-dir.x, -dir.y, -dir.z)));
-    x.F = sf.albedo * conductor_reflectance(sf.eta, sf.k, wi.z);
+    for_channels<N>([&](int c) __attribute__((always_inline)) { x.F[c] = surface_F(sf, c, wi.z); });
     gpis_nee_query q;
     memset(&q, 0, sizeof q);
     q.ray_dir[0] = dir.x; q.ray_dir[1] = dir.y; q.ray_dir[2] = dir.z;
@@ -565,30 +586,41 @@ __device__ __forceinline__ void nee_setup_sample(const SceneConst &sc, const gpi
 }
 
 // After the neePDF / neeGrad launches, for a sample with want_light or want_phase: the shadow segments that are marched (gl, gp;
-// the light's takes the jitter x.v1, the phase's the next one) and what each adds to L when it is visible.
-__device__ __forceinline__ void nee_shade_sample(const SceneConst &sc, const gpis_surface_s &sf, const gpis_ray_in &ray, const gpis_seg_out &o,
-                                                 const NeeAux &x, size_t i, const NeeArrays &b, uint8_t &gl, uint8_t &gp)
+// the light's takes the jitter x.v1, the phase's the next one) and what each adds to L when it is visible: channel c into
+// contrib_light / contrib_phase[c * plane + i].  The light's segment is marched unless f is zero in EVERY channel (Vec3f == 0.0f,
+// Vec.hpp:452-458); the pdfs and the heuristics are scalars.
+template <int N, typename Surface>
+__device__ __forceinline__ void nee_shade_sample(const SceneConst &sc, const Surface &sf, const gpis_ray_in &ray, const gpis_seg_out &o,
+                                                 const NeeAuxN<N> &x, size_t i, const NeeArrays &b, float *contrib_light, float *contrib_phase, size_t plane,
+                                                 uint8_t &gl, uint8_t &gp)
 {
     const float pdf_l = (0.5f * (1.0f / 3.1415926536f)) / (1.0f - sf.cap_cos);
     const V3 p = v3(o.p[0], o.p[1], o.p[2]);
     const gpis_ray_in sh0 = scene_next_ray(ray, o);      // handleVolume's copy of the state: segment word + 1
     if (b.want_light[i]) {
         const float pdf = b.pdf_half[i];
-        const float f = x.F * pdf;
+        float f[N];
+        bool some = false;
+        for_channels<N>([&](int c) __attribute__((always_inline)) {
+            f[c] = x.F[c] * pdf;
+            some = some || f[c] != 0.0f;
+        });
         float t0, t1;
         const V3 d = v3(x.d[0], x.d[1], x.d[2]);
-        if (f != 0.0f && sphere_chord(p, d, sc.s.bound_radius, t0, t1)) {
+        if (some && sphere_chord(p, d, sc.s.bound_radius, t0, t1)) {
             gpis_ray_in sh = sh0;
             sh.dir[0] = d.x; sh.dir[1] = d.y; sh.dir[2] = d.z;
             sh.far_t = t1;
             sh.u_jitter = x.v1;
             sh.last_aniso[0] = (double)b.grad_half[3 * i]; sh.last_aniso[1] = (double)b.grad_half[3 * i + 1]; sh.last_aniso[2] = (double)b.grad_half[3 * i + 2];
             b.shadow_light[i] = sh;
-            const float e = 1.f * sf.cap_radiance;
-            float lightF = f * e / pdf_l;
-            if (x.scheme != GPIS_NEE)
-                lightF *= power_heuristic(pdf_l, pdf);
-            b.contrib_light[i] = lightF;
+            for_channels<N>([&](int c) __attribute__((always_inline)) {
+                const float e = 1.f * surface_cap_radiance(sf, c);
+                float lightF = f[c] * e / pdf_l;
+                if (x.scheme != GPIS_NEE)
+                    lightF *= power_heuristic(pdf_l, pdf);
+                contrib_light[c * plane + i] = lightF;
+            });
             gl = 1;
         }
     }
@@ -601,11 +633,13 @@ __device__ __forceinline__ void nee_shade_sample(const SceneConst &sc, const gpi
         sh.far_t = t1;
         sh.u_jitter = gl ? x.v2 : x.v1;
         b.shadow_phase[i] = sh;
-        const float e = 1.f * sf.cap_radiance;
-        float phaseF = e * x.F;
-        if (x.scheme != GPIS_UNI)
-            phaseF *= power_heuristic(b.pdf_normal[i], pdf_l);
-        b.contrib_phase[i] = phaseF;
+        for_channels<N>([&](int c) __attribute__((always_inline)) {
+            const float e = 1.f * surface_cap_radiance(sf, c);
+            float phaseF = e * x.F[c];
+            if (x.scheme != GPIS_UNI)
+                phaseF *= power_heuristic(b.pdf_normal[i], pdf_l);
+            contrib_phase[c * plane + i] = phaseF;
+        });
         gp = 1;
     }
 }
@@ -648,7 +682,7 @@ __global__ void __launch_bounds__(256) k_nee_shade(SceneConst sc, gpis_surface_s
     if (i >= n_samples) return;
     uint8_t gl = 0, gp = 0;
     if (b.want_light[i] || b.want_phase[i])
-        nee_shade_sample(sc, sf, a.rays[i], a.seg[i], b.aux[i], i, b, gl, gp);
+        nee_shade_sample(sc, sf, a.rays[i], a.seg[i], b.aux[i], i, b, b.contrib_light, b.contrib_phase, 0, gl, gp);
     b.go_light[i] = gl;
     b.go_phase[i] = gp;
 }
@@ -713,14 +747,14 @@ __global__ void __launch_bounds__(256) k_nee_paths_shade(SceneConst sc, gpis_sur
         const gpis_ray_in ray = a.rays[i];
         const NeeAux x = b.aux[i];
         if (b.want_light[i] || b.want_phase[i])
-            nee_shade_sample(sc, sf, ray, o, x, i, b, gl, gp);
+            nee_shade_sample(sc, sf, ray, o, x, i, b, b.contrib_light, b.contrib_phase, 0, gl, gp);
         c.segs[i] += (uint32_t)gl + (uint32_t)gp;
         Pcg32 g;
         g.state = a.rng[i];
         for (int k = 0; k < (int)gl + (int)gp; ++k)     // one jitter per shadow segment that is marched
             (void)g.next_i();
         // the bounce: no Russian roulette, no neePDF of the mirror direction (the reference's value is unused)
-        const float thr = c.thr_hit[i] * x.F;
+        const float thr = c.thr_hit[i] * x.F[0];
         a.throughput[i] = thr;
         float t0, t1;
         const V3 w = v3(x.w[0], x.w[1], x.w[2]);
@@ -747,6 +781,10 @@ __global__ void __launch_bounds__(256) k_nee_paths_gather(float cap_radiance, si
     if (b.go_light[i] || b.go_phase[i])
         a.emission[i] = a.emission[i] + c.thr_hit[i] * nee_gather_sample(cap_radiance, i, b);
 }
+
+// ---- the same bounce loop in RGB (gpis_render_scene_s_nee_paths_rgb): k_cond_rgb_setup, k_cond_rgb_emit, k_cond_rgb_shade,
+// k_cond_rgb_gather
+#include "gpis_cond_rgb.hpp"
 
 // ---- scene S driver ----------------------------------------------------------------------
 extern "C" void gpis_default_scene_s(gpis_scene_s *s, uint32_t width, uint32_t height, uint32_t spp)
@@ -1453,14 +1491,14 @@ struct NeeWs {
     NeePathArrays c;
 };
 // the layout of stage[3] for chunks of up to ns_max samples
-static void nee_carve(NeeWs &W, size_t ns_max, bool paths)
+static void nee_carve(NeeWs &W, size_t ns_max, bool paths, size_t aux_bytes = sizeof(NeeAux))
 {
     size_t off = 0;
     auto carve = [&](size_t bytes) { return ws_carve(off, bytes); };
     W.o_rays = carve(ns_max * sizeof(gpis_ray_in)); W.o_seg = carve(ns_max * sizeof(gpis_seg_out));
     W.o_rng = carve(ns_max * 8); W.o_thr = carve(ns_max * 4); W.o_em = carve(ns_max * 4); W.o_alive = carve(ns_max);
     W.o_coeff = carve(ns_max * sizeof(gpis_cond_coeff)); W.o_qh = carve(ns_max * sizeof(gpis_nee_query)); W.o_qn = carve(ns_max * sizeof(gpis_nee_query));
-    W.o_aux = carve(ns_max * sizeof(NeeAux)); W.o_shl = carve(ns_max * sizeof(gpis_ray_in)); W.o_shp = carve(ns_max * sizeof(gpis_ray_in));
+    W.o_aux = carve(ns_max * aux_bytes); W.o_shl = carve(ns_max * sizeof(gpis_ray_in)); W.o_shp = carve(ns_max * sizeof(gpis_ray_in));
     W.o_ph = carve(ns_max * 4); W.o_gh = carve(ns_max * 12); W.o_pn = carve(ns_max * 4); W.o_cl = carve(ns_max * 4); W.o_cp = carve(ns_max * 4);
     for (int k = 0; k < 7; ++k) W.o_f[k] = carve(ns_max);
     W.o_th = W.o_segs = 0;
@@ -1485,6 +1523,20 @@ static void nee_bind(gpis_medium *m, NeeWs &W)
     b.go_light = (uint8_t *)(ws + W.o_f[3]); b.go_phase = (uint8_t *)(ws + W.o_f[4]); b.vis_light = (uint8_t *)(ws + W.o_f[5]); b.vis_phase = (uint8_t *)(ws + W.o_f[6]);
     c.thr_hit = (float *)(ws + W.o_th); c.segs = (uint32_t *)(ws + W.o_segs);
 }
+// the light and the phase estimator of the hits of one march: neePDF / neeGrad between set-up and shade, then the shadow marches
+static int nee_queries(gpis_medium *m, const NeeArrays &b, size_t ns, hipStream_t st)
+{
+    ProfScope prof(m, 2, st);
+    launch::nee(nee_instance(m->host_model), m->d_model.p, ns, b.q_half, b.pdf_half, b.grad_half, m->d_counters.p, b.want_light, st);
+    if (int r = launch_check("k_nee")) return r;
+    launch::nee(nee_instance(m->host_model), m->d_model.p, ns, b.q_normal, b.pdf_normal, nullptr, m->d_counters.p, b.want_pdf_normal, st);
+    return launch_check("k_nee");
+}
+static int nee_shadow_marches(gpis_medium *m, const NeeArrays &b, size_t ns, hipStream_t st, int hint)
+{
+    if (int r = transmittance_impl(m, ns, b.shadow_light, b.vis_light, b.go_light, st, hint)) return r;
+    return transmittance_impl(m, ns, b.shadow_phase, b.vis_phase, b.go_phase, st, hint);
+}
 // One chunk of ns samples: `begin` (the driver's camera step), the estimator of one hit or the bounce loop, `finish` (its sums).
 // Each callback launches and returns its launch_check.
 template <typename Begin, typename Finish>
@@ -1496,27 +1548,15 @@ static int nee_chunk(gpis_medium *m, const SceneConst &sc, const gpis_surface_s 
     const NeeArrays &b = W.b;
     const NeePathArrays &c = W.c;
     int rc = GPIS_OK;
-    // the light and the phase estimator of the hits of one march: neePDF / neeGrad between set-up and shade, then the shadow marches
-    auto nee_queries = [&]() -> int {
-        ProfScope prof(m, 2, st);
-        launch::nee(nee_instance(m->host_model), m->d_model.p, ns, b.q_half, b.pdf_half, b.grad_half, m->d_counters.p, b.want_light, st);
-        if (int r = launch_check("k_nee")) return r;
-        launch::nee(nee_instance(m->host_model), m->d_model.p, ns, b.q_normal, b.pdf_normal, nullptr, m->d_counters.p, b.want_pdf_normal, st);
-        return launch_check("k_nee");
-    };
-    auto shadow_marches = [&](int hint) -> int {
-        if (int r = transmittance_impl(m, ns, b.shadow_light, b.vis_light, b.go_light, st, hint)) return r;
-        return transmittance_impl(m, ns, b.shadow_phase, b.vis_phase, b.go_phase, st, hint);
-    };
     if ((rc = begin())) return rc;
     if (!paths) {
         if ((rc = sample_distance_impl(m, ns, a.rays, a.seg, b.coeff, a.alive, st))) return rc;
         k_nee_setup<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b);
         if ((rc = launch_check("k_nee_setup"))) return rc;
-        if ((rc = nee_queries())) return rc;
+        if ((rc = nee_queries(m, b, ns, st))) return rc;
         k_nee_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b);
         if ((rc = launch_check("k_nee_shade"))) return rc;
-        if ((rc = shadow_marches(MARCH_COHERENT))) return rc;
+        if ((rc = nee_shadow_marches(m, b, ns, st, MARCH_COHERENT))) return rc;
         k_nee_gather<<<grid_of(ns, 256), 256, 0, st>>>(surf->cap_radiance, ns, a, b);
         if ((rc = launch_check("k_nee_gather"))) return rc;
     } else {
@@ -1528,10 +1568,10 @@ static int nee_chunk(gpis_medium *m, const SceneConst &sc, const gpis_surface_s 
             if ((rc = sample_distance_impl(m, ns, a.rays, a.seg, b.coeff, a.alive, st, hint))) return rc;
             k_nee_paths_setup<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, a, b, c);
             if ((rc = launch_check("k_nee_paths_setup"))) return rc;
-            if ((rc = nee_queries())) return rc;
+            if ((rc = nee_queries(m, b, ns, st))) return rc;
             k_nee_paths_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, bounce, max_path_bounces, a, b, c);
             if ((rc = launch_check("k_nee_paths_shade"))) return rc;
-            if ((rc = shadow_marches(hint))) return rc;
+            if ((rc = nee_shadow_marches(m, b, ns, st, hint))) return rc;
             k_nee_paths_gather<<<grid_of(ns, 256), 256, 0, st>>>(surf->cap_radiance, ns, a, b, c);
             if ((rc = launch_check("k_nee_paths_gather"))) return rc;
         }
@@ -1631,5 +1671,174 @@ extern "C" int gpis_render_scene_s_nee_paths_adaptive(gpis_medium *m, const gpis
                     return launch_check("k_paths_adaptive_begin");
                 },
                 [&] { return paths_adaptive_finish(sc, ch, st, W.a.emission, W.c.segs, radiance_sum, sample_count, seg_count, d_records); });
+        });
+}
+
+// ---- the conductor NEE / MIS path driver in RGB and its adaptive form.  The workspace is NeeWs's layout (its aux slots sized for
+// NeeAuxN<3>) followed by the colour planes of thr, thr_hit, em, contrib_light and contrib_phase (60 B per sample), on an emissive
+// medium the points, values and mask of the emission (37 B) and, for the adaptive entry, the clamped luminance and the clamp flag
+// of gpis_render_scene_s_paths_rgb_adaptive; the chunk body mirrors the path branch of nee_chunk around the kernels of
+// gpis_cond_rgb.hpp.
+struct CondRgbWs {
+    NeeWs nee;
+    size_t bytes;                      // of stage[3]
+    size_t o_thr, o_th, o_em, o_cl, o_cp, o_points, o_e3, o_emit, o_lum, o_clamped;
+    CondRgbArrays r;
+    float *lum;                        // adaptive entry only
+    uint8_t *clamped;
+};
+static void cond_rgb_carve(CondRgbWs &W, size_t ns_max, bool emissive, bool adaptive)
+{
+    nee_carve(W.nee, ns_max, true, sizeof(NeeAuxN<3>));
+    size_t off = W.nee.bytes;
+    auto carve = [&](size_t bytes) { return ws_carve(off, bytes); };
+    W.o_thr = carve(ns_max * 12); W.o_th = carve(ns_max * 12); W.o_em = carve(ns_max * 12); W.o_cl = carve(ns_max * 12); W.o_cp = carve(ns_max * 12);
+    W.o_points = W.o_e3 = W.o_emit = W.o_lum = W.o_clamped = 0;
+    if (emissive) { W.o_points = carve(ns_max * 24); W.o_e3 = carve(ns_max * 12); W.o_emit = carve(ns_max); }
+    if (adaptive) { W.o_lum = carve(ns_max * 4); W.o_clamped = carve(ns_max); }
+    W.r.plane = ns_max;
+    W.bytes = off;
+}
+static void cond_rgb_bind(gpis_medium *m, CondRgbWs &W)
+{
+    nee_bind(m, W.nee);
+    char *ws = (char *)m->stage[3].p;
+    CondRgbArrays &r = W.r;
+    r.thr = (float *)(ws + W.o_thr); r.thr_hit = (float *)(ws + W.o_th); r.em = (float *)(ws + W.o_em);
+    r.contrib_light = (float *)(ws + W.o_cl); r.contrib_phase = (float *)(ws + W.o_cp);
+    r.aux = (NeeAuxN<3> *)(ws + W.nee.o_aux);
+    r.points = (double *)(ws + W.o_points); r.e3 = (float *)(ws + W.o_e3); r.emit = (uint8_t *)(ws + W.o_emit);
+    W.lum = (float *)(ws + W.o_lum); W.clamped = (uint8_t *)(ws + W.o_clamped);
+}
+// One chunk of ns samples: `begin` (the camera step on W.nee.a), the bounce loop, `finish` (the driver's sums over W.r.em and
+// W.nee.c.segs).  On an emissive medium the segment of bounce max-1 is marched too: its hit can only emit.
+template <typename Begin, typename Finish>
+static int cond_rgb_chunk(gpis_medium *m, const SceneConst &sc, const gpis_surface_rgb_s *surf, const CondRgbWs &W, size_t ns, int max_path_bounces,
+                          hipStream_t st, Begin begin, Finish finish)
+{
+    const PathArrays &a = W.nee.a;
+    const NeeArrays &b = W.nee.b;
+    const NeePathArrays &c = W.nee.c;
+    const CondRgbArrays &r = W.r;
+    const int emissive = m->host_model.emission.enabled != 0 ? 1 : 0;
+    const int n_marched = emissive ? max_path_bounces : max_path_bounces - 1;
+    int rc = GPIS_OK;
+    if ((rc = begin())) return rc;
+    HIP_TRY(hipMemsetAsync(c.segs, 0, ns * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(r.em, 0, 3 * r.plane * sizeof(float), st));
+    for (int bounce = 0; bounce < n_marched; ++bounce) {
+        const int hint = bounce > 0 ? MARCH_SCATTERED : MARCH_COHERENT;
+        if ((rc = sample_distance_impl(m, ns, a.rays, a.seg, b.coeff, a.alive, st, hint))) return rc;
+        k_cond_rgb_setup<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, bounce, max_path_bounces, emissive, a, b, c, r);
+        if ((rc = launch_check("k_cond_rgb_setup"))) return rc;
+        if (emissive) {
+            if ((rc = gpis_mean_color_emission_batch(m, ns, r.points, nullptr, r.e3, st))) return rc;
+            k_cond_rgb_emit<<<grid_of(ns, 256), 256, 0, st>>>(ns, bounce, r);
+            if ((rc = launch_check("k_cond_rgb_emit"))) return rc;
+        }
+        if (bounce + 1 >= max_path_bounces) break;      // the extra last segment: no estimator and no bounce follow it
+        if ((rc = nee_queries(m, b, ns, st))) return rc;
+        k_cond_rgb_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, *surf, ns, bounce, n_marched, a, b, c, r);
+        if ((rc = launch_check("k_cond_rgb_shade"))) return rc;
+        if ((rc = nee_shadow_marches(m, b, ns, st, hint))) return rc;
+        k_cond_rgb_gather<<<grid_of(ns, 256), 256, 0, st>>>(surf->cap_radiance[0], surf->cap_radiance[1], surf->cap_radiance[2], ns, b, r);
+        if ((rc = launch_check("k_cond_rgb_gather"))) return rc;
+    }
+    return finish();
+}
+
+extern "C" void gpis_default_surface_rgb(gpis_surface_rgb_s *surf)
+{
+    memset(surf, 0, sizeof *surf);
+    const float eta[3] = {0.200438f, 0.924033f, 1.10221f}, k[3] = {3.91295f, 2.45285f, 2.14219f};     // ConductorBsdf.cpp:24-28: "Cu"
+    for (int c = 0; c < 3; ++c) {
+        surf->eta[c] = eta[c]; surf->k[c] = k[c];
+        surf->albedo[c] = 1.0f; surf->cap_radiance[c] = 1.0f;
+    }
+    surf->cap_cos = 0.9781476f;
+}
+
+extern "C" int gpis_render_scene_s_nee_paths_rgb(gpis_medium *m, const gpis_scene_s *s, const gpis_surface_rgb_s *surf, int max_path_bounces,
+                                                 float *radiance_sum3, uint32_t *seg_count, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && surf && radiance_sum3 && max_path_bounces >= 1);
+    CHECK_ARGS(scene_args_ok(s));
+    CHECK_ARGS(surf->cap_cos < 1.0f && surf->cap_cos > -1.0f);
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(m->mu);
+    HIP_TRY(hipSetDevice(m->device));
+    const SceneConst sc = make_scene_const(s);
+    const size_t total_pixels = scene_rows(*s) * s->width;
+    CondRgbWs W;
+    size_t chunk_pixels = 0;
+    int rc = GPIS_OK;
+    for (int l = chunk_log2(m, 27);; --l) {        // the chunks of gpis_render_scene_s_nee_paths (nee_frames)
+        chunk_pixels = chunk_pixels_of(l, s->spp_count, total_pixels);
+        cond_rgb_carve(W, chunk_pixels * s->spp_count, m->host_model.emission.enabled != 0, false);
+        if (try_stage(m, 3, W.bytes))
+            break;
+        if (l <= 20) return set_err(GPIS_ERR_DEVICE, "NEE driver: no memory for a 1 Mi-sample workspace");
+    }
+    if ((rc = ws_acquire(m, 0, st))) return rc;
+    cond_rgb_bind(m, W);
+    for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
+        const size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
+        const size_t ns = np * s->spp_count;
+        rc = cond_rgb_chunk(
+            m, sc, surf, W, ns, max_path_bounces, st,
+            [&] {
+                k_paths_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, p0, ns, W.nee.a);
+                return launch_check("k_paths_begin");
+            },
+            [&] {
+                if (seg_count) {
+                    k_scene_sum_u32<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, W.nee.c.segs, seg_count);
+                    if (int r = launch_check("k_scene_sum_u32")) return r;
+                }
+                k_paths_rgb_accumulate<0><<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, W.r.plane, W.r.em, radiance_sum3);
+                return launch_check("k_paths_rgb_accumulate");
+            });
+        if (rc) return rc;
+    }
+    return ws_release(m, 0, st);
+}
+
+extern "C" int gpis_render_scene_s_nee_paths_rgb_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a, const gpis_surface_rgb_s *surf,
+                                                          int max_path_bounces, float *radiance_sum3, uint32_t *sample_count, uint32_t *seg_count,
+                                                          gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && a && surf && radiance_sum3 && sample_count && max_path_bounces >= 1);
+    CHECK_ARGS(scene_args_ok(s));
+    CHECK_ARGS(surf->cap_cos < 1.0f && surf->cap_cos > -1.0f);
+    hipStream_t st = (hipStream_t)stream;
+    const SceneConst sc = make_scene_const(s);
+    CondRgbWs W;
+    return adaptive_passes(
+        MediumPasses{m, 27}, s, a, __func__, st, records, info,
+        [&](size_t n, bool &fits) {
+            cond_rgb_carve(W, n, m->host_model.emission.enabled != 0, true);
+            fits = try_stage(m, 3, W.bytes);
+            return (int)GPIS_OK;
+        },
+        [&]() {
+            cond_rgb_bind(m, W);
+            return (int)GPIS_OK;
+        },
+        [&](const AdaptiveChunk &ch, size_t ns, gpis_adaptive_record *d_records) {
+            return cond_rgb_chunk(
+                m, sc, surf, W, ns, max_path_bounces, st,
+                [&] {
+                    k_paths_adaptive_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, ch, ns, W.nee.a);
+                    return launch_check("k_paths_adaptive_begin");
+                },
+                [&] {
+                    k_rgb_adaptive_value<0><<<grid_of(ns, 256), 256, 0, st>>>(ns, W.r.plane, W.r.em, W.lum, W.clamped);
+                    if (int rc = launch_check("k_rgb_adaptive_value")) return rc;
+                    k_rgb_adaptive_accumulate<0><<<grid_of((size_t)ch.nrec * (kVarianceTile * kVarianceTile), 256), 256, 0, st>>>(
+                        sc, ch, W.r.plane, W.r.em, W.clamped, W.nee.c.segs, radiance_sum3, sample_count, seg_count);
+                    if (int rc = launch_check("k_rgb_adaptive_accumulate")) return rc;
+                    k_rgb_adaptive_stats<0><<<grid_of(ch.nrec, 256), 256, 0, st>>>(ch, W.lum, d_records);
+                    return launch_check("k_rgb_adaptive_stats");
+                });
         });
 }
