@@ -998,6 +998,77 @@ extern int gpis_render_scene_s_nee_paths_rgb_adaptive(gpis_medium *m, const gpis
                                                       float *radiance_sum3, uint32_t *sample_count, uint32_t *seg_count,
                                                       gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
 
+/* Materials chosen by GP id: the medium's phase-function table (GPM.cpp:119-125: "phase_function", then
+ * "additional_phase_functions"; GaussianProcessMedium::sampleDistance ends with sample.phase = _phaseFunctions[state.lastGPId],
+ * GPM.cpp:335), each entry a BRDFPhaseFunction over a ConductorBsdf or a LambertBsdf, under ONE light, gpis_surface_rgb_s's cap.
+ * The id of a hit is gpis_seg_out.gp_id: the slot the CSG minimum chose (has_mean_additional) or the surface / volume side of
+ * surf_vol_phase_separate (SCN.cpp:80-86). */
+#define GPIS_MAX_MATERIALS 4
+typedef enum gpis_material_type { GPIS_MATERIAL_CONDUCTOR = 0, GPIS_MATERIAL_LAMBERT = 1 } gpis_material_type;
+typedef struct gpis_material_rgb {   /* 48 bytes */
+    int32_t type;                    /* gpis_material_type */
+    float eta[3], k[3];              /* conductor only */
+    float albedo[3];
+    int32_t _pad[2];
+} gpis_material_rgb;
+typedef struct gpis_materials_s {    /* 224 bytes */
+    uint32_t n_materials;            /* 1 .. GPIS_MAX_MATERIALS: material[0] = the medium's phase function, 1.. = additional_phase_functions */
+    float cap_cos;                   /* the light: gpis_surface_rgb_s's cap */
+    float cap_radiance[3];
+    uint32_t _pad[3];
+    gpis_material_rgb material[GPIS_MAX_MATERIALS];
+} gpis_materials_s;
+/* n_materials = 2: material[0] the copper of gpis_default_surface_rgb (albedo 1), material[1] Lambert with albedo 0.8; the cap
+ * of gpis_default_surface_rgb (cap_cos 0.9781476, radiance 1). */
+void gpis_default_materials(gpis_materials_s *mats);
+
+/* gpis_render_scene_s_nee_paths_rgb with the material of every hit chosen by its GP id:
+ *     material[gp_id < n_materials ? gp_id : 0]
+ * (the reference indexes its table unchecked; the fallback is the Tungsten binding's rule).  Accepts and refuses what
+ * gpis_render_scene_s_nee_paths_rgb does, with `mats` in the place of `surf` (cap_cos outside (-1, 1) included), and refuses
+ * (GPIS_ERR_INVALID_ARG, nothing written) n_materials outside 1 .. GPIS_MAX_MATERIALS and a type outside gpis_material_type in
+ * any of the n_materials entries.
+ * Per sample, operation for operation in float with contraction off.  Everything up to the material is
+ * gpis_render_scene_s_nee_paths_rgb verbatim: the PCG32 stream and the camera step, the segment words, step 1 (which segments are
+ * marched, with and without emission), step 2 (the emission with thr BEFORE the weight, then thr[c] = thr[c] * weight[c]), no
+ * Russian roulette, one jitter per shadow segment that is marched (the light's first), and the copy of the state at the hit that
+ * the shadow segments and the next segment start from (segment word + 1, last_gp_id = the hit's id).  Then, per hit:
+ *   CONDUCTOR: steps 3-7 of gpis_render_scene_s_nee_paths_rgb with the material's eta, k, albedo and the table's cap.
+ *   LAMBERT (BRDFPhaseFunction over LambertBsdf, LambertBsdf.cpp:27-68, under a non-Dirac light): both estimators run, with the
+ *   power heuristic, WHATEVER scheme the segment reports (TraceBase.cpp:354, 380, 396, 415 ask isSpecular() first), and there is
+ *   no neePDF / neeGrad query.  Frame and wi as in the conductor step; pdf_l = (0.5f * (1.0f/3.1415926536f)) / (1.0f - cap_cos).
+ *     L1. Light sample.  The cap direction d by the draws of the conductor's light sample (z, then the disk pairs), always;
+ *         wo = normalized(to_local(frame, d)); f[c] = albedo[c] * (1.0f/3.1415926536f) * wo.z if wi.z > 0 && wo.z > 0, else 0.
+ *         The shadow segment is marched iff some f[c] != 0 and the chord from the hit along d exists; it starts from the state
+ *         copy with last_aniso = the hit's own aniso (no evalGrad: TraceBase.cpp:371 is specular-only).
+ *         lightF[c] = f[c] * cap_radiance[c] / pdf_l, times power_heuristic(pdf_l, wo.z * (1.0f/3.1415926536f)).
+ *     L2. Phase sample, only if wi.z > 0 (otherwise no draws).  One cosine direction wo_p by unit-disk rejection (dx, dy pairs
+ *         until d2 = dx*dx + dy*dy satisfies d2 < 1; z = sqrtf(max(1 - d2, 0))), w_p = normalized(to_global(frame, wo_p)).  It
+ *         counts iff !(dot(w_p, capDir) < cap_cos) and the chord along w_p exists; then its shadow segment is marched.
+ *         phaseF[c] = cap_radiance[c] * albedo[c], times power_heuristic(wo_p.z * (1.0f/3.1415926536f), pdf_l).
+ *     L3. L and em[c] = em[c] + thr[c] * L[c] as step 6 of gpis_render_scene_s_nee_paths_rgb (the all-channels-zero cap_radiance
+ *         rule included).
+ *     L4. The bounce (handleVolume, TraceBase.cpp:552, draws a second, independent sample): wi.z <= 0 ends the path without a
+ *         draw; otherwise another disk-rejection cosine direction w and thr[c] = thr[c] * albedo[c]; max(thr) == 0 ends the path;
+ *         chord, next ray and next jitter as in the conductor step.
+ *   Order of draws at a Lambert hit: the light direction, the phase direction, the shadow jitters (the light's first, only for
+ *   the segments marched), the bounce direction, the next segment's jitter.  This is the one difference from the serial
+ *   reference beside the rejection samplers: the serial code draws the light's jitter before the phase direction, and the staged
+ *   kernels need both directions at set-up (as the conductor step needs its two jitters ahead).
+ * Image, counts, accumulation and the independence of cuts, chunks and tuning options are those of
+ * gpis_render_scene_s_nee_paths_rgb.  Consequences: a table whose entries all equal one conductor gives that entry's frame bit
+ * for bit; on a medium whose ids are all 0, material[1..] changes nothing.  Asynchronous on `stream`. */
+int gpis_render_scene_s_material_paths_rgb(gpis_medium *m, const gpis_scene_s *s, const gpis_materials_s *mats, int max_path_bounces,
+                                           float *radiance_sum3, uint32_t *seg_count, void *stream);
+
+/* gpis_render_scene_s_material_paths_rgb — the same estimator, sample for sample — under the sample schedule of
+ * gpis_render_scene_s_adaptive, exactly as gpis_render_scene_s_nee_paths_rgb_adaptive runs gpis_render_scene_s_nee_paths_rgb: its
+ * pass loop, records, camera step, clamp, luminance statistics and sums.  Refuses what either of those two entries refuses. */
+extern int gpis_render_scene_s_material_paths_rgb_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a,
+                                                           const gpis_materials_s *mats, int max_path_bounces,
+                                                           float *radiance_sum3, uint32_t *sample_count, uint32_t *seg_count,
+                                                           gpis_adaptive_record *records, gpis_adaptive_info *info, void *stream);
+
 /* ---- weight-space GP medium (WeightSpaceGaussianProcessMedium.cpp, WeightSpaceGaussianProcess.cpp) --------------------
  * The field of one realization is  f(p) = sqrt(cov(p,p)) * (sqrt(2/N) * sum_i w_i cos((d_i . p) * omega_i + phi_i)) + mean(p)
  * with N random Fourier features of the squared-exponential covariance (WSG:120-127, 160-240).  A realization is fixed by the

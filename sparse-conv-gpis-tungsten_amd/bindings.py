@@ -221,6 +221,18 @@ SURFACE_S = np.dtype([
 SURFACE_RGB_S = np.dtype([
     ("eta", "<f4", 3), ("k", "<f4", 3), ("albedo", "<f4", 3), ("cap_radiance", "<f4", 3), ("cap_cos", "<f4"), ("_pad", "<f4", 3),
 ], align=True)
+# materials chosen by GP id (gpis_render_scene_s_material_paths_rgb)
+MAX_MATERIALS = 4
+
+
+class MATERIAL:
+    CONDUCTOR, LAMBERT = 0, 1
+
+
+MATERIAL_RGB = np.dtype([("type", "<i4"), ("eta", "<f4", 3), ("k", "<f4", 3), ("albedo", "<f4", 3), ("_pad", "<i4", 2)], align=True)
+MATERIALS_S = np.dtype([
+    ("n_materials", "<u4"), ("cap_cos", "<f4"), ("cap_radiance", "<f4", 3), ("_pad", "<u4", 3), ("material", MATERIAL_RGB, MAX_MATERIALS),
+], align=True)
 
 # variance-driven adaptive sampling (gpis_render_scene_s_adaptive)
 ADAPTIVE_S = np.dtype([("spp_step", "<u4"), ("threshold", "<u4"), ("seed", "<u4"), ("_pad", "<u4")], align=True)
@@ -271,6 +283,18 @@ def default_surface_rgb():
     return s
 
 
+def default_materials():
+    """gpis_default_materials without loading the library: material[0] the copper of default_surface_rgb, material[1] Lambert with
+    albedo 0.8, under default_surface_rgb's cap."""
+    cu = default_surface_rgb()
+    t = np.zeros((), dtype=MATERIALS_S)
+    t["n_materials"], t["cap_cos"], t["cap_radiance"] = 2, cu["cap_cos"], cu["cap_radiance"]
+    m = t["material"]
+    m[0]["type"], m[0]["eta"], m[0]["k"], m[0]["albedo"] = MATERIAL.CONDUCTOR, cu["eta"], cu["k"], cu["albedo"]
+    m[1]["type"], m[1]["albedo"] = MATERIAL.LAMBERT, 0.8
+    return t
+
+
 # ---- weight-space GP medium (include/gpis.h: gpis_ws_*) ----
 WS_MAX_BASIS = 1024
 
@@ -303,7 +327,8 @@ _EXPECTED_SIZES = {
     "gpis_params": PARAMS.itemsize, "gpis_mean": MEAN.itemsize, "gpis_ray_in": RAY_IN.itemsize,
     "gpis_seg_out": SEG_OUT.itemsize, "gpis_cond_coeff": COND_COEFF.itemsize, "gpis_query": QUERY.itemsize,
     "gpis_nee_query": NEE_QUERY.itemsize, "gpis_derived": DERIVED.itemsize, "gpis_scene_s": SCENE_S.itemsize,
-    "gpis_surface_s": SURFACE_S.itemsize, "gpis_surface_rgb_s": SURFACE_RGB_S.itemsize, "gpis_ramp": RAMP.itemsize,
+    "gpis_surface_s": SURFACE_S.itemsize, "gpis_surface_rgb_s": SURFACE_RGB_S.itemsize,
+    "gpis_material_rgb": MATERIAL_RGB.itemsize, "gpis_materials_s": MATERIALS_S.itemsize, "gpis_ramp": RAMP.itemsize,
     "gpis_fs_state": FS_STATE.itemsize, "gpis_guide_info": GUIDE_INFO.itemsize,
     "gpis_ws_params": WS_PARAMS.itemsize, "gpis_ws_query": WS_QUERY.itemsize,
     "gpis_adaptive_s": ADAPTIVE_S.itemsize, "gpis_adaptive_record": ADAPTIVE_RECORD.itemsize, "gpis_adaptive_info": ADAPTIVE_INFO.itemsize,
@@ -459,6 +484,7 @@ class GpisLib:
         "gpis_ws_render_scene_s_adaptive", "gpis_ws_render_scene_s_paths_adaptive",
         "gpis_render_scene_s_paths_adaptive", "gpis_render_scene_s_nee_paths_adaptive",
         "gpis_default_surface_rgb", "gpis_render_scene_s_nee_paths_rgb", "gpis_render_scene_s_nee_paths_rgb_adaptive",
+        "gpis_default_materials", "gpis_render_scene_s_material_paths_rgb", "gpis_render_scene_s_material_paths_rgb_adaptive",
         "gpis_fs_render_scene_s_adaptive", "gpis_fs_render_scene_s_paths_adaptive",
         "gpis_network_mean_host", "gpis_network_mean_batch", "gpis_bake_mean_network",
     ]
@@ -564,6 +590,10 @@ class GpisLib:
         L.gpis_default_surface_rgb.restype = None
         L.gpis_render_scene_s_nee_paths_rgb.argtypes = [vp, vp, vp, i32, vp, vp, vp]
         L.gpis_render_scene_s_nee_paths_rgb_adaptive.argtypes = [vp, vp, vp, vp, i32] + [vp] * 6
+        L.gpis_default_materials.argtypes = [vp]
+        L.gpis_default_materials.restype = None
+        L.gpis_render_scene_s_material_paths_rgb.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+        L.gpis_render_scene_s_material_paths_rgb_adaptive.argtypes = [vp, vp, vp, vp, i32] + [vp] * 6
         L.gpis_ws_render_scene_s_paths_adaptive.argtypes = [vp, vp, vp, i32, i32, ctypes.c_float] + [vp] * 5
         L.gpis_fs_render_scene_s_adaptive.argtypes = [vp] * 9
         L.gpis_fs_render_scene_s_paths_adaptive.argtypes = [vp, vp, vp, i32, ctypes.c_float] + [vp] * 6
@@ -858,6 +888,20 @@ class Medium:
         info) as render_scene_s_paths_rgb_adaptive returns them."""
         surface = np.array(surface, dtype=SURFACE_RGB_S).reshape(())
         return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_nee_paths_rgb_adaptive", scene, (_ptr(surface), int(max_bounces)),
+                            channels=3, has_count=True, want_count=want_segs, adaptive=_adaptive_s(adaptive), want_records=want_records)
+
+    def render_scene_s_material_paths_rgb(self, scene, materials, max_bounces, want_segs=False):
+        """One call of the RGB path driver whose material is chosen per hit by the GP id (gpis_render_scene_s_material_paths_rgb)
+        into zeroed device buffers: what render_scene_s_nee_paths_rgb returns.  `materials`: MATERIALS_S."""
+        materials = np.array(materials, dtype=MATERIALS_S).reshape(())
+        return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_material_paths_rgb", scene, (_ptr(materials), int(max_bounces)),
+                            channels=3, has_count=True, want_count=want_segs)
+
+    def render_scene_s_material_paths_rgb_adaptive(self, scene, materials, max_bounces, adaptive=None, want_segs=False, want_records=False):
+        """One frame of that driver under the reference's adaptive sample schedule (gpis_render_scene_s_material_paths_rgb_adaptive)
+        into zeroed device buffers: what render_scene_s_nee_paths_rgb_adaptive returns."""
+        materials = np.array(materials, dtype=MATERIALS_S).reshape(())
+        return _scene_frame(self.L, self.h, self.device, "gpis_render_scene_s_material_paths_rgb_adaptive", scene, (_ptr(materials), int(max_bounces)),
                             channels=3, has_count=True, want_count=want_segs, adaptive=_adaptive_s(adaptive), want_records=want_records)
 
     def fs_render_scene_s_adaptive(self, scene, adaptive=None, want_hits=False, want_records=False):

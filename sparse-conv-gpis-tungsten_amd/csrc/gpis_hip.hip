@@ -431,11 +431,11 @@ extern "C" const char *gpis_abi_sizes(void)
              "gpis_params=%zu,gpis_mean=%zu,gpis_ray_in=%zu,gpis_seg_out=%zu,gpis_cond_coeff=%zu,gpis_query=%zu,"
              "gpis_nee_query=%zu,gpis_derived=%zu,gpis_scene_s=%zu,gpis_surface_s=%zu,gpis_ramp=%zu,gpis_fs_state=%zu,gpis_guide_info=%zu,"
              "gpis_ws_params=%zu,gpis_ws_query=%zu,gpis_adaptive_s=%zu,gpis_adaptive_record=%zu,gpis_adaptive_info=%zu,gpis_mean_network=%zu,"
-             "gpis_surface_rgb_s=%zu",
+             "gpis_surface_rgb_s=%zu,gpis_material_rgb=%zu,gpis_materials_s=%zu",
              sizeof(gpis_params), sizeof(gpis_mean), sizeof(gpis_ray_in), sizeof(gpis_seg_out), sizeof(gpis_cond_coeff),
              sizeof(gpis_query), sizeof(gpis_nee_query), sizeof(gpis_derived), sizeof(gpis_scene_s), sizeof(gpis_surface_s), sizeof(gpis_ramp), sizeof(gpis_fs_state), sizeof(gpis_guide_info),
              sizeof(gpis_ws_params), sizeof(gpis_ws_query), sizeof(gpis_adaptive_s), sizeof(gpis_adaptive_record), sizeof(gpis_adaptive_info), sizeof(gpis_mean_network),
-             sizeof(gpis_surface_rgb_s));
+             sizeof(gpis_surface_rgb_s), sizeof(gpis_material_rgb), sizeof(gpis_materials_s));
     return buf;
 }
 

@@ -7,6 +7,8 @@
 //                                   gpis_render_scene_s_paths_rgb_adaptive
 //   the conductor NEE / MIS frames  gpis_render_scene_s_nee, gpis_render_scene_s_nee_paths, gpis_render_scene_s_nee_paths_adaptive,
 //                                   gpis_render_scene_s_nee_paths_rgb, gpis_render_scene_s_nee_paths_rgb_adaptive (gpis_cond_rgb.hpp)
+//   materials chosen by GP id       gpis_render_scene_s_material_paths_rgb, gpis_render_scene_s_material_paths_rgb_adaptive
+//                                   (gpis_material_rgb.hpp)
 //   the function-space frames       gpis_fs_render_scene_s, gpis_fs_render_scene_s_paths (fused kernels: tu_fs_scene.hip, tu_fs_paths.hip)
 #include <hip/hip_runtime.h>
 
@@ -785,6 +787,8 @@ __global__ void __launch_bounds__(256) k_nee_paths_gather(float cap_radiance, si
 // ---- the same bounce loop in RGB (gpis_render_scene_s_nee_paths_rgb): k_cond_rgb_setup, k_cond_rgb_emit, k_cond_rgb_shade,
 // k_cond_rgb_gather
 #include "gpis_cond_rgb.hpp"
+// ---- and with the material of a hit chosen by its GP id (gpis_render_scene_s_material_paths_rgb): k_mat_rgb_setup, k_mat_rgb_shade
+#include "gpis_material_rgb.hpp"
 
 // ---- scene S driver ----------------------------------------------------------------------
 extern "C" void gpis_default_scene_s(gpis_scene_s *s, uint32_t width, uint32_t height, uint32_t spp)
@@ -1687,9 +1691,9 @@ struct CondRgbWs {
     float *lum;                        // adaptive entry only
     uint8_t *clamped;
 };
-static void cond_rgb_carve(CondRgbWs &W, size_t ns_max, bool emissive, bool adaptive)
+static void cond_rgb_carve(CondRgbWs &W, size_t ns_max, bool emissive, bool adaptive, size_t aux_bytes = sizeof(NeeAuxN<3>))
 {
-    nee_carve(W.nee, ns_max, true, sizeof(NeeAuxN<3>));
+    nee_carve(W.nee, ns_max, true, aux_bytes);
     size_t off = W.nee.bytes;
     auto carve = [&](size_t bytes) { return ws_carve(off, bytes); };
     W.o_thr = carve(ns_max * 12); W.o_th = carve(ns_max * 12); W.o_em = carve(ns_max * 12); W.o_cl = carve(ns_max * 12); W.o_cp = carve(ns_max * 12);
@@ -1827,6 +1831,158 @@ extern "C" int gpis_render_scene_s_nee_paths_rgb_adaptive(gpis_medium *m, const 
         [&](const AdaptiveChunk &ch, size_t ns, gpis_adaptive_record *d_records) {
             return cond_rgb_chunk(
                 m, sc, surf, W, ns, max_path_bounces, st,
+                [&] {
+                    k_paths_adaptive_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, ch, ns, W.nee.a);
+                    return launch_check("k_paths_adaptive_begin");
+                },
+                [&] {
+                    k_rgb_adaptive_value<0><<<grid_of(ns, 256), 256, 0, st>>>(ns, W.r.plane, W.r.em, W.lum, W.clamped);
+                    if (int rc = launch_check("k_rgb_adaptive_value")) return rc;
+                    k_rgb_adaptive_accumulate<0><<<grid_of((size_t)ch.nrec * (kVarianceTile * kVarianceTile), 256), 256, 0, st>>>(
+                        sc, ch, W.r.plane, W.r.em, W.clamped, W.nee.c.segs, radiance_sum3, sample_count, seg_count);
+                    if (int rc = launch_check("k_rgb_adaptive_accumulate")) return rc;
+                    k_rgb_adaptive_stats<0><<<grid_of(ch.nrec, 256), 256, 0, st>>>(ch, W.lum, d_records);
+                    return launch_check("k_rgb_adaptive_stats");
+                });
+        });
+}
+
+// ---- materials chosen by GP id: the RGB conductor driver's workspace (its aux slots sized for MatAux) and its chunk body around
+// k_mat_rgb_setup / k_mat_rgb_shade; the emission add and the gather are the conductor driver's kernels.
+static void mat_rgb_carve(CondRgbWs &W, size_t ns_max, bool emissive, bool adaptive)
+{
+    cond_rgb_carve(W, ns_max, emissive, adaptive, sizeof(MatAux));
+}
+template <typename Begin, typename Finish>
+static int mat_rgb_chunk(gpis_medium *m, const SceneConst &sc, const gpis_materials_s *mats, const CondRgbWs &W, size_t ns, int max_path_bounces,
+                         hipStream_t st, Begin begin, Finish finish)
+{
+    const PathArrays &a = W.nee.a;
+    const NeeArrays &b = W.nee.b;
+    const NeePathArrays &c = W.nee.c;
+    const CondRgbArrays &r = W.r;
+    MatAux *aux = (MatAux *)r.aux;
+    const int emissive = m->host_model.emission.enabled != 0 ? 1 : 0;
+    const int n_marched = emissive ? max_path_bounces : max_path_bounces - 1;
+    int rc = GPIS_OK;
+    if ((rc = begin())) return rc;
+    HIP_TRY(hipMemsetAsync(c.segs, 0, ns * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(r.em, 0, 3 * r.plane * sizeof(float), st));
+    for (int bounce = 0; bounce < n_marched; ++bounce) {
+        const int hint = bounce > 0 ? MARCH_SCATTERED : MARCH_COHERENT;
+        if ((rc = sample_distance_impl(m, ns, a.rays, a.seg, b.coeff, a.alive, st, hint))) return rc;
+        k_mat_rgb_setup<<<grid_of(ns, 256), 256, 0, st>>>(sc, *mats, ns, bounce, max_path_bounces, emissive, a, b, c, r, aux);
+        if ((rc = launch_check("k_mat_rgb_setup"))) return rc;
+        if (emissive) {
+            if ((rc = gpis_mean_color_emission_batch(m, ns, r.points, nullptr, r.e3, st))) return rc;
+            k_cond_rgb_emit<<<grid_of(ns, 256), 256, 0, st>>>(ns, bounce, r);
+            if ((rc = launch_check("k_cond_rgb_emit"))) return rc;
+        }
+        if (bounce + 1 >= max_path_bounces) break;      // the extra last segment: no estimator and no bounce follow it
+        if ((rc = nee_queries(m, b, ns, st))) return rc;
+        k_mat_rgb_shade<<<grid_of(ns, 256), 256, 0, st>>>(sc, *mats, ns, bounce, n_marched, a, b, c, r, aux);
+        if ((rc = launch_check("k_mat_rgb_shade"))) return rc;
+        if ((rc = nee_shadow_marches(m, b, ns, st, hint))) return rc;
+        k_cond_rgb_gather<<<grid_of(ns, 256), 256, 0, st>>>(mats->cap_radiance[0], mats->cap_radiance[1], mats->cap_radiance[2], ns, b, r);
+        if ((rc = launch_check("k_cond_rgb_gather"))) return rc;
+    }
+    return finish();
+}
+
+extern "C" void gpis_default_materials(gpis_materials_s *mats)
+{
+    memset(mats, 0, sizeof *mats);
+    gpis_surface_rgb_s cu;
+    gpis_default_surface_rgb(&cu);
+    mats->n_materials = 2;
+    mats->cap_cos = cu.cap_cos;
+    mats->material[0].type = GPIS_MATERIAL_CONDUCTOR;
+    mats->material[1].type = GPIS_MATERIAL_LAMBERT;
+    for (int c = 0; c < 3; ++c) {
+        mats->cap_radiance[c] = cu.cap_radiance[c];
+        mats->material[0].eta[c] = cu.eta[c]; mats->material[0].k[c] = cu.k[c]; mats->material[0].albedo[c] = cu.albedo[c];
+        mats->material[1].albedo[c] = 0.8f;
+    }
+}
+
+static bool materials_ok(const gpis_materials_s *mats)
+{
+    if (!mats || mats->n_materials < 1 || mats->n_materials > GPIS_MAX_MATERIALS) return false;
+    for (uint32_t k = 0; k < mats->n_materials; ++k)
+        if (mats->material[k].type != GPIS_MATERIAL_CONDUCTOR && mats->material[k].type != GPIS_MATERIAL_LAMBERT) return false;
+    return mats->cap_cos < 1.0f && mats->cap_cos > -1.0f;
+}
+
+extern "C" int gpis_render_scene_s_material_paths_rgb(gpis_medium *m, const gpis_scene_s *s, const gpis_materials_s *mats, int max_path_bounces,
+                                                      float *radiance_sum3, uint32_t *seg_count, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && radiance_sum3 && max_path_bounces >= 1);
+    CHECK_ARGS(scene_args_ok(s));
+    CHECK_ARGS(materials_ok(mats));
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(m->mu);
+    HIP_TRY(hipSetDevice(m->device));
+    const SceneConst sc = make_scene_const(s);
+    const size_t total_pixels = scene_rows(*s) * s->width;
+    CondRgbWs W;
+    size_t chunk_pixels = 0;
+    int rc = GPIS_OK;
+    for (int l = chunk_log2(m, 27);; --l) {        // the chunks of gpis_render_scene_s_nee_paths_rgb
+        chunk_pixels = chunk_pixels_of(l, s->spp_count, total_pixels);
+        mat_rgb_carve(W, chunk_pixels * s->spp_count, m->host_model.emission.enabled != 0, false);
+        if (try_stage(m, 3, W.bytes))
+            break;
+        if (l <= 20) return set_err(GPIS_ERR_DEVICE, "material driver: no memory for a 1 Mi-sample workspace");
+    }
+    if ((rc = ws_acquire(m, 0, st))) return rc;
+    cond_rgb_bind(m, W);
+    for (size_t p0 = 0; p0 < total_pixels; p0 += chunk_pixels) {
+        const size_t np = total_pixels - p0 < chunk_pixels ? total_pixels - p0 : chunk_pixels;
+        const size_t ns = np * s->spp_count;
+        rc = mat_rgb_chunk(
+            m, sc, mats, W, ns, max_path_bounces, st,
+            [&] {
+                k_paths_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, p0, ns, W.nee.a);
+                return launch_check("k_paths_begin");
+            },
+            [&] {
+                if (seg_count) {
+                    k_scene_sum_u32<<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, W.nee.c.segs, seg_count);
+                    if (int r = launch_check("k_scene_sum_u32")) return r;
+                }
+                k_paths_rgb_accumulate<0><<<grid_of(np, 256), 256, 0, st>>>(sc, p0, np, W.r.plane, W.r.em, radiance_sum3);
+                return launch_check("k_paths_rgb_accumulate");
+            });
+        if (rc) return rc;
+    }
+    return ws_release(m, 0, st);
+}
+
+extern "C" int gpis_render_scene_s_material_paths_rgb_adaptive(gpis_medium *m, const gpis_scene_s *s, const gpis_adaptive_s *a,
+                                                               const gpis_materials_s *mats, int max_path_bounces, float *radiance_sum3,
+                                                               uint32_t *sample_count, uint32_t *seg_count, gpis_adaptive_record *records,
+                                                               gpis_adaptive_info *info, void *stream)
+{
+    CHECK_ARGS(std_handle(m) && s && a && radiance_sum3 && sample_count && max_path_bounces >= 1);
+    CHECK_ARGS(scene_args_ok(s));
+    CHECK_ARGS(materials_ok(mats));
+    hipStream_t st = (hipStream_t)stream;
+    const SceneConst sc = make_scene_const(s);
+    CondRgbWs W;
+    return adaptive_passes(
+        MediumPasses{m, 27}, s, a, __func__, st, records, info,
+        [&](size_t n, bool &fits) {
+            mat_rgb_carve(W, n, m->host_model.emission.enabled != 0, true);
+            fits = try_stage(m, 3, W.bytes);
+            return (int)GPIS_OK;
+        },
+        [&]() {
+            cond_rgb_bind(m, W);
+            return (int)GPIS_OK;
+        },
+        [&](const AdaptiveChunk &ch, size_t ns, gpis_adaptive_record *d_records) {
+            return mat_rgb_chunk(
+                m, sc, mats, W, ns, max_path_bounces, st,
                 [&] {
                     k_paths_adaptive_begin<<<grid_of(ns, 256), 256, 0, st>>>(sc, ch, ns, W.nee.a);
                     return launch_check("k_paths_adaptive_begin");
